@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- reads/sec of the MI355X hot path (libsmr_hip) on BASELINE.json's headline workload.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload illumina150|refs8|pacbio5k]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload illumina150|refs8|pacbio5k] [--dump-outputs DIR] [--full]
   (N > 1: one rank per GPU; started by torch.distributed.run, or by this script itself when no launcher is around it)
+
+A plain run sets up, warms up, times the K steps and prints the JSON line.  --dump-outputs DIR also writes the results of the last timed
+step as DIR/<name>.npy (dump_outputs() below).  --full adds the passes beside the headline: the exact-count pass (work_per_read,
+roofline.equivalent_rate), the N = 1 configuration of a multi-rank run (efficiency_vs_n1), the PCIe-inclusive leg and the CPU baseline.
 
 --workload: illumina150 (default) = BASELINE.json configs[2], the configuration the metric is quoted on (below);
             refs8    = configs[3]: the same reads against EIGHT resident reference DBs (bundled silva-arc-16s-id95 + 7 seeded synthetic ones
@@ -32,7 +36,7 @@ The JSON line also carries
                 the REFERENCE's traversal would move for the same reads (SURVEY.md 8d formula) only as `equivalent_rate`
   kernels       HIP-event time and launch count of each kernel family in the timed region
   cpu_baseline  the UNMODIFIED reference (oracle/_ref/sortmerna_ref) timed on this host's cores on a bounded sample of
-                the same reads with the same index files (rank 0, N=1 only)
+                the same reads with the same index files (rank 0, N=1 only, --full)
 """
 import argparse
 import json
@@ -176,6 +180,64 @@ def cpu_baseline(args, dbs, parts_per_db, sample, smr, eng, idx_slots):
         return res
     finally:
         shutil.rmtree(wd, ignore_errors=True)
+
+
+DUMP_SEED = 20240611          # the fixed sample of reads whose results --dump-outputs writes
+DUMP_MAX_BYTES = 64 << 20
+
+
+def parse_record(b):
+    """Read::toBinString bytes of smr_result_record (read.cpp:429-462, ssw.hpp:106-140) -> (header fields, [(alignment fields, cigar)])"""
+    import struct
+    head = struct.unpack_from("<6I3BHiIQ2IQ", b, 0)
+    o, al = 61, []
+    for _ in range(head[-1]):
+        _, cl = struct.unpack_from("<QQ", b, o)
+        cig = struct.unpack_from("<%dI" % cl, b, o + 16)
+        o += 16 + 4 * cl
+        al.append((struct.unpack_from("<IiiiiIHHHB", b, o), cig))
+        o += 31
+    assert o == len(b), (o, len(b))
+    return head, al
+
+
+def dump_outputs(eng, batch, n_db, long_reads, out_dir):
+    """What the last timed step handed back for its batch, as float64 .npy files (every value is an integer below 2^53):
+      counters     [num_aligned, num_short, reads_matched_per_db...]
+      read_index   the reads whose results follow: a fixed seeded sample of up to 131072 reads of the batch (2048 for reads over 512 nt)
+      read_fields  per sampled read: has_record, then its record's header (6 x u32 lastIndex, lastPart, ..., is_done, is_hit,
+                   null_align_output, max_SW_count, num_alignments, hit_seeds, alignv size, min_index, max_index, number of alignments)
+      alignments   per alignment: row in read_index, ref_num, ref_begin1, ref_end1, read_begin1, read_end1, readlen, score1, part,
+                   index_num, strand, CIGAR length
+      cigar        the alignments' CIGAR words (length << 4 | op), concatenated in alignment order"""
+    import numpy as np
+    n = eng.n_reads                                          # (the batch is the selected one)
+    cap = 2048 if long_reads else 1 << 17
+    idx = np.arange(n) if n <= cap else np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(n, cap, replace=False))
+    ctr = eng.counters(n_db)
+    rows, al_rows, cig = [], [], []
+    for k, i in enumerate(idx):
+        b = eng.record(int(i))
+        if not b:
+            rows.append([0] * 17)
+            continue
+        head, al = parse_record(b)
+        rows.append([1] + list(head))
+        for f, c in al:
+            al_rows.append([k] + list(f) + [len(c)])
+            cig.extend(c)
+    files = {"counters": np.array([ctr["num_aligned"], ctr["num_short"]] + list(ctr["reads_matched_per_db"][:n_db]), dtype=np.float64),
+             "read_index": idx.astype(np.float64),
+             "read_fields": np.array(rows, dtype=np.float64).reshape(-1, 17),
+             "alignments": np.array(al_rows, dtype=np.float64).reshape(-1, 12),
+             "cigar": np.array(cig, dtype=np.float64)}
+    total = sum(a.nbytes for a in files.values())
+    if total > DUMP_MAX_BYTES:
+        sys.exit("--dump-outputs: %d bytes would exceed the limit of %d" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("outputs of the last timed step (batch %d, %d of its %d reads) written to %s (%.1f MB)" % (batch, len(idx), n, out_dir, total / 1e6))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -339,6 +401,20 @@ def make_shard(args, synth, codes, offs, rank, world):
     return b"".join(blobs), np.concatenate(offl)
 
 
+def make_packed(L, b, sample_reads, make, *a):
+    """make(*a) -> (blob, offsets), packed by smr_reads_pack -> (handle, offsets, the first sample_reads reads of batch 0 or None).
+    Runs on a host thread: numpy and the ctypes call release the GIL, so the batches are made and packed side by side."""
+    import ctypes as C
+    blob, o = make(*a)
+    sample = None
+    if b == 0 and sample_reads > 0:
+        ns = min(len(o) - 1, sample_reads)
+        sample = (blob[:int(o[ns])], o[:ns + 1].copy())
+    h = C.c_void_p()
+    assert L.smr_reads_pack(blob, o.ctypes.data, len(o) - 1, C.byref(h)) == 0
+    return h, o, sample
+
+
 def self_launch(n):
     """`python bench.py --gpus N ...` without a launcher: start the N ranks (one per GPU) through torch.distributed.run on this node,
     exactly as the driver's wrapped command would, and hand their output and exit code through.  Rank 0 prints the JSON line."""
@@ -382,6 +458,12 @@ def main():
     ap.add_argument("--n1-value", type=float, default=0.0, help="--scaling strong: the value of the same command at --gpus 1; the line then carries efficiency_vs_n1 = value / (N x that)")
     ap.add_argument("--resident-batches", type=int, default=0,
                     help="distinct read batches kept resident in HBM (1..%d); step i runs on batch i %% this; 0 = as many as hold 16 M reads, between 2 and 8" % MAX_RESIDENT)
+    ap.add_argument("--full", action="store_true",
+                    help="also the passes that are not the headline: exact-count pass (work_per_read, equivalent_rate, the two seed kernels' num_aligned "
+                         "compared), the N = 1 configuration of a multi-rank run, the PCIe-inclusive leg and the CPU baseline of the reference")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (counters, and the per-read results of a fixed seeded "
+                         "sample of its batch) as DIR/<name>.npy in float64")
     args = ap.parse_args()
 
     t_process = time.time()                                  # set-up (DBs, index replica, resident batches) is timed per rank and reported: config.setup_s
@@ -406,6 +488,8 @@ def main():
     args.db_nt = args.db_nt or (14_000_000 if args.workload == "pacbio5k" else 3_770_000 if args.workload == "config2" else 140_000_000)
     if args.resident_batches <= 0:
         args.resident_batches = max(2, min(8, 16_000_000 // max(args.batch_reads, 1)))
+    # a plain run does what its headline needs; the passes beside it (exact counts, N = 1 configuration, PCIe leg, CPU baseline) need --full
+    extras = args.full and not args.profile_run
 
     import numpy as np
     import torch
@@ -445,6 +529,22 @@ def main():
     dbs = [p for _, p in dbl]
     log("%d DB file(s) ready (%.1fs)" % (len(dbs), time.time() - t0))
     barrier()
+    # the read batches are generated and packed on host threads while the index is built on the GPU: W + K different batches per rank,
+    # resident in HBM below; batch b is a function of (arguments, rank, b) only, whichever thread makes it
+    codes, offs = load_all_codes(synth, dbs)
+    n_total = args.warmup + args.steps              # step i (warmup first, then timed) runs on resident batch i % nb
+    nb = max(1, min(n_total, args.resident_batches, MAX_RESIDENT))
+    if args.workload == "config2":
+        config2_reads()                                      # (loaded once, before the threads share it)
+    from concurrent.futures import ThreadPoolExecutor
+    from sortmerna_amd import capi
+    L = capi.load()
+    gen = ThreadPoolExecutor(max_workers=min(nb, 8))
+    ns = args.cpu_sample_reads if extras else 0                # (the CPU baseline's sample: the first reads of batch 0)
+    if args.scaling == "strong":
+        batch_futs = [gen.submit(make_packed, L, b, ns, make_shard, args, synth, codes, offs, rank, world) for b in range(nb)]
+    else:
+        batch_futs = [gen.submit(make_packed, L, b, ns, make_batch, args, synth, codes, offs, args.batch_reads, 1234 + 1000 * rank + b) for b in range(nb)]
     t0 = time.time()
     eng = smr.Engine(local)
     # sorting / ids / positions / mini-tries as device kernels (seconds for 140 Mnt).  With several ranks every rank builds
@@ -475,27 +575,16 @@ def main():
 
     # ---------------- reads: W + K different batches per rank, resident in HBM ----------------
     t0 = time.time()
-    codes, offs = load_all_codes(synth, dbs)
-    n_total = args.warmup + args.steps              # step i (warmup first, then timed) runs on resident batch i % nb
-    nb = max(1, min(n_total, args.resident_batches, MAX_RESIDENT))
     sample0 = None
     tot_reads = tot_len = 0
     min_len, max_len = 1 << 30, 0
-    import ctypes as C
     shard_reads = []                                         # reads of every resident batch of this rank
     for b in range(nb):
-        if args.scaling == "strong":
-            blob, o = make_shard(args, synth, codes, offs, rank, world)
-        else:
-            blob, o = make_batch(args, synth, codes, offs, args.batch_reads, 1234 + 1000 * rank + b)
-        nrb = len(o) - 1
-        shard_reads.append(nrb)
+        h, o, sample = batch_futs[b].result()
+        batch_futs[b] = None
+        shard_reads.append(len(o) - 1)
         if b == 0:
-            ns = min(nrb, args.cpu_sample_reads)
-            sample0 = (blob[:int(o[ns])], o[:ns + 1].copy())
-        h = C.c_void_p()
-        rc = eng.L.smr_reads_pack(blob, o.ctypes.data, nrb, C.byref(h))
-        assert rc == 0
+            sample0 = sample
         r = smr.Reads(h)
         eng.select_batch(b)
         eng.upload_reads(r, 1)
@@ -506,6 +595,7 @@ def main():
             last_packed = r                                  # kept on the host for the PCIe-inclusive measurement below
         else:
             r.free()
+    gen.shutdown()
     del codes, offs
     log("%d batch(es) of %s reads resident, %.0f nt per read (%.1fs)" % (nb, "/".join(str(x) for x in sorted(set(shard_reads))), tot_len / max(tot_reads, 1), time.time() - t0))
     reads_per_step = shard.reduce_counters([shard_reads[0]], device=cdev)[0] if args.scaling == "strong" else args.gpus * args.batch_reads
@@ -534,24 +624,25 @@ def main():
     timed = [i % nb for i in range(args.warmup, n_total)]        # the resident batch of every timed step
     uses = [timed.count(b) for b in range(nb)]
     # Algorithmic bytes of the timed steps: a workload property, counted once per distinct batch by the per-lane DFS seed kernel whose
-    # work counters follow the reference's sequential scan exactly (untimed; the timed steps use the pigeonhole kernel, same results).
-    eng.set_seed_mode(1)
+    # work counters follow the reference's sequential scan exactly (untimed; the timed steps use the pigeonhole kernel, same results).  --full only.
     exact = [0] * 6
-    exact_aligned = None if args.profile_run else 0
-    for b in range(nb):
-        if uses[b] == 0 or args.profile_run:
-            continue
-        eng.prof_reset()
-        step(b)
-        pe = eng.prof()
-        for k, v in enumerate([pe.n_windows, pe.n_lookup, pe.n_node, pe.n_entry, pe.n_hit, pe.n_read_bytes]):
-            exact[k] += int(v) * uses[b]
-        exact_aligned += eng_counters_aligned(eng, b) * uses[b]
-    eng.set_seed_mode(0)
+    exact_aligned = 0 if extras else None
+    if extras:
+        eng.set_seed_mode(1)
+        for b in range(nb):
+            if uses[b] == 0:
+                continue
+            eng.prof_reset()
+            step(b)
+            pe = eng.prof()
+            for k, v in enumerate([pe.n_windows, pe.n_lookup, pe.n_node, pe.n_entry, pe.n_hit, pe.n_read_bytes]):
+                exact[k] += int(v) * uses[b]
+            exact_aligned += eng_counters_aligned(eng, b) * uses[b]
+        eng.set_seed_mode(0)
     # N > 1, weak scaling: the N = 1 configuration of THIS run -- rank 0 alone, its GPU, its batches, the same timed steps, while the other ranks wait --
     # so that the line carries efficiency_vs_n1 = value / (N x that) from one process tree and one DB cache (the driver computes its own from its N = 1 run)
     n1_value = None
-    if world > 1 and args.scaling == "weak" and not args.profile_run:
+    if world > 1 and args.scaling == "weak" and extras:
         barrier()
         if rank == 0:
             t1 = time.perf_counter()
@@ -591,16 +682,19 @@ def main():
         dist.all_reduce(prof)
     prof = [float(x) for x in prof.cpu()]
     kp = {k: {"ms": prof[17 + 3 * i], "launches": prof[18 + 3 * i], "bytes": prof[19 + 3 * i]} for i, k in enumerate(kp_names)}      # sums over ranks
+    if args.dump_outputs and rank == 0:
+        eng.select_batch(timed[-1])
+        dump_outputs(eng, timed[-1], n_db, max_len > 512, args.dump_outputs)
 
     # informational: the same step when the boundary hands over a HOST buffer (packed batch -> smr_reads_upload: allocations + H2D over
     # PCIe + state reset), serial, no overlap with the previous batch.  Never `value`.
     t0 = time.perf_counter()
-    for _ in range(0 if args.profile_run else 2):
+    for _ in range(2 if extras else 0):
         eng.select_batch(nb - 1)
         eng.upload_reads(last_packed, 1)
         smr.align_resident(eng, idx_slots, plist, with_cigar=not args.no_cigar)
     torch.cuda.synchronize()
-    pcie_rate = None if args.profile_run else 2 * shard_reads[nb - 1] / (time.perf_counter() - t0)
+    pcie_rate = None if not extras else 2 * shard_reads[nb - 1] / (time.perf_counter() - t0)
     last_packed.free()
 
     if rank == 0:
@@ -659,7 +753,7 @@ def main():
                 "kernels": rk,
                 "seed_stage": {"achieved": st_bytes / max(st_ms * 1e-3, 1e-12) / 1e9, "frac": st_bytes / max(st_ms * 1e-3, 1e-12) / 1e9 / HBM_PEAK_GBS,
                                "algorithmic_bytes_per_launch": st_bytes / max(seed_l, 1), "avg_launch_ms": st_ms / max(seed_l, 1), "bytes_per_read": st_bytes / reads_timed},
-                "equivalent_rate": {"GB/s": (b_ref / max(st_ms * 1e-3, 1e-12) / 1e9) if b_ref else None, "bytes_per_read": b_ref / reads_timed,
+                "equivalent_rate": None if exact_aligned is None else {"GB/s": (b_ref / max(st_ms * 1e-3, 1e-12) / 1e9) if b_ref else None, "bytes_per_read": b_ref / reads_timed,
                                     "note": "bytes the REFERENCE's trie traversal would move for these reads (SURVEY.md 8d formula on exact counters) / the seed stage's time; "
                                             "not a roofline figure: the shipped search reaches the same hits without that traversal"},
                 "note": "kernel = the seed-stage kernel with the most time in the timed steps; achieved = the algorithmic HBM bytes THAT kernel counts for itself on the device "
@@ -720,7 +814,7 @@ def main():
                        "walk_rounds_per_pass": eng.walk_rounds(), "hit_list_entries_per_search": int(eng.prof().hit_list_cap)},
             "pcie_inclusive_reads_per_s_per_gpu": pcie_rate,
             "counters": {"reads": reads_timed, "num_aligned": int(ctr_t[0]), "num_short": int(ctr_t[1]), "reads_matched_per_db": [int(x) for x in ctr_t[2:2 + n_db]]},
-            "work_per_read": {"windows": prof[6] / reads_timed, "lookups": n_lookup / reads_timed, "nodes": n_node / reads_timed,
+            "work_per_read": None if exact_aligned is None else {"windows": prof[6] / reads_timed, "lookups": n_lookup / reads_timed, "nodes": n_node / reads_timed,
                               "entries": n_entry / reads_timed, "hits": n_hit / reads_timed},
             "roofline": roof,
             "kernels": {"k_seed": {"ms": seed_ms / args.gpus, "launches": seed_l / args.gpus},
@@ -745,7 +839,7 @@ def main():
         if n1_value:
             out["n1_value_rank0_alone"] = n1_value
             out["efficiency_vs_n1"] = out["value"] / (args.gpus * n1_value)
-        if args.gpus == 1 and not args.no_cpu_baseline and not args.profile_run:
+        if args.gpus == 1 and not args.no_cpu_baseline and extras:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, dbs, parts_per_db, sample0, smr, eng, idx_slots)
             except Exception as e:  # the baseline must never lose the measured GPU number

@@ -28,7 +28,7 @@ def test_bench_control_flow_on_the_emulator(monkeypatch, tmp_path, steps, warmup
     monkeypatch.setattr(tempfile, "tempdir", str(tmp_path))
     nreads = 60 if workload == "pacbio5k" else (300 if steps > 2 else 1500)      # (config2: the first 1500 reads of the bundled read set vs the whole bundled DB)
     argv = ["bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--batch-reads", str(nreads), "--db-nt", "1000000" if workload == "refs8" else "150000",
-            "--cpu-sample-reads", str(nreads), "--cpu-threads", "2", "--workload", workload, "--long-read-len", "600"]
+            "--cpu-sample-reads", str(nreads), "--cpu-threads", "2", "--workload", workload, "--long-read-len", "600", "--full"]
     if not baseline:
         argv.append("--no-cpu-baseline")
     monkeypatch.setattr(sys, "argv", argv)
@@ -71,7 +71,7 @@ def test_unwrapped_multi_rank_command(tmp_path):
     env = dict(os.environ, TMPDIR=str(tmp_path), SMR_BENCH_BACKEND="gloo", SMR_BENCH_DEVICE="0")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
     cmd = [sys.executable, os.path.join(paths.REPO, "tests", "helpers", "bench_on_emu.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch-reads", "1200", "--db-nt", "150000", "--no-cpu-baseline"]
+           "--batch-reads", "1200", "--db-nt", "150000", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
@@ -126,3 +126,49 @@ def test_the_traffic_file_belongs_to_the_seed_kernels_in_the_tree():
     if tj["kernel_src_sha"] != pmc_traffic.kernel_src_sha():
         warnings.warn("profiles/hbm_traffic.json was measured on other seed-stage sources (%s, tree: %s): bench.py will print roofline.traffic = null"
                       % (tj["kernel_src_sha"], pmc_traffic.kernel_src_sha()))
+
+
+def _run_bench_on_emu(monkeypatch, tmp_path, extra):
+    import torch
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    monkeypatch.setenv("TMPDIR", str(tmp_path))
+    monkeypatch.setenv("SMR_BENCH_BACKEND", "gloo")
+    import tempfile
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path))
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch-reads", "1500", "--db-nt", "150000",
+                                      "--cpu-threads", "2"] + extra)
+    sys.path.insert(0, paths.REPO)
+    import importlib
+    bench = importlib.import_module("bench")
+    buf = io.StringIO()
+    with emu.active(), redirect_stdout(buf):
+        bench.main()
+    return json.loads([l for l in buf.getvalue().splitlines() if l.startswith("{")][-1])
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(monkeypatch, tmp_path):
+    """Without --full the line has its headline keys and none of the side passes (exact counts, PCIe leg, CPU baseline); --dump-outputs
+    writes the last timed step's results as float64 arrays, and a --full run of the same command writes the same arrays."""
+    import numpy as np
+    out = _run_bench_on_emu(monkeypatch, tmp_path, ["--dump-outputs", str(tmp_path / "plain")])
+    for k in KEYS:
+        assert k in out, k
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["unit"] == "reads/s" and out["value"] > 0 and out["dtype"] == "u8/i32"
+    assert abs(out["ms_per_step"] * 2 / 1e3 * out["value"] - 2 * 1500) < 1e-3
+    assert out["cpu_baseline"] is None and out["pcie_inclusive_reads_per_s_per_gpu"] is None and out["work_per_read"] is None
+    d = tmp_path / "plain"
+    names = ["counters", "read_index", "read_fields", "alignments", "cigar"]
+    arr = {n: np.load(d / (n + ".npy")) for n in names}
+    assert all(a.dtype == np.float64 for a in arr.values()) and sum(a.nbytes for a in arr.values()) <= 64 << 20
+    assert arr["read_index"].tolist() == list(range(1500)) and arr["read_fields"].shape == (1500, 17)
+    # the counters are those of the last timed step's batch alone: they agree with its records
+    ctr, rf, al = arr["counters"], arr["read_fields"], arr["alignments"]
+    assert len(ctr) == 3 and ctr[0] == (rf[:, 8] == 1).sum() > 0 and ctr[2] == ctr[0]
+    assert al.shape[1] == 12 and len(al) >= ctr[0] and set(al[:, 0].astype(int)) == set(np.nonzero(rf[:, 16])[0])
+    assert al[:, 11].sum() == len(arr["cigar"]) > 0
+    full = _run_bench_on_emu(monkeypatch, tmp_path, ["--dump-outputs", str(tmp_path / "full"), "--full", "--no-cpu-baseline"])
+    assert full["work_per_read"] is not None and full["pcie_inclusive_reads_per_s_per_gpu"] > 0
+    for n in names:
+        assert np.array_equal(arr[n], np.load(tmp_path / "full" / (n + ".npy"))), n
