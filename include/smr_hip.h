@@ -203,6 +203,9 @@ int smr_index_check_device(smr_ctx*, int slot, smr_index*);
  * (meta = {tuples, forward tuples, coarse bins, fine key bits, char bits, forward keys, candidate records per wave, waves handed to the DFS kernel}). */
 int smr_index_pigeonhole(smr_index*, const uint32_t** pg, uint64_t* pg_words, const uint32_t** root3, uint64_t* root3_words, char* err, size_t errcap);
 int smr_seed_tuples_fetch(smr_ctx*, uint64_t* tuples, uint64_t cap_tuples, uint32_t* cbase, uint32_t cap_cbase, uint32_t meta[8]);
+/* Test seam of the seed-hit pool (SMR_SEED_POOL_WORDS=<n> starts it at n words, clamped to [64, 0x7FFFFFF0]): info = {pool words, regrows
+ * since smr_create, one past the highest pool word the selected batch's last seed stage handed out, 1 if that stage inlined one-hit windows}. */
+int smr_seed_pool_info(smr_ctx*, uint64_t info[4]);
 int smr_index_unload(smr_ctx*, int slot);
 
 /* Several read batches (0..15) can be resident at once, so the host can upload batch k+1 while batch k is being

@@ -86,6 +86,8 @@ struct smr_ctx {
   Batch* b = &bt[0];
   // pools / scratch (shared by all batches: one batch is aligned at a time)
   uint32_t* d_pool = nullptr; uint64_t pool_words = 0;
+  uint64_t n_pool_grown = 0;              // seed-hit pool regrows (C_ERR_POOL) since smr_create (smr_seed_pool_info)
+  uint32_t pool_inline = 0;               // SeedBufs::seg_inline of the last seed-stage launch (smr_seed_pool_info)
   uint32_t hcap = 4;                      // lane-local hit list capacity of k_seed_search; doubles (and the part is redone) on overflow
   int seed_exact = 0;                     // 1: k_seed_search for every wave (exact work counters); 0: k_seed_pg (+ redo of the waves whose pool overflowed)
   // Bloom words per read in k_cand (a power of two, 64..512): fewer = more blocks of k_cand per CU, but more reads marked for k_chain by a false
@@ -621,8 +623,18 @@ extern "C" int smr_reads_upload_batch(smr_ctx* c, int batch, const smr_reads* r,
 
 namespace {
 int ensure_pool(smr_ctx* c) {          // seed-hit pool: scratch shared by all batches, sized for the selected one before its kernels run
-  const uint64_t want_pool = std::max<uint64_t>((uint64_t)c->b->n * 64 + (1u << 20), 1u << 22);
+  uint64_t want_pool = std::max<uint64_t>((uint64_t)c->b->n * 64 + (1u << 20), 1u << 22);
+  if (const char* e = getenv("SMR_SEED_POOL_WORDS"))          // test aid: start the pool small (regrow) or large (offsets above 2^30)
+    want_pool = std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 0), C_NSHARD), 0x7FFFFFF0ull);
   if (c->pool_words < want_pool) { int rc = dev_alloc(c, &c->d_pool, want_pool); if (rc) return rc; c->pool_words = want_pool; }
+  return SMR_OK;
+}
+
+int grow_pool(smr_ctx* c) {            // a seed kernel found its shard of the pool full (C_ERR_POOL): twice the words, the attempt is redone
+  const uint64_t w = c->pool_words * 2;
+  if (w > 0x7FFFFFF0ull) { set_err(c, "seed-hit pool exceeds 8 GiB"); return SMR_ERR_CAPACITY; }
+  int rc = dev_alloc(c, &c->d_pool, w); if (rc) return rc;
+  c->pool_words = w; c->n_pool_grown++;
   return SMR_OK;
 }
 }  // namespace
@@ -702,8 +714,7 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
     ev_collect(c);
     bool retry = false;
     if (h[C_ERR_HITCAP]) { if (!grow_hcap(c, P.partialwin)) return SMR_ERR_CAPACITY; retry = true; }
-    if (h[C_ERR_POOL]) { uint64_t w = c->pool_words * 2; if (w > 0x7FFFFFF0ull) { set_err(c, "seed-hit pool exceeds 8 GiB"); return SMR_ERR_CAPACITY; }
-      if ((rc = dev_alloc(c, &c->d_pool, w))) return rc; c->pool_words = w; retry = true; }
+    if (h[C_ERR_POOL]) { if ((rc = grow_pool(c))) return rc; retry = true; }
     if (h[C_ERR_PAIRS]) {
       c->pairs_cap *= 4; c->hits_cap *= 4; dev_free(&c->d_pairs); dev_free(&c->d_lis); dev_free(&c->d_hits); dev_free(&c->d_tuples); dev_free(&c->d_tuples2);
       if (c->pairs_cap > (1u << 22)) { set_err(c, "per-read candidate scratch exceeds capacity"); return SMR_ERR_CAPACITY; }
@@ -961,7 +972,7 @@ extern "C" int smr_seed_scan(smr_ctx* c, int slot, const smr_params* p, int stra
     ev_collect(c);
     bool retry = false;
     if (h[C_ERR_HITCAP]) { if (!grow_hcap(c, P.partialwin)) return SMR_ERR_CAPACITY; retry = true; }
-    if (h[C_ERR_POOL]) { uint64_t w = c->pool_words * 2; if ((rc = dev_alloc(c, &c->d_pool, w))) return rc; c->pool_words = w; retry = true; }
+    if (h[C_ERR_POOL]) { if ((rc = grow_pool(c))) return rc; retry = true; }
     if (!retry) { if (n_hits_out) *n_hits_out = h[C_HIT]; return SMR_OK; }
   }
   set_err(c, "capacity retries exhausted");
@@ -981,6 +992,24 @@ extern "C" int smr_seed_tuples_fetch(smr_ctx* c, uint64_t* tuples, uint64_t cap_
   meta[0] = nt; meta[1] = std::min(sn[SN_FWD], nt); meta[2] = c->sb.nc; meta[3] = c->sb.fb; meta[4] = c->sb.cb; meta[5] = c->sb.nkh; meta[6] = c->ccap; meta[7] = sn[SN_REDO];
   if (tuples) { if (cap_tuples < nt) return SMR_ERR_CAPACITY; if (nt) HIPCHK(c, hipMemcpy(tuples, c->sb.srt, (size_t)nt * sizeof(SeedTup), hipMemcpyDeviceToHost)); }
   if (cbase) { if (cap_cbase < c->sb.nc + 1u) return SMR_ERR_CAPACITY; HIPCHK(c, hipMemcpy(cbase, c->sb.cbase, (size_t)(c->sb.nc + 1u) * 4, hipMemcpyDeviceToHost)); }
+  return SMR_OK;
+}
+
+// Test seam (tests/test_gpu_parity.py, the seed-hit pool at its limits): info = {pool words, regrows since smr_create, one past the highest pool
+// word handed out, 1 if the last seed-stage launch inlined one-hit windows}.  The third is max(shard * region + cursor) over the shards with a
+// non-zero cursor of the selected batch: what the last attempt's last strand handed out (the cursors restart with each strand).
+extern "C" int smr_seed_pool_info(smr_ctx* c, uint64_t info[4]) {
+  if (!c || !info) return SMR_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<unsigned long long> cur(C_NSHARD * C_PCUR_STRIDE, 0ull);
+  if (c->b->d_ctr) {
+    HIPCHK(c, hipMemcpyAsync(cur.data(), &c->b->d_ctr[C_PCUR], cur.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  const uint64_t region = std::min<uint64_t>(c->pool_words, 0x7FFFFFF0ull) / C_NSHARD;
+  uint64_t hi = 0;
+  for (int s = 0; s < C_NSHARD; s++) if (cur[s * C_PCUR_STRIDE]) hi = std::max<uint64_t>(hi, s * region + cur[s * C_PCUR_STRIDE]);
+  info[0] = c->pool_words; info[1] = c->n_pool_grown; info[2] = hi; info[3] = c->pool_inline;
   return SMR_OK;
 }
 

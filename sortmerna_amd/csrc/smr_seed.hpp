@@ -166,7 +166,8 @@ struct SeedKey { uint32_t slot, chars, key; bool dup; };          // a decoded t
 // A window whose search leaves ONE hit (most windows of a read sampled from the DB: the 0-error match) needs no segment: its wseg word IS the hit --
 // SEED_SEG_INLINE | id (| SEED_ZERO_BIT forward, | SEED_CAND_COND reverse).  k_seed_pg then writes no pool words for it and k_seed_finish reads none: a
 // 128-byte line per window less in the kernel furthest from its bytes (round 5: 7.8 GB moved for 1.3 GB).  Needs ids and pool offsets below 2^30
-// (SeedBufs::seg_inline; the host checks both).
+// (SeedBufs::seg_inline; the host checks both).  Every reader of the bit checks SeedBufs::seg_inline first: with inlining off, bit 30 of a wseg
+// word is part of a pool offset (a pool of more than 2^30 words hands out such offsets from its upper shards) and never tags an id.
 #define SEED_SEG_INLINE 0x40000000u
 #define SEED_SEG_ID 0x3FFFFFFFu
 struct SeedBufs {
@@ -978,7 +979,7 @@ __global__ void __launch_bounds__(64) k_seed_search(DIndex ix, DParams P, int pa
       if (mine && DIR == 1 && wseg_has(sb, 0, slot)) {     // the window's list so far = the forward search's hits
         const uint32_t seg = sb.wseg[0][slot];
         if (seg & SEED_ZERO_BIT) mine = false;             // accept_zero_kmer: no reverse search (paralleltraversal.cpp:188)
-        else if (seg & SEED_SEG_INLINE) { n_prev = 1; hl[lane] = seg & SEED_SEG_ID; sl.nh = 1; }
+        else if (sb.seg_inline && (seg & SEED_SEG_INLINE)) { n_prev = 1; hl[lane] = seg & SEED_SEG_ID; sl.nh = 1; }
         else {
           const uint32_t o = seg & ~SEED_ZERO_BIT;
           n_prev = pool[o] & 0xFFFFu;
@@ -1071,6 +1072,7 @@ __global__ void __launch_bounds__(256) k_seed_finish(DReads rd, DParams P, int p
       const uint32_t slot0 = r * sb.maxwin;
       uint32_t seeds = 0, upper = 0, rlook = 0, nsearched = 0;
       uint32_t rem0 = 0, rem1 = 0;                           // (k * stride) % skip[0], % skip[1], kept by addition
+      const bool inl_ok = sb.seg_inline != 0;                // SEED_SEG_INLINE tags an id only when the launch inlines (else bit 30 belongs to an offset)
       // the windows' bits, 32 at a time: a read's windows are consecutive bits of fbits[0] / fbits[1]
       auto bits32 = [&](int d, uint32_t b0) -> uint32_t {
         const uint32_t i = b0 >> 5, s = b0 & 31u;
@@ -1082,7 +1084,7 @@ __global__ void __launch_bounds__(256) k_seed_finish(DReads rd, DParams P, int p
         uint32_t n = 0;
         const bool fzero = sf != NONE && (sf & SEED_ZERO_BIT);
         // (a one-hit window's hit lies in the word itself: SEED_SEG_INLINE -- no pool line is touched for it)
-        const bool fin = sf != NONE && (sf & SEED_SEG_INLINE), rin = sr != NONE && (sr & SEED_SEG_INLINE);
+        const bool fin = inl_ok && sf != NONE && (sf & SEED_SEG_INLINE), rin = inl_ok && sr != NONE && (sr & SEED_SEG_INLINE);
         const uint32_t of = sf & ~SEED_ZERO_BIT, orv = sr & ~SEED_ZERO_BIT;
         const uint32_t hr = sr == NONE ? 0u : rin ? 1u : pool[orv];
         const uint32_t nf = sf == NONE ? 0u : fin ? 1u : (pool[of] & 0xFFFFu), nr = hr & 0xFFFFu;
@@ -1122,7 +1124,8 @@ __global__ void __launch_bounds__(256) k_seed_finish(DReads rd, DParams P, int p
           const uint32_t j = (uint32_t)__ffs((int)mm) - 1u, k = kb + j;
           const uint32_t sf = ((mf >> j) & 1u) ? sb.wseg[0][slot0 + k] : NONE, sr = ((mr >> j) & 1u) ? sb.wseg[1][slot0 + k] : NONE;
           if (sf != NONE && ((srch >> j) & 1u) && !(sf & SEED_ZERO_BIT)) rlook++;        // ... unless the forward search hit exactly
-          const uint32_t cf = sf == NONE ? 0u : (sf & SEED_SEG_INLINE) ? 1u : (pool[sf & ~SEED_ZERO_BIT] & 0xFFFFu), cr = sr == NONE ? 0u : (sr & SEED_SEG_INLINE) ? 1u : (pool[sr & ~SEED_ZERO_BIT] & 0xFFFFu);
+          const uint32_t cf = sf == NONE ? 0u : (inl_ok && (sf & SEED_SEG_INLINE)) ? 1u : (pool[sf & ~SEED_ZERO_BIT] & 0xFFFFu);
+          const uint32_t cr = sr == NONE ? 0u : (inl_ok && (sr & SEED_SEG_INLINE)) ? 1u : (pool[sr & ~SEED_ZERO_BIT] & 0xFFFFu);
           if (seeds < FIN_KEEP) { s_sf[seeds][threadIdx.x] = sf; s_sr[seeds][threadIdx.x] = sr; s_k[seeds][threadIdx.x] = (uint16_t)k; }
           seeds++; upper += cf + cr;
         }

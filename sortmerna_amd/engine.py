@@ -391,6 +391,13 @@ class Engine:
         self._chk(self.L.smr_seed_tuples_fetch(self.h, tup.ctypes.data, len(tup), cbase.ctypes.data, len(cbase), meta), "smr_seed_tuples_fetch")
         return tup[: meta[0]], cbase, dict(n=meta[0], n_fwd=meta[1], nc=meta[2], fb=meta[3], cb=meta[4], nkh=meta[5], ccap=meta[6], redo=meta[7])
 
+    def seed_pool_info(self):
+        """dict(words, grown, hi, inline) of the seed-hit pool (smr_seed_pool_info: a test seam): its size in words, its regrows since the engine
+        was created, one past the highest word the last seed stage handed out, whether that stage inlined one-hit windows"""
+        info = (C.c_uint64 * 4)()
+        self._chk(self.L.smr_seed_pool_info(self.h, info), "smr_seed_pool_info")
+        return dict(words=info[0], grown=info[1], hi=info[2], inline=bool(info[3]))
+
     def prof_reset(self):
         self._chk(self.L.smr_prof_reset(self.h), "smr_prof_reset")
 

@@ -58,6 +58,40 @@ else:
         _align_body(engine, wl, opts)
 
 
+# the seed-hit pool at its limits (test_gpu_parity.py): one seed mode by default, both with SMR_EMU_FULL=1 -- the pigeonhole kernel where it
+# writes segments the default path does not (one-hit windows without inlining; a retry of parts that share one seed sort), the DFS kernel for
+# offsets above 2^30 (every reverse search goes through k_seed_search<1>'s reader of the forward list: all three readers of SEED_SEG_INLINE)
+from test_gpu_parity import seg_inline_off_body, pool_above_2_30_body, pool_regrown_body  # noqa: E402
+
+
+def _pool_modes(default):
+    return [0, 1] if FULL else [default]
+
+# the emulator's hipMalloc fills every allocation (0xA5), so the pool occupies host memory: 4.25 GiB puts shards 61..63 above 2^30 words
+EMU_POOL_ABOVE_2_30_WORDS = 0x44000000
+
+
+def _host_bytes_free():
+    return os.sysconf("SC_AVPHYS_PAGES") * os.sysconf("SC_PAGE_SIZE")
+
+
+@pytest.mark.parametrize("mode", _pool_modes(0), ids=lambda m: "dfs" if m else "pg")
+def test_seed_lists_with_seg_inline_off_give_the_oracle_records(emulator, wl, monkeypatch, mode):
+    seg_inline_off_body(wl, monkeypatch, mode)
+
+
+@pytest.mark.parametrize("mode", _pool_modes(1), ids=lambda m: "dfs" if m else "pg")
+def test_seed_hit_pool_offsets_above_2_30_give_the_oracle_records(emulator, wl, monkeypatch, mode):
+    if _host_bytes_free() < 16 * 10**9:
+        pytest.skip("the emulated pool of 4.25 GiB needs 16 GB of free host memory")
+    pool_above_2_30_body(wl, monkeypatch, mode, EMU_POOL_ABOVE_2_30_WORDS)
+
+
+@pytest.mark.parametrize("mode", _pool_modes(0), ids=lambda m: "dfs" if m else "pg")
+def test_seed_hit_pool_regrown_from_a_small_start_gives_the_oracle_records(emulator, wl, tmp_path, monkeypatch, mode):
+    pool_regrown_body(wl, tmp_path, monkeypatch, mode)
+
+
 from test_gpu_parity import test_candidate_walk_in_rounds_gives_the_oracle_records as _walk_body, WALK_VARIANTS  # noqa: E402
 
 # (the GPU suite runs every variant with five option sets; here every variant once and one variant with the other option sets, unless SMR_EMU_FULL=1)

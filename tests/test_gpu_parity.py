@@ -38,8 +38,9 @@ def _compare(recs_gpu, recs_orc, what):
     assert not bad, msg
 
 
-def test_seed_scan_matches_oracle(engine, wl):
-    """k_seed (window scan + burst-trie descent) vs traversetrie_align restated on the CPU, per strand and pass."""
+def _check_seed_scan(engine, wl, cases, fetch=True):
+    """smr_seed_scan's (read, id, window) triples vs traversetrie_align restated on the CPU, for each (strand, pass) of `cases`
+    (fetch=False: only their number, which smr_seed_scan returns -- smr_seed_hits_fetch copies the whole seed-hit pool to the host)"""
     L = orc.lib()
     ix = L.orc_index_load(wl.prefix.encode(), 0, 18)
     engine.upload_reads(wl.reads, 1)
@@ -47,15 +48,16 @@ def test_seed_scan_matches_oracle(engine, wl):
     p = smr.default_params(minimal_score=wl.minimal_score)
     strides = [18, 9, 3]
     ids = (C.c_uint32 * 4096)()
-    for strand in (0, 1):
+    for strand in sorted(set(c[0] for c in cases)):
         iseqs = [iseq_for_strand(s, strand) for s in wl.seqs]
-        for pass_ in (0, 1, 2):
+        for pass_ in sorted(c[1] for c in cases if c[0] == strand):
             engine.reset_state()
             n = engine.seed_scan(0, p, strand, pass_)
-            got = engine.seed_hits()
-            assert len(got) == n
-            got_set = set(map(tuple, got.tolist()))
-            assert len(got_set) == len(got), "duplicate (read,id,win) triples"
+            if fetch:
+                got = engine.seed_hits()
+                assert len(got) == n
+                got_set = set(map(tuple, got.tolist()))
+                assert len(got_set) == len(got), "duplicate (read,id,win) triples"
             exp = set()
             for r, v in enumerate(iseqs):
                 if len(v) < 18:
@@ -69,10 +71,18 @@ def test_seed_scan_matches_oracle(engine, wl):
                     c = L.orc_window_hits(ix, v.ctypes.data, w, 18, 0, 0, ids, 4096, C.byref(z))
                     for q in range(c):
                         exp.add((r, ids[q], w))
+            if not fetch:
+                assert n == len(exp), "strand %d pass %d: %d gpu hits vs %d oracle hits" % (strand, pass_, n, len(exp))
+                continue
             assert got_set == exp, "strand %d pass %d: %d gpu hits vs %d oracle hits, %d differ" % (
                 strand, pass_, len(got_set), len(exp), len(got_set ^ exp))
     L.orc_index_free(ix)
     engine.unload_index(0)
+
+
+def test_seed_scan_matches_oracle(engine, wl):
+    """k_seed (window scan + burst-trie descent) vs traversetrie_align restated on the CPU, per strand and pass."""
+    _check_seed_scan(engine, wl, [(strand, pass_) for strand in (0, 1) for pass_ in (0, 1, 2)])
 
 
 @pytest.mark.parametrize("opts", [
@@ -455,6 +465,110 @@ def test_small_candidate_pool_is_redone_and_grows(wl, monkeypatch):
         e.close()
 
 
+def _counters_equal(ctr_g, ctr_o, what):
+    assert (ctr_g["num_aligned"], ctr_g["num_short"], ctr_g["reads_matched_per_db"][0]) == (ctr_o["num_aligned"], ctr_o["num_short"], ctr_o["per_db"]), what
+
+
+# The seed stage keeps a window's hit list as one word of wseg: a pool offset, or -- when SeedBufs::seg_inline is on -- the one hit itself
+# tagged SEED_SEG_INLINE (bit 30).  The host turns inlining off for pools of more than 2^30 words, whose upper shards hand out offsets with
+# bit 30 set; every reader must then take the word for an offset.  SMR_SEED_POOL_WORDS starts the pool at a given size (smr_seed_pool_info
+# tells what happened to it).
+POOL_ABOVE_2_30_WORDS = 0x60000000       # 6 GiB: shards 43..63 of 64 start above 2^30 words
+
+
+def seg_inline_off_body(wl, monkeypatch, mode):
+    """SMR_SEG_INLINE=0 at the default pool size: every one-hit window writes a segment, the readers decode offsets only"""
+    monkeypatch.setenv("SMR_SEG_INLINE", "0")
+    recs_o, ctr_o = wl.oracle_records()
+    e = smr.Engine(0)
+    try:
+        e.set_seed_mode(mode)
+        recs_g, ctr_g = wl.gpu_records(e)
+        assert not e.seed_pool_info()["inline"]
+        _compare(recs_g, recs_o, "SMR_SEG_INLINE=0, seed mode %d" % mode)
+        _counters_equal(ctr_g, ctr_o, "SMR_SEG_INLINE=0, seed mode %d" % mode)
+        assert e.prof().n_hit == ctr_o["n_hit"]
+        assert ctr_o["num_aligned"] > 100
+        _check_seed_scan(e, wl, [(0, 0), (1, 2)])
+        assert not e.seed_pool_info()["inline"]
+    finally:
+        e.close()
+
+
+def pool_above_2_30_body(wl, monkeypatch, mode, words):
+    """A seed-hit pool of `words` > 2^30 words: the host turns inlining off and the upper shards hand out offsets with bit 30 set, which the
+    readers (k_seed_search<1>'s forward list, k_seed_finish's merge and upper bound) must not take for inlined ids.  The seed stage alone
+    first (hits per (strand, pass) = the oracle's: a list read as an inlined id has one hit), then whole alignments (records, counters,
+    seed hits): the ids such a reader makes up lie far outside the index, and only a few of them need to reach a record."""
+    assert words > 1 << 30 and (words // 64) * 61 >= 1 << 30
+    monkeypatch.setenv("SMR_SEED_POOL_WORDS", str(words))
+    recs_o, ctr_o = wl.oracle_records()
+    e = smr.Engine(0)
+    try:
+        e.set_seed_mode(mode)
+        _check_seed_scan(e, wl, [(0, 0), (1, 2)], fetch=False)
+        info = e.seed_pool_info()
+        assert info["words"] == words and info["grown"] == 0 and not info["inline"], info
+        assert info["hi"] >= 1 << 30, info               # words above 2^30 were really handed out (else this proves nothing)
+        e.prof_reset()
+        recs_g, ctr_g = wl.gpu_records(e)
+        info = e.seed_pool_info()
+        assert info["words"] == words and info["grown"] == 0 and not info["inline"] and info["hi"] >= 1 << 30, info
+        _compare(recs_g, recs_o, "pool of %#x words, seed mode %d" % (words, mode))
+        _counters_equal(ctr_g, ctr_o, "pool of %#x words, seed mode %d" % (words, mode))
+        assert e.prof().n_hit == ctr_o["n_hit"]
+        assert ctr_o["num_aligned"] > 100
+    finally:
+        e.close()                                         # (frees the pool before the next test)
+
+
+def pool_regrown_body(wl, tmp_path, monkeypatch, mode):
+    """SMR_SEED_POOL_WORDS=4096 (64 words per shard): the first attempt of every entry point overflows the pool (C_ERR_POOL), which is
+    doubled until the stage fits, and the attempt is redone -- smr_align_part on one part, on a multi-part index with the shared seed sort
+    (a retry restarts a part whose sort arrays an earlier attempt built), and smr_seed_scan.  The grown pool is kept: a second run of the
+    same reads grows it no more and gives the same records."""
+    monkeypatch.setenv("SMR_SEED_POOL_WORDS", "4096")
+    w = Workload(str(tmp_path), db_nt=400_000, n_reads=1500, seed=21, max_mb=1.0)
+    assert w.stats.nparts >= 3
+    for x, what in ((wl, "one part"), (w, "%d parts, shared seed sort" % w.stats.nparts)):
+        recs_o, ctr_o = x.oracle_records()
+        e = smr.Engine(0)
+        try:
+            e.set_seed_mode(mode)
+            recs_g, ctr_g = x.gpu_records(e)
+            info = e.seed_pool_info()
+            assert info["grown"] >= 1 and info["words"] >= 4096 << info["grown"], info
+            _compare(recs_g, recs_o, "pool grown from 4096 words, %s, seed mode %d" % (what, mode))
+            _counters_equal(ctr_g, ctr_o, "pool grown from 4096 words, %s, seed mode %d" % (what, mode))
+            recs_2, ctr_2 = x.gpu_records(e)
+            assert e.seed_pool_info()["grown"] == info["grown"]
+            assert recs_2 == recs_g and ctr_2 == ctr_g
+        finally:
+            e.close()
+    e = smr.Engine(0)
+    try:
+        e.set_seed_mode(mode)
+        _check_seed_scan(e, wl, [(0, 0), (1, 2)])
+        assert e.seed_pool_info()["grown"] >= 1
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["pg", "dfs"])
+def test_seed_lists_with_seg_inline_off_give_the_oracle_records(wl, monkeypatch, mode):
+    seg_inline_off_body(wl, monkeypatch, mode)
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["pg", "dfs"])
+def test_seed_hit_pool_offsets_above_2_30_give_the_oracle_records(wl, monkeypatch, mode):
+    pool_above_2_30_body(wl, monkeypatch, mode, POOL_ABOVE_2_30_WORDS)
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["pg", "dfs"])
+def test_seed_hit_pool_regrown_from_a_small_start_gives_the_oracle_records(wl, tmp_path, monkeypatch, mode):
+    pool_regrown_body(wl, tmp_path, monkeypatch, mode)
+
+
 def test_batch_dominated_by_one_sequence(engine, tmp_path):
     """3 000 copies of two reads among 500 others (a sample dominated by one organism's rRNA): all their windows share a few keys, so
     the tuple sort sees bins of thousands (one block of k_seed_bins handles a whole coarse bin) and whole waves of k_seed_pg search the
@@ -668,11 +782,12 @@ def _pg_key(T, frm, cnt):
     return k
 
 
-def _host_recount_of_the_search(pg, root3, tuples, cbase, meta, direction, zero_slots, pw, full=False):
+def _host_recount_of_the_search(pg, root3, tuples, cbase, meta, direction, zero_slots, pw, full=False, inline=True):
     """What k_seed_pg<direction> counts as its algorithmic HBM bytes (smr_seed_pg.hpp, C_B_PG0 / C_B_PG1), recomputed on the host from the
     pigeonhole layout of the HOST transform and the launch's sorted tuples: per tuple 8 B + its block-table entry 8 B (+ 1 B: the window's
     group bit, reverse); per search with directories 8 directory words; 4 B per string inside its four exact-key ranges; 8 B per accepted
-    {rank, id}; the segment written (4 B per word) + 4 B for the window slot pointing to it; 2 B per wave chunk (its coarse bin).
+    {rank, id}; the segment written (4 B per word) + 4 B for the window slot pointing to it (a one-hit window's slot holds the hit itself
+    when the launch inlines: 4 B, no segment); 2 B per wave chunk (its coarse bin).
     -> (bytes, slots whose forward search ended with a 0-error match)"""
     h = pw // 2
     n_fwd, n_all, fb, cb, nkh = meta["n_fwd"], meta["n"], meta["fb"], meta["cb"], meta["nkh"]
@@ -748,7 +863,7 @@ def _host_recount_of_the_search(pg, root3, tuples, cbase, meta, direction, zero_
             if not present:
                 hl.append(idc)
         if hl:
-            total += 4 if len(hl) == 1 else 4 * (1 + len(hl)) + 4      # one hit: it lies in the window's slot word (SEED_SEG_INLINE), no segment
+            total += 4 if len(hl) == 1 and inline else 4 * (1 + len(hl)) + 4      # one hit, inlined: it lies in the window's slot word (SEED_SEG_INLINE)
             segs.add(slot)
         if zero_end:
             zeros.add(slot)
@@ -760,15 +875,20 @@ def _host_recount_of_the_search(pg, root3, tuples, cbase, meta, direction, zero_
     return total, zeros
 
 
-@pytest.mark.parametrize("strand,pass_,dedup", [(0, 0, None), (1, 2, None), (0, 0, "2"), (1, 2, "2")], ids=["s0p0", "s1p2", "s0p0-dedup", "s1p2-dedup"])
-def test_pigeonhole_search_bytes_equal_a_host_recount(wl, monkeypatch, strand, pass_, dedup):
+@pytest.mark.parametrize("strand,pass_,dedup,seg_inline", [(0, 0, None, True), (1, 2, None, True), (0, 0, "2", True), (1, 2, "2", True),
+                                                      (0, 0, None, False), (1, 2, None, False), (0, 0, "2", False), (1, 2, "2", False)],
+                         ids=["s0p0", "s1p2", "s0p0-dedup", "s1p2-dedup", "s0p0-seg_inline_off", "s1p2-seg_inline_off", "s0p0-dedup-seg_inline_off", "s1p2-dedup-seg_inline_off"])
+def test_pigeonhole_search_bytes_equal_a_host_recount(wl, monkeypatch, strand, pass_, dedup, seg_inline):
     """The roofline numerator of the dominant seed kernel is counted by the kernel itself (C_B_PG0 / C_B_PG1).  Here the same quantity is
     recomputed on the HOST -- from the pigeonhole layout the host transform builds (smr_build_pigeonhole) and the launch's sorted tuples, walking
     the four exact-key ranges of every search, the closed-form automaton, the duplicate rule and the reference's list rules in Python -- and
     must equal the device's counters exactly, for the forward and for the reverse launch.  The `dedup` cases search every repeated seed once
-    (SMR_SEED_DEDUP=2: every key with two tuples counts as hot) and count what the repeats cost instead."""
+    (SMR_SEED_DEDUP=2: every key with two tuples counts as hot) and count what the repeats cost instead.  The `seg_inline_off` cases turn the
+    inlining of one-hit windows off (SMR_SEG_INLINE=0): such a window then writes a segment of two words, like a longer list."""
     if dedup:
         monkeypatch.setenv("SMR_SEED_DEDUP", dedup)
+    if not seg_inline:
+        monkeypatch.setenv("SMR_SEG_INLINE", "0")
     e = smr.Engine(0)
     try:
         e.upload_reads(wl.reads, 1)
@@ -781,8 +901,10 @@ def test_pigeonhole_search_bytes_equal_a_host_recount(wl, monkeypatch, strand, p
         tuples, cbase, meta = e.seed_tuples()
         assert meta["redo"] == 0 and meta["n"] > 1000 and 0 < meta["n_fwd"] < meta["n"]
         kp = e.prof_kernels()
-        exp0, zeros = _host_recount_of_the_search(pg, root3, tuples, cbase, meta, 0, set(), 9)
-        exp1, _ = _host_recount_of_the_search(pg, root3, tuples, cbase, meta, 1, zeros, 9)
+        if not seg_inline:
+            assert not e.seed_pool_info()["inline"]
+        exp0, zeros = _host_recount_of_the_search(pg, root3, tuples, cbase, meta, 0, set(), 9, inline=seg_inline)
+        exp1, _ = _host_recount_of_the_search(pg, root3, tuples, cbase, meta, 1, zeros, 9, inline=seg_inline)
         assert len(zeros) > 10                                    # the workload has exact seed matches: the reverse launch really skips searches
         assert (sum(1 for t in tuples if int(t) >> 63) > 20) == bool(dedup)
         assert int(kp["k_seed_pg<0>"]["bytes"]) == exp0, (int(kp["k_seed_pg<0>"]["bytes"]), exp0)

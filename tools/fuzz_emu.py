@@ -99,9 +99,9 @@ def main():
                                ("SMR_WALK_SPLIT", [None, None, None, "0"]), ("SMR_HANDOVER", [None, None, None, "0"]), ("SMR_CAND_BLOOM", [None, None, None, "64"]),
                                ("SMR_PG_CAND_CAP", [None, None, None, "8"]), ("SMR_WALK_GATHER", [None, None, None, "0"]),
                                # round 6: repeated seeds searched once / large bins sorted by several blocks at thresholds of a test's size, one seed sort for all parts
-                               # forced or off, single-hit windows with a segment after all
+                               # forced or off, single-hit windows with a segment after all; a seed-hit pool of 64 words per shard (regrown on every entry point)
                                ("SMR_SEED_DEDUP", [None, None, "2", "16", "0"]), ("SMR_SEED_HOT_BIN", [None, None, "64"]), ("SMR_SEED_HOT_SUB", [None, None, "200"]),
-                               ("SMR_SEED_SHARED", [None, None, "2", "0"]), ("SMR_SEG_INLINE", [None, None, None, "0"])):
+                               ("SMR_SEED_SHARED", [None, None, "2", "0"]), ("SMR_SEG_INLINE", [None, None, None, "0"]), ("SMR_SEED_POOL_WORDS", [None, None, None, "4096"])):
                 v = vals[int(rng.integers(0, len(vals)))]
                 os.environ.pop(name, None)
                 if v is not None:
