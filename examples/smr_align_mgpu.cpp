@@ -27,6 +27,11 @@
 //          --chunk-reads M     per rank: chunks of M reads (0 = 2 M), any number of them
 //          --fastx --other --blast '1 [cigar] [qcov] [qstrand]' --sam   report files (BLAST tabular, SAM without @SQ)
 //          -num_alignments N, -no-best, -e EVALUE as in smr_align
+//          -otu_map -de_novo_otu -id X -coverage X   the %id / %coverage pass (smr_idcov_part, the reference's denovo_stats) per chunk after the
+//                              traceback, its four sums in the C2 reduction, otu_map.txt (the shards' maps merged in rank order before the file is
+//                              written) and aligned_denovo.fa|fq, and aligned.log with the two Results lines.  Defaults and refusals are the
+//                              reference's (options.cpp:1623-1628, 1667-1674, 1744-1757): 0.97 / 0.97 under -otu_map, else 0; -id / -coverage
+//                              without -otu_map and -otu_map with -no-best are errors
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 
@@ -34,6 +39,7 @@
 #include <unistd.h>
 
 #include <chrono>
+#include <ctime>
 #include <condition_variable>
 #include <cstdint>
 #include <cstdio>
@@ -112,9 +118,12 @@ struct RankOut {
   std::vector<uint8_t> records;        // concatenated (u64 klen, key, u64 vlen, value) entries of the shard
   uint64_t n_records = 0;
   std::vector<uint64_t> counters;      // reduced: identical on every rank
+  uint64_t idcov[4] = {0, 0, 0, 0};    // reduced n_yid_ycov, n_yid_ncov, n_nid_ycov, num_denovo
+  smr_report* rep = nullptr;           // -otu_map: kept open until the shards' maps are merged
   double t_upload = 0, t_align = 0, t_fetch = 0, t_write = 0;
   int sw_kernel = -1;                     // smr_sw_mode of the rank's context: 0 = 32-bit kernel only (the packed kernel failed its self-check or was switched off)
   uint32_t minimal_score0 = 0;
+  std::vector<uint32_t> minimal_score_db;
 };
 }  // namespace
 
@@ -127,6 +136,9 @@ int main(int argc, char** argv) {
   int world = 0;
   uint64_t chunk_reads = 0;
   smr_report_opts ro; memset(&ro, 0, sizeof ro);
+  bool id_given = false, cov_given = false;
+  std::string cmdline;
+  for (int i = 0; i < argc; i++) { cmdline += argv[i]; cmdline += " "; }
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto val = [&]() -> std::string { if (i + 1 >= argc) die("missing value after " + a); return argv[++i]; };
@@ -154,9 +166,19 @@ int main(int argc, char** argv) {
       strcpy(ro.blast_cols, cols.c_str());
     }
     else if (a == "-sam" || a == "--sam") ro.sam = 1;
+    else if (a == "-otu_map" || a == "--otu_map") ro.otu_map = 1;
+    else if (a == "-de_novo_otu" || a == "--de_novo_otu") ro.denovo = 1;
+    else if (a == "-id" || a == "--id") { ro.min_id = atof(val().c_str()); id_given = true; }
+    else if (a == "-coverage" || a == "--coverage") { ro.min_cov = atof(val().c_str()); cov_given = true; }
     else die("unknown option " + a);
   }
   if (dbs.empty() || reads_path.empty()) die("--ref and --reads are required");
+  // the reference's rules for the four options (options.cpp:1623-1628, 1667-1674, 1744-1757)
+  if ((id_given || cov_given) && !ro.otu_map) die("options '-id' and '-coverage' can only be used together with '-otu_map': they are the thresholds of the OTU map");
+  if (ro.otu_map && !base.is_best) die("option '-otu_map' cannot be used with '-no-best': the OTU map is built from the best alignments");
+  if (ro.otu_map) { if (!id_given) ro.min_id = 0.97; if (!cov_given) ro.min_cov = 0.97; }
+  if (!(ro.min_id >= 0 && ro.min_id <= 1 && ro.min_cov >= 0 && ro.min_cov <= 1)) die("-id and -coverage take a value within [0, 1]");
+  const bool idcov = ro.otu_map || ro.denovo;
   if (const char* why = smr_params_refused(&base)) die(std::string("these options are outside what libsmr_hip aligns (the reference accepts them): ") + why);
   for (auto& d : dbs) if (!d.has_gumbel) die("--gumbel LAMBDA K is required for every --ref (the reference computes them with its vendored ALP library, refstats.cpp:194-233; minimal_score depends on them)");
   int ndev = 0;
@@ -190,7 +212,7 @@ int main(int argc, char** argv) {
   // loaded or built (one host copy shared by all ranks) ----
   const double t0 = now_s();
   smr_reads* all = nullptr;
-  const bool want_reports = ro.fastx || ro.other || ro.blast_tabular || ro.sam;
+  const bool want_reports = ro.fastx || ro.other || ro.blast_tabular || ro.sam || idcov;
   double t_reads = 0;
   char rerr[512] = "";
   int reads_rc = SMR_OK;
@@ -315,6 +337,7 @@ int main(int argc, char** argv) {
       pk[k].index_num = (uint32_t)k;
     }
     O.minimal_score0 = pk[0].minimal_score;
+    for (size_t k = 0; k < dbs.size(); k++) O.minimal_score_db.push_back(pk[k].minimal_score);
     O.t_upload += now_s() - t;
     // the shard's report files (this rank's directory; merged in rank order afterwards)
     smr_report* rep = nullptr;
@@ -387,6 +410,8 @@ int main(int argc, char** argv) {
     // C2 accumulator: the Readstats counters of all chunks of this rank, summed on the device
     void* d_acc = nullptr; uint32_t nctr = 0;
     { void* dummy = nullptr; if (smr_counters_device(gpu, &dummy, &nctr) != SMR_OK) die(smr_last_error(gpu)); }
+    const uint32_t nctr0 = nctr;
+    if (idcov) nctr = SMR_COUNTERS_WITH_IDCOV;           // + n_yid_ycov, n_yid_ncov, n_nid_ycov, num_denovo behind the 66
     if (hipMalloc(&d_acc, (size_t)nctr * 8) != hipSuccess || hipMemset(d_acc, 0, (size_t)nctr * 8) != hipSuccess) die("hipMalloc failed");
     for (size_t c = 0; c < n_chunks; c++) {
       { std::unique_lock<std::mutex> l(pm); pcv.wait(l, [&] { return uploaded > c; }); }
@@ -399,6 +424,14 @@ int main(int argc, char** argv) {
           p.is_last_index_part = (k + 1 == dbs.size() && part + 1 == dbs[k].parts.size());
           if (smr_align_part(gpu, slot[k][part], &p) != SMR_OK || smr_traceback(gpu, slot[k][part], &p) != SMR_OK) die(smr_last_error(gpu));
         }
+      // denovo_stats (processor.cpp:287-438) for the chunk: after ALL its parts are aligned -- the pass counts final alignments --, per (index, part)
+      if (idcov)
+        for (size_t k = 0; k < dbs.size(); k++)
+          for (size_t part = 0; part < dbs[k].parts.size(); part++) {
+            smr_params p = pk[k];
+            p.part = (uint32_t)part;
+            if (smr_idcov_part(gpu, slot[k][part], &p, ro.min_id, ro.min_cov) != SMR_OK) die(smr_last_error(gpu));
+          }
       if (smr_counters_accumulate(gpu, d_acc, nctr) != SMR_OK || smr_results_fetch(gpu) != SMR_OK) die(smr_last_error(gpu));
       if (smr_batch_select(gpu, 15) != SMR_OK) die(smr_last_error(gpu));          // nothing of slot c % NS is "selected" while the uploader refills it later
       O.t_align += now_s() - t;
@@ -416,9 +449,11 @@ int main(int argc, char** argv) {
       O.counters.assign(2 + dbs.size(), 0);
       O.counters[0] = hc[0]; O.counters[1] = hc[1];
       for (size_t k = 0; k < dbs.size(); k++) O.counters[2 + k] = hc[2 + k];
+      if (idcov) for (int q = 0; q < 4; q++) O.idcov[q] = hc[nctr0 + q];
     }
     (void)hipFree(d_acc);
-    if (rep && smr_report_close(rep) != SMR_OK) die("cannot write the report files");
+    if (rep && ro.otu_map) O.rep = rep;                  // (closed by main once the shards' maps are merged)
+    else if (rep && smr_report_close(rep) != SMR_OK) die("cannot write the report files");
     O.t_write = t_wr;
     O.t_fetch = now_s() - t;
     smr_destroy(gpu);
@@ -430,9 +465,18 @@ int main(int argc, char** argv) {
   const double t_ranks = now_s() - t_start;
   // (the communicators are not destroyed: the process ends with _exit below)
 
+  // ---- otu_map.txt: one map for the run.  The shards' entries are merged in rank order into rank 0's report object (per (index, part), so
+  // that a group lists its reads in the order of the reference's loops), which then writes the file; its line count is Readstats::total_otu ----
+  uint64_t total_otu = 0;
+  if (ro.otu_map) {
+    if (smr_report_otu_count(outs[0].rep, &total_otu) != SMR_OK) die("smr_report_otu_count failed");
+    for (int r = 1; r < world; r++) if (smr_report_otu_merge(outs[0].rep, outs[r].rep) != SMR_OK) die("smr_report_otu_merge failed");
+    for (int r = world - 1; r >= 0; r--) if (smr_report_close(outs[r].rep) != SMR_OK) die("cannot write the report files");
+    rename((out_dir + "/rank0/otu_map.txt").c_str(), (out_dir + "/otu_map.txt").c_str());      // (absent when no read passed both thresholds)
+  }
   // ---- report files: the shards' files concatenated in rank order (Report::merge, report.cpp:56-97) ----
   if (want_reports) {
-    const char* names[] = {"aligned.fq", "aligned.fa", "other.fq", "other.fa", "aligned.blast", "aligned.sam"};
+    const char* names[] = {"aligned.fq", "aligned.fa", "other.fq", "other.fa", "aligned.blast", "aligned.sam", "aligned_denovo.fq", "aligned_denovo.fa"};
     std::vector<char> buf(1 << 22);
     for (const char* nm : names) {
       FILE* o = nullptr;
@@ -478,7 +522,32 @@ int main(int argc, char** argv) {
   fprintf(f, "Total reads = %llu\nTotal reads passing E-value threshold = %llu\nToo short reads (last part) = %llu\n", (unsigned long long)n,
           (unsigned long long)ctr[0], (unsigned long long)ctr[1]);
   for (size_t k = 0; k < dbs.size(); k++) fprintf(f, "%s\t%llu\n", dbs[k].fasta.c_str(), (unsigned long long)ctr[2 + k]);
+  if (idcov) fprintf(f, "num_yid_ycov = %llu\nnum_yid_ncov = %llu\nnum_nid_ycov = %llu\nnum_denovo = %llu\nTotal OTUs = %llu\n", (unsigned long long)outs[0].idcov[0],
+                     (unsigned long long)outs[0].idcov[1], (unsigned long long)outs[0].idcov[2], (unsigned long long)outs[0].idcov[3], (unsigned long long)total_otu);
   fclose(f);
+  if (idcov) {
+    // aligned.log (Summary::to_string, summary.cpp:102-175) with the two Results lines of -de_novo_otu / -otu_map
+    for (int r = 1; r < world; r++) for (int q = 0; q < 4; q++) if (outs[r].idcov[q] != outs[0].idcov[q]) die("the ranks disagree on the reduced id / coverage counters");
+    std::vector<smr_summary_db> sd(dbs.size());
+    for (size_t k = 0; k < dbs.size(); k++) {
+      smr_index_info info; smr_index_get_info(dbs[k].parts[0], &info);
+      sd[k].ref_file = dbs[k].fasta.c_str();
+      sd[k].skiplengths[0] = info.lnwin; sd[k].skiplengths[1] = info.lnwin / 2; sd[k].skiplengths[2] = 3;
+      sd[k].lambda = dbs[k].lambda; sd[k].K = dbs[k].K; sd[k].minimal_score = outs[0].minimal_score_db[k]; sd[k].reads_matched = ctr[2 + k];
+    }
+    const time_t tt = time(nullptr);
+    const std::string stamp = ctime(&tt);
+    const char* rf[1] = {reads_path.c_str()};
+    smr_summary sm; memset(&sm, 0, sizeof sm);
+    sm.cmdline = cmdline.c_str(); sm.pid = ""; sm.timestamp = stamp.c_str();
+    sm.seed_len = 18; sm.num_seeds = base.num_seeds; sm.edges = base.edges; sm.match = base.match; sm.mismatch = base.mismatch; sm.gap_open = base.gap_open;
+    sm.gap_ext = base.gap_ext; sm.score_N = base.score_N; sm.sam_sq = 0; sm.threads = world;
+    sm.reads_files = rf; sm.n_reads_files = 1;
+    sm.total_reads = n; sm.num_aligned = ctr[0]; sm.all_reads_len = smr_reads_total_len(all); sm.min_read_len = smr_reads_min_len(all); sm.max_read_len = smr_reads_max_len(all);
+    sm.dbs = sd.data(); sm.n_dbs = (uint32_t)sd.size();
+    sm.is_denovo = ro.denovo; sm.total_denovo = outs[0].idcov[3]; sm.is_otu_map = ro.otu_map; sm.total_id_cov = outs[0].idcov[0]; sm.total_otu = total_otu;
+    if (smr_summary_write((out_dir + "/aligned.log").c_str(), &sm) != SMR_OK) die("cannot write aligned.log");
+  }
   double tu = 0, ta = 0, tf = 0, tw = 0;
   for (auto& o : outs) { tu = std::max(tu, o.t_upload); ta = std::max(ta, o.t_align); tf = std::max(tf, o.t_fetch); tw = std::max(tw, o.t_write); }
   const double t_all = now_s() - t0;

@@ -21,6 +21,8 @@
  *                    traverse_bursttrie.cpp:100-298, alignment.cpp:100-509, ssw.c:834-941
  *   smr_result_*     Read::toBinString() / kvdb.put()         read.cpp:429-462, processor.cpp:150-155
  *   smr_counters     Readstats atomics                        readstats.hpp:77-85
+ *   smr_idcov_*      denovo_stats: %id / %coverage of every stored alignment, the four per-read and Readstats counters of -otu_map / -de_novo_otu
+ *                    processor.cpp:287-438, Read::calc_miss_gap_match read.cpp:547-589
  *
  * Hard limits of this build (each is an explicit error -- SMR_ERR_CAPACITY / SMR_ERR_ARG with a message --, never a silent difference):
  *   reads                 <= 65 535 letters each; reads x windows of the finest pass < 2^31 per batch (150-nt reads: ~47 M; the benches use 8 M)
@@ -243,9 +245,42 @@ int smr_traceback(smr_ctx*, int slot, const smr_params*);
 int smr_counters(smr_ctx*, uint64_t* out, uint32_t n_db);
 /* Device pointer + count of the u64 counters block (for an in-place RCCL all-reduce by the caller). */
 int smr_counters_device(smr_ctx*, void** dptr, uint32_t* n_u64);
-/* d_acc[k] += counter k of the selected batch for k < n_u64 (<= the count smr_counters_device gives), on the device: a host that aligns its
- * shard chunk by chunk through a few recycled batches keeps one device block of sums (and all-reduces THAT over the ranks). */
+/* d_acc[k] += counter k of the selected batch for k < n_u64 (<= the count smr_counters_device gives, or <= SMR_COUNTERS_WITH_IDCOV: k = 66 .. 69 are
+ * the four sums of smr_idcov_counters), on the device: a host that aligns its shard chunk by chunk through a few recycled batches keeps one device
+ * block of sums (and all-reduces THAT over the ranks). */
 int smr_counters_accumulate(smr_ctx*, void* d_acc, uint32_t n_u64);
+
+/* ------------------------------------------------------------------------------------------------
+ * %id / %coverage pass (the reference's denovo_stats, processor.cpp:287-438: what -otu_map and -de_novo_otu need).
+ * Call order: smr_align_part + smr_traceback for EVERY (index, part) of the run, then smr_idcov_part once per (index, part) with that part's
+ * references resident in `slot`, then smr_results_fetch.  The reference runs the pass after all alignment; here smr_align_part answers
+ * SMR_ERR_STATE once the pass has counted an alignment of the batch (smr_state_reset / smr_reads_upload* start over; a call that found no
+ * alignment to count changes nothing).  A host that keeps one slot and uploads part after part therefore uploads every part a second time
+ * for the pass when there is more than one; keeping the parts resident in slots 0..63 avoids that.
+ * ---------------------------------------------------------------------------------------------- */
+/* denovo_stats for ONE (index, part): processor.cpp:287-366.  Every stored alignment of that part is walked along its CIGAR over the read and
+ * the reference letters (n_miss, n_gap, n_match of Read::calc_miss_gap_match), id = n_match / (n_miss + n_gap + n_match) and
+ * cov = |read_end1 - read_begin1 + 1| / readlen are rounded to three decimals and compared with min_id / min_cov (each within [0, 1], else SMR_ERR_ARG);
+ * the class (both / id only / coverage only / neither) bumps one of the read's four counters (Read::c_yid_ycov, n_yid_ncov, n_nid_ycov, n_denovo:
+ * smr_result_record writes them; zero without this call) and one of the batch's.  Like the reference, the walk reads the FORWARD read also for an
+ * alignment on the reverse strand (csrc/smr_idcov.hpp says why).  SMR_ERR_STATE when an alignment of the part has no CIGAR yet.  Each alignment is
+ * counted once: a second call for the same (index, part) changes nothing.  SMR_ERR_CAPACITY when reads x alignment slots reaches 2^32. */
+int smr_idcov_part(smr_ctx*, int slot, const smr_params*, double min_id, double min_cov);
+/* out = {n_yid_ycov, n_yid_ncov, n_nid_ycov, num_denovo} of the selected batch (readstats.hpp:77-85) */
+int smr_idcov_counters(smr_ctx*, uint64_t out[4]);
+/* Device pointer to those four u64 (for an in-place all-reduce by the caller; SMR_ERR_STATE when the selected batch has no counter block
+ * yet); smr_counters_device keeps handing out its 66.
+ * smr_counters_accumulate takes them as k = 66 .. 69 of a block of SMR_COUNTERS_WITH_IDCOV u64. */
+int smr_idcov_counters_device(smr_ctx*, void** dptr, uint32_t* n_u64);
+#define SMR_COUNTERS_WITH_IDCOV 70
+/* The kernels of the pass at the seam of Read::calc_miss_gap_match: n independent triples (read i in the 0..4 alphabet, FORWARD letters, bytes
+ * [read_off[i], read_off[i+1]); the reference window that starts at the alignment's first reference letter; BAM-style u32 CIGAR operations
+ * length << 4 | op, op 0 / 1 / 2 = M / I / D, [cigar_off[i], cigar_off[i+1])) with read_begin / read_end / readlen as s_align2 carries them:
+ * out[4 i ..] = {n_miss, n_gap, n_match, class} with class 0 = id and coverage, 1 = id only, 2 = coverage only, 3 = neither.
+ * SMR_ERR_ARG when a CIGAR runs past its read or window. */
+int smr_idcov_batch(smr_ctx*, uint32_t n, const uint8_t* reads, const uint64_t* read_off, const uint8_t* refs, const uint64_t* ref_off,
+                    const uint32_t* cigars, const uint64_t* cigar_off, const int32_t* read_begin, const int32_t* read_end, const uint32_t* readlen,
+                    double min_id, double min_cov, uint32_t* out);
 
 /* Results.  smr_result_record writes Read::toBinString() bytes of read i (the KVDB value,
  * read.cpp:429-462; 0 bytes when the read has no alignment) and returns the size needed. */
@@ -309,7 +344,7 @@ int smr_cigar_batch(smr_ctx*, uint32_t n_pairs, const uint8_t* reads, const uint
 int smr_prof_reset(smr_ctx*);
 int smr_prof_get(smr_ctx*, smr_prof* out);
 /* The same period per kernel family (k_seed_keys, the tuple sort, k_seed_pg<0>, k_seed_pg<1>, k_seed_finish, k_cand, k_chain, k_begins,
- * k_trace): HIP-event time on the engine's stream, number of launches, and for the seed-stage kernels the ALGORITHMIC HBM bytes of what
+ * k_trace, ..., k_idcov): HIP-event time on the engine's stream, number of launches, and for the seed-stage kernels the ALGORITHMIC HBM bytes of what
  * the shipped kernels themselves do, from exact device counters: every tuple (12 B) written once by k_seed_keys next to its inputs
  * (read records, per-read state, two lookup words per window), read and written once by each of the two sort passes, read once by
  * k_seed_pg, which adds per search 8 B of block table, its directory words, 4 B per string looked at, 8 B per accepted {rank, id} and
@@ -340,6 +375,13 @@ typedef struct {
   int out2;              /* -out2: separate files for the mates: *_fwd / *_rev                     */
   int sout;              /* -sout: separate files for pairs and singletons: *_paired / *_singleton */
   int zip_out;           /* gzip every report file, names + ".gz" (the reference does so for gzip reads files or -zip-out 1, report_fx_base.cpp:94-95) */
+  /* the outputs of the %id / %coverage pass: the records must come from a run of smr_idcov_part with the same thresholds */
+  int otu_map;           /* -otu_map: otu_map.txt, written by smr_report_close (fill_otu_map, otumap.cpp:131-281): one line per reference id that a read
+                            with c_yid_ycov > 0 aligned to with %id >= min_id and %coverage >= min_cov -- id, then the read ids, tab separated; lines in
+                            std::map order of the id, reads in (index, part) then input order; no file when no read passed (otumap.cpp:200,276) */
+  int denovo;            /* -de_novo_otu: aligned_denovo.fa|fq (+ the _fwd / _paired ... suffixes, + .gz): the reads with n_denovo > 0 and the other
+                            three counters 0 (output.cpp:133-143), mates routed like ReportDenovo::append (report_denovo.cpp:57-134) */
+  double min_id, min_cov; /* -id / -coverage */
 } smr_report_opts;
 int smr_report_open(const char* out_dir, const smr_report_opts*, int is_fastq, smr_report** out, char* err, size_t errcap);
 /* per --ref: Gumbel parameters and the corrected sizes (smr_refstats_corrected); per (index, part): where its reference ids/sequences are */
@@ -350,6 +392,12 @@ int smr_report_add(smr_report*, const char* header, const char* seq, const char*
 /* a pair of mates (read i of the first and of the second file / two consecutive records of an interleaved file) */
 int smr_report_add_pair(smr_report*, const char* header1, const char* seq1, const char* qual1, const uint8_t* record1, size_t record1_len,
                         const char* header2, const char* seq2, const char* qual2, const uint8_t* record2, size_t record2_len);
+/* *total_otu = lines of otu_map.txt (Readstats::total_otu, for smr_summary), stored when smr_report_close runs: the pointer must live until then */
+int smr_report_otu_count(smr_report*, uint64_t* total_otu);
+/* One otu_map.txt for a run whose reads went through several report objects (one per device, each fed a contiguous shard of the reads in input
+ * order): moves the map entries of `src` behind those of `dst`, per (index, part).  Merged in shard order, every group then lists its reads in
+ * (index, part) loop order, then input order, like the reference at -threads 1.  `src` writes no map at its close; `dst` writes the merged one. */
+int smr_report_otu_merge(smr_report* dst, smr_report* src);
 int smr_report_set_cmdline(smr_report*, const char* cmdline);   /* text after "CL:" in the SAM @PG line (default "libsmr_hip") */
 int smr_report_close(smr_report*);      /* writes aligned.blast / aligned.sam, closes the files, frees the object */
 const char* smr_report_last_error(const smr_report*);
@@ -369,6 +417,9 @@ typedef struct {
   const char* const* reads_files; uint32_t n_reads_files;
   uint64_t total_reads, num_aligned, all_reads_len; uint32_t min_read_len, max_read_len;
   const smr_summary_db* dbs; uint32_t n_dbs;
+  /* the two optional Results lines (summary.cpp:139-158) */
+  int is_denovo; uint64_t total_denovo;                        /* -de_novo_otu: Readstats::num_denovo */
+  int is_otu_map; uint64_t total_id_cov, total_otu;            /* -otu_map: Readstats::n_yid_ycov, lines of otu_map.txt (smr_report_otu_count) */
 } smr_summary;
 int smr_summary_write(const char* path, const smr_summary*);
 

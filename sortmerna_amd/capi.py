@@ -27,7 +27,8 @@ class IndexInfo(C.Structure):
 
 class ReportOpts(C.Structure):
     _fields_ = [("fastx", C.c_int), ("other", C.c_int), ("blast_tabular", C.c_int), ("blast_cols", C.c_char * 64), ("sam", C.c_int),
-                ("blast_pairwise", C.c_int), ("sam_sq", C.c_int), ("paired_in", C.c_int), ("paired_out", C.c_int), ("out2", C.c_int), ("sout", C.c_int), ("zip_out", C.c_int)]
+                ("blast_pairwise", C.c_int), ("sam_sq", C.c_int), ("paired_in", C.c_int), ("paired_out", C.c_int), ("out2", C.c_int), ("sout", C.c_int), ("zip_out", C.c_int),
+                ("otu_map", C.c_int), ("denovo", C.c_int), ("min_id", C.c_double), ("min_cov", C.c_double)]
 
 
 class SummaryDb(C.Structure):
@@ -41,7 +42,8 @@ class Summary(C.Structure):
                 ("gap_ext", C.c_int32), ("score_N", C.c_int32), ("sam_sq", C.c_int32), ("threads", C.c_int32),
                 ("reads_files", C.POINTER(C.c_char_p)), ("n_reads_files", C.c_uint32),
                 ("total_reads", C.c_uint64), ("num_aligned", C.c_uint64), ("all_reads_len", C.c_uint64),
-                ("min_read_len", C.c_uint32), ("max_read_len", C.c_uint32), ("dbs", C.POINTER(SummaryDb)), ("n_dbs", C.c_uint32)]
+                ("min_read_len", C.c_uint32), ("max_read_len", C.c_uint32), ("dbs", C.POINTER(SummaryDb)), ("n_dbs", C.c_uint32),
+                ("is_denovo", C.c_int), ("total_denovo", C.c_uint64), ("is_otu_map", C.c_int), ("total_id_cov", C.c_uint64), ("total_otu", C.c_uint64)]
 
 
 class Prof(C.Structure):
@@ -64,8 +66,8 @@ EXPORTS = [
     "smr_reads_digest", "smr_reads_count", "smr_reads_total_len", "smr_reads_min_len", "smr_reads_max_len", "smr_create", "smr_device_count", "smr_destroy",
     "smr_last_error", "smr_index_upload", "smr_index_check_device", "smr_index_pigeonhole", "smr_seed_tuples_fetch", "smr_seed_pool_info", "smr_index_unload", "smr_batch_select", "smr_set_seed_mode", "smr_reads_upload", "smr_reads_upload_batch", "smr_state_reset", "smr_align_part",
     "smr_traceback", "smr_counters", "smr_counters_device", "smr_results_fetch", "smr_result_record", "smr_result_record_batch", "smr_counters_accumulate",
-    "smr_result_is_hit", "smr_seed_scan", "smr_seed_hits_fetch", "smr_sw_selfcheck", "smr_sw_mode", "smr_walk_rounds", "smr_ssw_batch", "smr_cigar_batch", "smr_prof_reset", "smr_prof_get", "smr_prof_kernels", "smr_refstats_corrected", "smr_report_open",
-    "smr_report_set_db", "smr_report_set_part", "smr_report_add", "smr_report_add_pair", "smr_report_set_cmdline", "smr_report_close", "smr_report_last_error",
+    "smr_result_is_hit", "smr_seed_scan", "smr_seed_hits_fetch", "smr_sw_selfcheck", "smr_sw_mode", "smr_walk_rounds", "smr_ssw_batch", "smr_cigar_batch", "smr_idcov_part", "smr_idcov_counters", "smr_idcov_counters_device", "smr_idcov_batch", "smr_prof_reset", "smr_prof_get", "smr_prof_kernels", "smr_refstats_corrected", "smr_report_open",
+    "smr_report_set_db", "smr_report_set_part", "smr_report_add", "smr_report_add_pair", "smr_report_set_cmdline", "smr_report_otu_count", "smr_report_otu_merge", "smr_report_close", "smr_report_last_error",
     "smr_summary_write", "smr_readstats_record", "smr_readstats_key",
 ]
 
@@ -191,6 +193,14 @@ def bind(L):
     L.smr_reads_upload_batch.argtypes = [vp, i32, vp, u32]
     L.smr_reads_slice.restype = i32
     L.smr_reads_slice.argtypes = [vp, u64, u64, C.POINTER(vp)]
+    L.smr_idcov_part.restype = i32
+    L.smr_idcov_part.argtypes = [vp, i32, C.POINTER(Params), C.c_double, C.c_double]
+    L.smr_idcov_counters.restype = i32
+    L.smr_idcov_counters.argtypes = [vp, C.POINTER(u64)]
+    L.smr_idcov_counters_device.restype = i32
+    L.smr_idcov_counters_device.argtypes = [vp, C.POINTER(vp), C.POINTER(u32)]
+    L.smr_idcov_batch.restype = i32
+    L.smr_idcov_batch.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp]
     L.smr_cigar_batch.restype = i32
     L.smr_cigar_batch.argtypes = [vp, u32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, u64, vp]
     L.smr_sw_mode.restype = i32
@@ -222,6 +232,10 @@ def bind(L):
     L.smr_report_set_cmdline.argtypes = [vp, cp]
     L.smr_summary_write.restype = i32
     L.smr_summary_write.argtypes = [cp, C.POINTER(Summary)]
+    L.smr_report_otu_merge.restype = i32
+    L.smr_report_otu_merge.argtypes = [vp, vp]
+    L.smr_report_otu_count.restype = i32
+    L.smr_report_otu_count.argtypes = [vp, C.POINTER(u64)]
     L.smr_report_close.restype = i32
     L.smr_report_close.argtypes = [vp]
     L.smr_report_last_error.restype = cp

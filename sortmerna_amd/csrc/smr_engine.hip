@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "smr_kernels.hpp"
+#include "smr_idcov.hpp"
 #include "smr_ibuild.hpp"
 #include "smr_pgbuild.hpp"
 #include "smr_hostmem.hpp"
@@ -36,9 +37,9 @@ struct EvMark { hipEvent_t e; int kind; };        // kind < 0: end of a run of i
 
 #define SMR_MAX_BATCHES 16
 // kernel families timed apart (one HIP event between them on the engine's stream)
-enum { KP_KEYS = 0, KP_SPLIT, KP_BINS, KP_PG0, KP_PG1, KP_FINISH, KP_CAND, KP_CHAIN, KP_BEGINS, KP_TRACE, KP_WALK, KP_SW16, KP_WNEXT, KP_COUNT };
+enum { KP_KEYS = 0, KP_SPLIT, KP_BINS, KP_PG0, KP_PG1, KP_FINISH, KP_CAND, KP_CHAIN, KP_BEGINS, KP_TRACE, KP_WALK, KP_SW16, KP_WNEXT, KP_IDCOV, KP_COUNT };
 static const char* const KP_NAME[KP_COUNT] = {"k_seed_keys", "k_seed_split", "k_seed_bins", "k_seed_pg<0>", "k_seed_pg<1>", "k_seed_finish", "k_cand", "k_chain", "k_begins", "k_trace",
-                                              "k_walk", "k_sw16", "k_wnext"};
+                                              "k_walk", "k_sw16", "k_wnext", "k_idcov"};
 
 // One resident read batch: packed reads + everything the reference keeps per read in the KVDB (read.cpp:429-539)
 // + its Readstats counter block + its CIGAR pool.  Several batches can be resident at once (the host uploads
@@ -55,6 +56,10 @@ struct Batch {
   AlignRec* d_saved_aln = nullptr; AlignRec* d_work_aln = nullptr;
   unsigned long long* d_ctr = nullptr;
   uint32_t* d_cigar = nullptr; uint64_t cigar_words = 0;
+  // the %id / %coverage pass (smr_idcov.hpp): per read {c_yid_ycov, n_yid_ncov, n_nid_ycov, n_denovo} of Read (read.hpp), part of what round-trips
+  // through the reference's KVDB; allocated by the first smr_idcov_part of the batch (a run that never asks for the pass pays nothing)
+  uint32_t* d_idcov = nullptr; size_t cap_idcov = 0; bool idcov_ran = false;
+  std::vector<uint32_t> h_idcov;           // of the reads with alignments, packed like h_state (empty: all zero)
   // host copies of results
   std::vector<RState> h_state; std::vector<AlignRec> h_aln; std::vector<uint32_t> h_cigar;       // of the reads with alignments, packed
   std::vector<uint32_t> h_idx, h_map;                                                            // packed position -> read, read -> packed position (or ~0)
@@ -115,6 +120,7 @@ struct smr_ctx {
   uint32_t* d_stab = nullptr; unsigned long long* d_tuples2 = nullptr; // per block: CH_EXT_CAP-slot table (4 arrays), tuples grouped by member
   size_t chain_lds_attr = 0, begins_lds_attr = 0, split_lds_attr = 0, bins_lds_attr = 0;
   uint32_t* d_fidx = nullptr; RState* d_fstate = nullptr; AlignRec* d_faln = nullptr; size_t fetch_cap_r = 0, fetch_cap_a = 0;   // staging of smr_results_fetch
+  uint32_t* d_fidcov = nullptr; size_t fetch_cap_i = 0;                                                                              // ... of the per-read id / coverage counters
   int sw_mode = getenv("SMR_SW_PACKED") ? atoi(getenv("SMR_SW_PACKED")) : 2;   // 1 / 2: packed 16-bit Smith-Waterman kernels (smr_sw_pk.hpp; 2 = lane hand-over by wave_ror, measured faster) where they apply
   unsigned long long* d_keys = nullptr; uint32_t keys_cap = 0;
   unsigned long long* d_pairs = nullptr; uint32_t* d_lis = nullptr; uint32_t pairs_cap = 0;
@@ -353,7 +359,7 @@ extern "C" void smr_destroy(smr_ctx* c) {
     Batch& B = c->bt[k];
     dev_free(&B.d_words); dev_free(&B.d_rec_off); dev_free(&B.d_len);
     dev_free(&B.d_saved); dev_free(&B.d_work); dev_free(&B.d_rw); dev_free(&B.d_marks); dev_free(&B.d_saved_aln); dev_free(&B.d_work_aln); dev_free(&B.d_ctr);
-    dev_free(&B.d_cigar);
+    dev_free(&B.d_cigar); dev_free(&B.d_idcov);
   }
   dev_free(&c->d_bound); dev_free(&c->d_rdq); dev_free(&c->d_mrec); dev_free(&c->d_mpool);
   for (int q = 0; q < 2; q++) { dev_free(&c->d_wlist[q]); dev_free(&c->d_wstate[q]); dev_free(&c->d_wtask[q]); dev_free(&c->d_wres[q]); }
@@ -371,7 +377,7 @@ extern "C" void smr_destroy(smr_ctx* c) {
   }
   for (auto& m : c->events) (void)hipEventDestroy(m.e);
   for (auto& e : c->ev_pool) (void)hipEventDestroy(e);
-  dev_free(&c->d_ctr_snap); dev_free(&c->d_fidx); dev_free(&c->d_fstate); dev_free(&c->d_faln);
+  dev_free(&c->d_ctr_snap); dev_free(&c->d_fidx); dev_free(&c->d_fstate); dev_free(&c->d_faln); dev_free(&c->d_fidcov);
   (void)hipStreamDestroy(c->upload_stream);
   (void)hipStreamDestroy(c->stream);
   delete c;
@@ -545,6 +551,9 @@ int reset_batch(smr_ctx* c, Batch& B, hipStream_t st) {
   HIPCHK(c, hipMemsetAsync(B.d_ctr, 0, (size_t)C_WINDOWS * 8, st));
   HIPCHK(c, hipMemsetAsync(B.d_ctr + C_ERR_HITCAP, 0, (size_t)(C_SW_SPEC - C_ERR_HITCAP) * 8, st));
   HIPCHK(c, hipMemsetAsync(B.d_ctr + C_PCUR, 0, (size_t)C_NSHARD * C_PCUR_STRIDE * 8, st));
+  HIPCHK(c, hipMemsetAsync(B.d_ctr + C_IDCOV, 0, 4 * 8, st));
+  if (B.d_idcov) HIPCHK(c, hipMemsetAsync(B.d_idcov, 0, std::min(B.cap_idcov, (size_t)B.n) * 16, st));
+  B.idcov_ran = false;
   HIPCHK(c, hipStreamSynchronize(st));
   B.fetched = false;
   return SMR_OK;
@@ -586,6 +595,7 @@ int upload_into(smr_ctx* c, Batch& B, const smr_reads* r, uint32_t max_aln, hipS
   HIPCHK(c, hipMemsetAsync(B.d_rw, 0, (size_t)B.n * sizeof(RWork), st));
   HIPCHK(c, hipMemsetAsync(B.d_work, 0, (size_t)B.n * sizeof(RState), st));
   B.cigar_words = 0; dev_free(&B.d_cigar);
+  if (B.cap_idcov < (size_t)B.n) { dev_free(&B.d_idcov); B.cap_idcov = 0; }       // (the next smr_idcov_part allocates it for this batch size)
   return reset_batch(c, B, st);
 }
 }  // namespace
@@ -649,6 +659,7 @@ __global__ void k_ctr_begin(unsigned long long* __restrict__ ctr, const unsigned
 extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
   if (!c || slot < 0 || slot >= 64) return SMR_ERR_ARG;
   if (!c->idx[slot].used || !c->b->d_saved) { set_err(c, "index slot empty or no reads uploaded"); return SMR_ERR_STATE; }
+  if (c->b->idcov_ran) { set_err(c, "smr_align_part after smr_idcov_part: the id / coverage pass counts final alignments (denovo_stats runs after align, processor.cpp:368); smr_state_reset or upload first"); return SMR_ERR_STATE; }
   HIPCHK(c, hipSetDevice(c->device));
   int rc = check_params(c, p); if (rc) return rc;
   const DevIndex& di = c->idx[slot];
@@ -809,6 +820,7 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
 }
 
 #include "smr_engine_trace.hpp"
+#include "smr_engine_idcov.hpp"
 extern "C" int smr_counters(smr_ctx* c, uint64_t* out, uint32_t n_db) {
   if (!c || !out) return SMR_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
@@ -826,12 +838,13 @@ extern "C" int smr_counters_device(smr_ctx* c, void** dptr, uint32_t* n_u64) {
 
 __global__ void k_ctr_accumulate(const unsigned long long* __restrict__ ctr, unsigned long long* __restrict__ acc, uint32_t n) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) acc[k] += ctr[k];
+  if (k < n) acc[k] += ctr[k < C_PER_DB + 64 ? k : C_IDCOV + (k - (C_PER_DB + 64))];      // 66 .. 69: n_yid_ycov, n_yid_ncov, n_nid_ycov, num_denovo
 }
 // acc[k] += the selected batch's counter k, k < n_u64 <= the block smr_counters_device hands out, on the device (a host that aligns its
-// shard in chunks keeps ONE device block of sums and all-reduces that over the ranks)
+// shard in chunks keeps ONE device block of sums and all-reduces that over the ranks).  k = 66 .. 69 are the four sums of the id / coverage pass
+// (smr_idcov_counters), which live elsewhere in the batch's block: a caller that wants them keeps a block of SMR_COUNTERS_WITH_IDCOV u64.
 extern "C" int smr_counters_accumulate(smr_ctx* c, void* d_acc, uint32_t n_u64) {
-  if (!c || !d_acc || n_u64 > C_PER_DB + 64 || !c->b->d_ctr) return SMR_ERR_ARG;
+  if (!c || !d_acc || n_u64 > C_PER_DB + 64 + 4 || !c->b->d_ctr) return SMR_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   hipLaunchKernelGGL(k_ctr_accumulate, dim3((n_u64 + 127) / 128), dim3(128), 0, c->stream, (const unsigned long long*)c->b->d_ctr, (unsigned long long*)d_acc, n_u64);
   HIPCHK(c, hipGetLastError());
@@ -880,6 +893,14 @@ extern "C" int smr_results_fetch(smr_ctx* c) {
     HIPCHK(c, hipMemcpyAsync(B.h_aln.data(), c->d_faln, nhit * B.slots * sizeof(AlignRec), hipMemcpyDeviceToHost, c->stream));
   }
   if (cw) HIPCHK(c, hipMemcpyAsync(B.h_cigar.data(), B.d_cigar, cw * 4, hipMemcpyDeviceToHost, c->stream));
+  B.h_idcov.clear();
+  if (B.d_idcov && nhit) {
+    if (c->fetch_cap_i < need_r) { if ((rc = dev_alloc(c, &c->d_fidcov, need_r * 4))) return rc; c->fetch_cap_i = need_r; }
+    B.h_idcov.resize(nhit * 4);
+    hipLaunchKernelGGL(k_idcov_gather, dim3((uint32_t)((nhit + 255) / 256)), dim3(256), 0, c->stream, (const uint32_t*)c->d_fidx, (const unsigned long long*)&B.d_ctr[C_FETCH_N],
+                       (const uint32_t*)B.d_idcov, c->d_fidcov);
+    HIPCHK(c, hipMemcpyAsync(B.h_idcov.data(), c->d_fidcov, nhit * 16, hipMemcpyDeviceToHost, c->stream));
+  }
   B.h_map.assign(B.n, 0xFFFFFFFFu);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (size_t j = 0; j < nhit; j++) B.h_map[B.h_idx[j]] = (uint32_t)j;
@@ -909,8 +930,11 @@ static size_t record_of(const Batch& B, uint32_t i, uint8_t* buf, size_t cap) {
   if (!buf || cap < need) return need;
   uint8_t* p = buf;
   auto put = [&](const void* v, size_t n) { memcpy(p, v, n); p += n; };
-  uint32_t z32 = 0; uint8_t z8 = 0;
-  put(&s.lastIndex, 4); put(&s.lastPart, 4); put(&z32, 4); put(&z32, 4); put(&z32, 4); put(&z32, 4);
+  uint8_t z8 = 0;
+  // Read::c_yid_ycov, n_yid_ncov, n_nid_ycov, n_denovo: zero until smr_idcov_part has run (the reference: until denovo_stats)
+  const uint32_t z4[4] = {0, 0, 0, 0};
+  const uint32_t* ic = c->b->h_idcov.size() >= 4 * ((size_t)j + 1) ? c->b->h_idcov.data() + 4 * (size_t)j : z4;
+  put(&s.lastIndex, 4); put(&s.lastPart, 4); put(ic, 16);
   put(&s.is_done, 1); put(&s.is_hit, 1); put(&z8, 1);
   put(&s.max_SW_count, 2);
   int32_t na = (int32_t)c->b->last_num_alignments; put(&na, 4);      // Read::init: num_alignments = opts.num_alignments (if > 0)

@@ -111,12 +111,16 @@ enum {
   // what the seed-stage kernels THEMSELVES move, for the roofline of each (smr_prof_kernels): tuples of the forward searches / of both
   // (every tuple is written once by k_seed_keys, read and written once by each of the two sort passes, read once by k_seed_pg), and the
   // algorithmic HBM bytes of k_seed_keys' inputs, of the two search launches and of k_seed_finish -- every kernel documents its own sum
-  C_TUP_F, C_TUP_ALL, C_B_KEYS, C_B_PG0, C_B_PG1, C_B_FIN, C_COUNT = 112,
+  C_TUP_F, C_TUP_ALL, C_B_KEYS, C_B_PG0, C_B_PG1, C_B_FIN,
+  // the id / coverage pass (smr_idcov.hpp): Readstats::n_yid_ycov, n_yid_ncov, n_nid_ycov, num_denovo (readstats.hpp:77-85; they start over with
+  // the batch's state like num_aligned), then the lengths of its two work lists and the alignments it found without a CIGAR
+  C_IDCOV, C_IDCOV_FEW = C_IDCOV + 4, C_IDCOV_MANY, C_IDCOV_NOCIG, C_COUNT = 112,
   // Work counters and the pool cursor are sharded 64 ways (by block id): one address would serialise ~10 ns per
   // atomic over ~10^6 waves.  Shard s keeps counter C_WINDOWS+k (k < 9) at C_SHARDS + 32*s + k and C_TUP_F+k at C_SHARDS + 32*s + 9 + k
   // (slots 16.. of a shard: the cycle counters of the -DSMR_*_PHASES debug builds); the host folds them.
   C_NSHARD = 64, C_SHARD_W = 32, C_SHARD_X = 9, C_SHARD_NX = 6, C_SHARD_PH = 16, C_SHARDS = C_COUNT, C_PCUR = C_SHARDS + C_SHARD_W * C_NSHARD, C_PCUR_STRIDE = 16 /* a 128-byte line per cursor: atomics on one line queue up */, C_TOTAL = C_PCUR + C_NSHARD * C_PCUR_STRIDE
 };
+static_assert(C_IDCOV_NOCIG < C_COUNT, "counter block");
 __device__ __forceinline__ void ctr_add(unsigned long long* ctr, int idx, unsigned long long v) {
   atomicAdd(&ctr[C_SHARDS + (blockIdx.x & (C_NSHARD - 1)) * C_SHARD_W + (idx >= C_TUP_F ? C_SHARD_X + idx - C_TUP_F : idx - C_WINDOWS)], v);
 }

@@ -7,6 +7,8 @@
 //   SAM (+ @SQ header lines)   ReportSam::append / write_header   report_sam.cpp:64-152, 155-211
 //   aligned.log                Summary::to_string                 summary.cpp:102-175
 //   %id / mismatches / gaps    Read::calc_miss_gap_match          read.cpp:547-589
+//   aligned_denovo.fa|fq       ReportDenovo::append               report_denovo.cpp:57-134 (which reads: output.cpp:133-143)
+//   otu_map.txt                fill_otu_map2 / OtuMap::write      otumap.cpp:72-105, 131-281
 // Input per read: the original header line, letters, quality and the Read::toBinString record (read.cpp:429-462) that
 // smr_result_record returns.  Rows are buffered per (index, part) and written in that order, like the reference's loop.
 #include <algorithm>
@@ -45,14 +47,17 @@ struct Aln {
 struct Db { double lambda = 0, K = 0; uint64_t full_ref = 0, full_read = 0; };
 
 // Read::toBinString layout (read.cpp:429-462, ssw.hpp:106-140)
-bool parse_record(const uint8_t* b, size_t n, bool& is_hit, std::vector<Aln>& out) {
+// idcov (may be null): Read::c_yid_ycov, n_yid_ncov, n_nid_ycov, n_denovo -- what smr_idcov_part (the reference: denovo_stats) left in the record
+bool parse_record(const uint8_t* b, size_t n, bool& is_hit, std::vector<Aln>& out, uint32_t* idcov = nullptr) {
   out.clear(); is_hit = false;
+  if (idcov) idcov[0] = idcov[1] = idcov[2] = idcov[3] = 0;
   if (n == 0) return true;
   size_t o = 0;
   auto rd = [&](void* dst, size_t k) { if (o + k > n) return false; memcpy(dst, b + o, k); o += k; return true; };
   uint32_t u32[6]; uint8_t fl[3]; uint16_t sw; int32_t na; uint32_t hs; uint64_t asz; uint32_t mn, mx; uint64_t cnt;
   if (!rd(u32, 24) || !rd(fl, 3) || !rd(&sw, 2) || !rd(&na, 4) || !rd(&hs, 4) || !rd(&asz, 8) || !rd(&mn, 4) || !rd(&mx, 4) || !rd(&cnt, 8)) return false;
   is_hit = fl[1] != 0;
+  if (idcov) for (int k = 0; k < 4; k++) idcov[k] = u32[2 + k];
   for (uint64_t k = 0; k < cnt; k++) {
     uint64_t rl, cl;
     if (!rd(&rl, 8) || !rd(&cl, 8)) return false;
@@ -80,7 +85,12 @@ std::string cigar_text(const Aln& a, size_t readlen) {        // soft clips as r
 
 struct smr_report {
   std::string dir; smr_report_opts o; bool fastq = false;
-  Out f_aligned[4], f_other[4];
+  Out f_aligned[4], f_other[4], f_denovo[4];
+  // otu_map.txt: (reference id, read id) per (index, part) in the order the reads were added = the order of fill_otu_map's loops at -threads 1
+  std::map<std::pair<uint32_t, uint32_t>, std::vector<std::pair<std::string, std::string>>> otu;
+  bool any_yid_ycov = false;                                           // Readstats::n_yid_ycov > 0 (otumap.cpp:200): is there a map file at all
+  uint64_t* otu_count_out = nullptr;
+  bool otu_handed_over = false;                                        // smr_report_otu_merge moved this object's entries into another one
   int num_out = 1;                                                     // ReportFxBase::set_num_out (report_fx_base.cpp:163-169)
   std::map<uint32_t, Db> dbs;
   std::map<std::pair<uint32_t, uint32_t>, const smr_index*> parts;
@@ -108,10 +118,11 @@ extern "C" int smr_report_open(const char* out_dir, const smr_report_opts* opts,
   for (int j = 0; j < r->num_out; j++) {
     if (opts->fastx) ok = r->f_aligned[j].open(r->dir + "/aligned" + sfx(j) + ext, opts->zip_out != 0) && ok;
     if (opts->other) ok = r->f_other[j].open(r->dir + "/other" + sfx(j) + ext, opts->zip_out != 0) && ok;
+    if (opts->denovo) ok = r->f_denovo[j].open(r->dir + "/aligned_denovo" + sfx(j) + ext, opts->zip_out != 0) && ok;       // report_denovo.cpp:51
   }
   if (!ok) {
     if (err && errcap) snprintf(err, errcap, "cannot create report files in %s", out_dir);
-    for (int j = 0; j < 4; j++) { r->f_aligned[j].close(); r->f_other[j].close(); }
+    for (int j = 0; j < 4; j++) { r->f_aligned[j].close(); r->f_other[j].close(); r->f_denovo[j].close(); }
     delete r; return SMR_ERR_IO;
   }
   *out = r;
@@ -139,14 +150,20 @@ void write_fx(smr_report* r, Out& f, const char* header, const char* seq, const 
   f.put(t);
 }
 int add_rows(smr_report* r, const char* header, const char* seq, const char* qual, const std::vector<Aln>& alns);
+int add_otu(smr_report* r, const char* header, const char* seq, const std::vector<Aln>& alns, const uint32_t* idcov);
+// a read for de novo clustering: none of its alignments passed %id or %coverage (output.cpp:133-143)
+inline bool is_dn(const uint32_t* ic) { return ic[3] > 0 && ic[0] == 0 && ic[1] == 0 && ic[2] == 0; }
 }  // namespace
 
 extern "C" int smr_report_add(smr_report* r, const char* header, const char* seq, const char* qual, const uint8_t* record, size_t record_len) {
   if (!r || !header || !seq) return SMR_ERR_ARG;
   bool is_hit = false;
   std::vector<Aln> alns;
-  if (!parse_record(record, record_len, is_hit, alns)) { r->err = "malformed record"; return SMR_ERR_ARG; }
+  uint32_t ic[4];
+  if (!parse_record(record, record_len, is_hit, alns, ic)) { r->err = "malformed record"; return SMR_ERR_ARG; }
   write_fx(r, is_hit ? r->f_aligned[0] : r->f_other[0], header, seq, qual);
+  if (r->o.denovo && is_dn(ic)) write_fx(r, r->f_denovo[0], header, seq, qual);
+  if (r->o.otu_map) { const int rc = add_otu(r, header, seq, alns, ic); if (rc != SMR_OK) return rc; }
   return add_rows(r, header, seq, qual, alns);
 }
 
@@ -155,7 +172,8 @@ extern "C" int smr_report_add_pair(smr_report* r, const char* header1, const cha
   if (!r || !header1 || !seq1 || !header2 || !seq2) return SMR_ERR_ARG;
   bool hit[2] = {false, false};
   std::vector<Aln> alns[2];
-  if (!parse_record(record1, record1_len, hit[0], alns[0]) || !parse_record(record2, record2_len, hit[1], alns[1])) { r->err = "malformed record"; return SMR_ERR_ARG; }
+  uint32_t ic[2][4];
+  if (!parse_record(record1, record1_len, hit[0], alns[0], ic[0]) || !parse_record(record2, record2_len, hit[1], alns[1], ic[1])) { r->err = "malformed record"; return SMR_ERR_ARG; }
   const char* hd[2] = {header1, header2}; const char* sq[2] = {seq1, seq2}; const char* ql[2] = {qual1, qual2};
   const bool both = hit[0] && hit[1], any = hit[0] || hit[1];
   const smr_report_opts& o = r->o;
@@ -181,11 +199,72 @@ extern "C" int smr_report_add_pair(smr_report* r, const char* header1, const cha
       if (idx >= 0) write_fx(r, r->f_other[idx], hd[i], sq[i], ql[i]);
     }
   }
-  for (int i = 0; i < 2; i++) { const int rc = add_rows(r, hd[i], sq[i], ql[i], alns[i]); if (rc != SMR_OK) return rc; }
+  // aligned_denovo.* (ReportDenovo::append, report_denovo.cpp:57-134): called when either mate is a de novo read (output.cpp:133-143)
+  if (o.denovo && (is_dn(ic[0]) || is_dn(ic[1]))) {
+    const bool dn[2] = {is_dn(ic[0]), is_dn(ic[1])}, both_dn = dn[0] && dn[1];
+    for (int i = 0; i < 2; i++) {
+      int idx = 0;
+      if (r->num_out == 1) { if (!(o.paired_in || dn[i])) continue; idx = 0; }
+      else if (r->num_out == 2 && o.out2) { if (o.paired_out && !both_dn) break; idx = (o.paired_in || dn[i]) ? i : 0; }       // (:74-85 has no `continue`: the other mate is written too, to the file `idx` was left at)
+      else if (r->num_out == 2) { if (both_dn) idx = 0; else if (dn[i]) idx = 1; else continue; }
+      else { if (both_dn) idx = i; else if (dn[i]) idx = i + 2; else continue; }
+      write_fx(r, r->f_denovo[idx], hd[i], sq[i], ql[i]);
+    }
+  }
+  for (int i = 0; i < 2; i++) {
+    if (o.otu_map) { const int rc = add_otu(r, hd[i], sq[i], alns[i], ic[i]); if (rc != SMR_OK) return rc; }
+    const int rc = add_rows(r, hd[i], sq[i], ql[i], alns[i]); if (rc != SMR_OK) return rc;
+  }
   return SMR_OK;
 }
 
 namespace {
+// fill_otu_map2 (otumap.cpp:131-190): a read with c_yid_ycov > 0 has each of its alignments classified AGAIN -- with the rounding written
+// `* 0.001` here, `/ 1000.0` in denovo_stats_run -- and joins the group of the reference of every alignment that passes both thresholds.
+// As in denovo_stats_run the letters walked are those of the FORWARD read, also for an alignment on the reverse strand: neither function
+// calls Read::revIntStr(), which only the BLAST / SAM writers do (report_blast.cpp:132, report_sam.cpp:118).
+int add_otu(smr_report* r, const char* header, const char* seq, const std::vector<Aln>& alns, const uint32_t* idcov) {
+  if (idcov[0] == 0) return SMR_OK;
+  r->any_yid_ycov = true;
+  std::string id(header);                                  // Read::getSeqId (read.cpp:371-377)
+  id = id.substr(0, id.find(' '));
+  size_t k0 = 0; while (k0 < id.size() && (id[k0] == '>' || id[k0] == '@')) k0++;
+  id = id.substr(k0);
+  const size_t len = strlen(seq);
+  std::string fwd(len, 0);
+  for (size_t i = 0; i < len; i++) fwd[i] = (char)nt_code((unsigned char)seq[i]);
+  for (const Aln& a : alns) {
+    const std::pair<uint32_t, uint32_t> key{a.index_num, a.part};
+    auto pit = r->parts.find(key);
+    if (pit == r->parts.end()) { r->err = "alignment refers to an (index, part) that was not registered"; return SMR_ERR_STATE; }
+    const smr_index* ix = pit->second;
+    if (a.ref_num >= ix->n_refs()) { r->err = "ref_num out of range"; return SMR_ERR_ARG; }
+    const uint8_t* refseq = ix->ref_seq.data() + ix->ref_off[a.ref_num];
+    const int64_t reflen = (int64_t)(ix->ref_off[a.ref_num + 1] - ix->ref_off[a.ref_num]);
+    uint32_t n_miss = 0, n_gap = 0, n_match = 0;
+    int64_t qb = a.ref_begin1, pb = a.read_begin1;
+    for (uint32_t c : a.cigar) {
+      const uint32_t letter = c & 0xF, length = c >> 4;
+      if (letter == 0) {
+        for (uint32_t u = 0; u < length; u++, ++qb, ++pb) {
+          if (qb < 0 || qb >= reflen || pb < 0 || pb >= (int64_t)len) { r->err = "a CIGAR runs past its read or its reference"; return SMR_ERR_ARG; }
+          if ((char)refseq[qb] != fwd[pb]) ++n_miss; else ++n_match;
+        }
+      } else if (letter == 1) { pb += length; n_gap += length; }
+      else { qb += length; n_gap += length; }
+    }
+    const double idf = (double)n_match / (double)(n_miss + n_gap + n_match);
+    const double cov = (double)std::abs(a.read_end1 - a.read_begin1 + 1) / (double)a.readlen;
+    const double idr = std::floor(idf * 1000.0 + 0.5) * 0.001, covr = std::floor(cov * 1000.0 + 0.5) * 0.001;
+    if (!(idr >= r->o.min_id && covr >= r->o.min_cov)) continue;
+    size_t first_seq = 0;
+    for (uint32_t q = 0; q < a.part && q < ix->parts.size(); q++) first_seq += ix->parts[q].numseq_part;
+    const std::string ref_id = first_seq + a.ref_num < ix->sq_header.size() ? ix->sq_header[first_seq + a.ref_num].first : std::string("*");
+    r->otu[key].emplace_back(ref_id, id);
+  }
+  return SMR_OK;
+}
+
 int add_rows(smr_report* r, const char* header, const char* seq, const char* qual, const std::vector<Aln>& alns) {
   if (alns.empty() || (!r->o.blast_tabular && !r->o.blast_pairwise && !r->o.sam)) return SMR_OK;
   // Read::getSeqId (read.cpp:371-377)
@@ -300,7 +379,27 @@ int add_rows(smr_report* r, const char* header, const char* seq, const char* qua
 extern "C" int smr_report_close(smr_report* r) {
   if (!r) return SMR_ERR_ARG;
   int rc = SMR_OK;
-  for (int j = 0; j < 4; j++) { r->f_aligned[j].close(); r->f_other[j].close(); }
+  for (int j = 0; j < 4; j++) { r->f_aligned[j].close(); r->f_other[j].close(); r->f_denovo[j].close(); }
+  if (r->o.otu_map && !r->otu_handed_over) {
+    // OtuMap::write (otumap.cpp:72-105): groups in std::map order of the reference id, the reads of a group in (index, part) loop order, then
+    // input order; plain text whatever zip_out says (std::ofstream); no file at all when no read passed both thresholds (otumap.cpp:200,276)
+    std::map<std::string, std::vector<std::string>> groups;
+    for (auto& kv : r->otu) for (auto& pr : kv.second) groups[pr.first].push_back(pr.second);
+    if (r->otu_count_out) *r->otu_count_out = r->any_yid_ycov ? groups.size() : 0;
+    if (r->any_yid_ycov) {
+      FILE* f = fopen((r->dir + "/otu_map.txt").c_str(), "wb");
+      if (!f) rc = SMR_ERR_IO;
+      else {
+        for (auto& g : groups) {
+          std::string line = g.first + "\t";
+          for (size_t i = 0; i < g.second.size(); i++) { line += g.second[i]; if (i + 1 < g.second.size()) line += "\t"; }
+          line += "\n";
+          fwrite(line.data(), 1, line.size(), f);
+        }
+        fclose(f);
+      }
+    }
+  }
   if (r->o.blast_tabular || r->o.blast_pairwise) {
     Out f;
     if (!f.open(r->dir + "/aligned.blast", r->o.zip_out != 0)) rc = SMR_ERR_IO; else { for (auto& kv : r->blast) f.put(kv.second); f.close(); }
@@ -325,6 +424,24 @@ extern "C" int smr_report_close(smr_report* r) {
   }
   delete r;
   return rc;
+}
+
+// One map for a run whose reads went through several report objects (one per device, each fed its shard of the reads file in input order):
+// the entries of `src` are appended to those of `dst` per (index, part), so that after merging the shards in rank order every group holds its
+// reads in (index, part) loop order, then input order -- what the reference writes at -threads 1.  `src` then writes no map when it is closed.
+extern "C" int smr_report_otu_merge(smr_report* dst, smr_report* src) {
+  if (!dst || !src || dst == src || !dst->o.otu_map || !src->o.otu_map) return SMR_ERR_ARG;
+  for (auto& kv : src->otu) { auto& d = dst->otu[kv.first]; d.insert(d.end(), kv.second.begin(), kv.second.end()); }
+  src->otu.clear();
+  dst->any_yid_ycov = dst->any_yid_ycov || src->any_yid_ycov;
+  src->otu_handed_over = true;
+  return SMR_OK;
+}
+
+extern "C" int smr_report_otu_count(smr_report* r, uint64_t* total_otu) {
+  if (!r || !total_otu) return SMR_ERR_ARG;
+  *total_otu = 0; r->otu_count_out = total_otu;
+  return SMR_OK;
 }
 
 extern "C" int smr_report_set_cmdline(smr_report* r, const char* cmdline) {
@@ -353,11 +470,15 @@ extern "C" int smr_summary_write(const char* path, const smr_summary* s) {
      << "    Number of alignment processing threads = " << s->threads << "\n";
   for (uint32_t i = 0; i < s->n_reads_files; i++) ss << "    Reads file: " << s->reads_files[i] << "\n";
   ss << "    Total reads = " << s->total_reads << "\n\n" << " Results:\n";
+  if (s->is_denovo) ss << "    Total reads for de novo clustering = " << s->total_denovo << "\n";
   const float ratio = (float)s->num_aligned / s->total_reads;
   ss << std::setprecision(2) << std::fixed
      << "    Total reads passing E-value threshold = " << s->num_aligned << " (" << (ratio * 100) << ")\n"
-     << "    Total reads failing E-value threshold = " << s->total_reads - s->num_aligned << " (" << (1 - ratio) * 100 << ")\n"
-     << "    Minimum read length = " << s->min_read_len << "\n" << "    Maximum read length = " << s->max_read_len << "\n"
+     << "    Total reads failing E-value threshold = " << s->total_reads - s->num_aligned << " (" << (1 - ratio) * 100 << ")\n";
+  if (s->is_otu_map)        // (the doubled percent signs are what the reference prints: summary.cpp:155 writes "%%id" into a stream)
+    ss << "    Total reads passing %%id and %%coverage thresholds = " << s->total_id_cov << " (" << ((float)s->total_id_cov / s->total_reads * 100) << ")\n"
+       << "    Total OTUs = " << s->total_otu << "\n";
+  ss << "    Minimum read length = " << s->min_read_len << "\n" << "    Maximum read length = " << s->max_read_len << "\n"
      << "    Mean read length    = " << (s->total_reads ? s->all_reads_len / s->total_reads : 0) << "\n\n" << " Coverage by database:\n";
   for (uint32_t i = 0; i < s->n_dbs; i++) {
     const float pcn = (float)((float)s->dbs[i].reads_matched / s->total_reads) * 100;
@@ -379,7 +500,7 @@ extern "C" const char* smr_report_last_error(const smr_report* r) { return r ? r
 // Readstats persistence: what the reference keeps in its KVDB next to the per-read records after the alignment stage --
 // Readstats::store_to_db (readstats.cpp:291-295) puts Readstats::toBstring() (:133-174) under the decimal std::hash of the '_'-joined
 // basenames of the read files (:82-91, util.cpp:216-222).  The identity / coverage counters and is_stats_calc belong to later stages of
-// the reference and are zero / false here; is_set_aligned_id_cov stays false because n_yid_ycov is 0 (readstats.cpp:199-203).
+// the reference and are zero / false in THIS record -- the one stored after the alignment stage, before denovo_stats (afterwards: smr_idcov_counters); is_set_aligned_id_cov stays false because n_yid_ycov is 0 (readstats.cpp:199-203).
 // ------------------------------------------------------------------------------------------------
 extern "C" size_t smr_readstats_record(uint64_t all_reads_count, uint64_t all_reads_len, uint32_t min_read_len, uint32_t max_read_len, uint64_t num_aligned,
                                        uint64_t num_short, const uint64_t* reads_matched_per_db, uint32_t n_db, uint8_t* buf, size_t cap) {

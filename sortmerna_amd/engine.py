@@ -333,6 +333,36 @@ class Engine:
     def traceback(self, slot, params):
         self._chk(self.L.smr_traceback(self.h, slot, C.byref(params)), "smr_traceback")
 
+    def idcov_part(self, slot, params, min_id, min_cov):
+        """the %id / %coverage pass (the reference's denovo_stats) over the stored alignments of (params.index_num, params.part), whose references
+        are resident in `slot`; after traceback() of every part of the run (smr_idcov_part)"""
+        self._chk(self.L.smr_idcov_part(self.h, slot, C.byref(params), float(min_id), float(min_cov)), "smr_idcov_part")
+
+    def idcov_counters(self):
+        out = (C.c_uint64 * 4)()
+        self._chk(self.L.smr_idcov_counters(self.h, out), "smr_idcov_counters")
+        return dict(n_yid_ycov=out[0], n_yid_ncov=out[1], n_nid_ycov=out[2], num_denovo=out[3])
+
+    def idcov_counters_device(self):
+        p = C.c_void_p()
+        n = C.c_uint32()
+        self._chk(self.L.smr_idcov_counters_device(self.h, C.byref(p), C.byref(n)), "smr_idcov_counters_device")
+        return p.value, n.value
+
+    def idcov_batch(self, reads, refs, cigars, read_begin, read_end, readlen, min_id, min_cov):
+        """reads: whole FORWARD reads, refs: the reference windows from each alignment's first reference letter on (byte strings in the 0..4
+        alphabet), cigars: u32 arrays (len << 4 | op); -> uint32 array (n, 4): n_miss, n_gap, n_match, class 0..3 (smr_idcov_batch)"""
+        n = len(reads)
+        ro = np.zeros(n + 1, dtype=np.uint64); fo = np.zeros(n + 1, dtype=np.uint64); co = np.zeros(n + 1, dtype=np.uint64)
+        ro[1:] = np.cumsum([len(x) for x in reads]); fo[1:] = np.cumsum([len(x) for x in refs]); co[1:] = np.cumsum([len(x) for x in cigars])
+        rb = np.frombuffer(b"".join(bytes(x) for x in reads) + b"\0", dtype=np.uint8).copy(); fb = np.frombuffer(b"".join(bytes(x) for x in refs) + b"\0", dtype=np.uint8).copy()
+        cg = np.concatenate([np.asarray(x, dtype=np.uint32) for x in cigars] + [np.zeros(1, dtype=np.uint32)])
+        b1 = np.asarray(read_begin, dtype=np.int32); e1 = np.asarray(read_end, dtype=np.int32); rl = np.asarray(readlen, dtype=np.uint32)
+        out = np.zeros((max(n, 1), 4), dtype=np.uint32)
+        self._chk(self.L.smr_idcov_batch(self.h, n, rb.ctypes.data, ro.ctypes.data, fb.ctypes.data, fo.ctypes.data, cg.ctypes.data, co.ctypes.data,
+                                         b1.ctypes.data, e1.ctypes.data, rl.ctypes.data, float(min_id), float(min_cov), out.ctypes.data), "smr_idcov_batch")
+        return out[:n]
+
     def counters(self, n_db=1):
         out = (C.c_uint64 * (2 + n_db))()
         self._chk(self.L.smr_counters(self.h, out, n_db), "smr_counters")
@@ -343,6 +373,11 @@ class Engine:
         n = C.c_uint32()
         self._chk(self.L.smr_counters_device(self.h, C.byref(p), C.byref(n)), "smr_counters_device")
         return p.value, n.value
+
+    def counters_accumulate(self, d_acc, n_u64):
+        """d_acc[k] += counter k of the selected batch, k < n_u64, on the device (smr_counters_accumulate); d_acc: a device address.  k < 66:
+        the block of counters_device(); k = 66 .. 69: the four sums of idcov_counters()"""
+        self._chk(self.L.smr_counters_accumulate(self.h, d_acc, n_u64), "smr_counters_accumulate")
 
     def fetch(self):
         self._chk(self.L.smr_results_fetch(self.h), "smr_results_fetch")
@@ -419,13 +454,17 @@ class Engine:
             self.h = None
 
 
-def align(engine, reads, index_parts, params_per_index, with_cigar=True, max_alignments_per_read=None):
+def align(engine, reads, index_parts, params_per_index, with_cigar=True, max_alignments_per_read=None, id_cov=None):
     """processor.cpp:align(): index_parts = [[Index part0, part1, ...] per --ref], params_per_index = [Params per --ref]
-    (each carrying that DB's minimal_score).  Returns nothing; results stay in `engine` (fetch()/record())."""
+    (each carrying that DB's minimal_score).  Returns nothing; results stay in `engine` (fetch()/record()).
+    id_cov = (min_id, min_cov): the %id / %coverage pass (denovo_stats) over every (index, part) once all of them are aligned."""
+    if id_cov is not None and not with_cigar:
+        raise SmrError("align: id_cov needs the CIGARs (with_cigar=True)")
     p0 = params_per_index[0]
     slots = max_alignments_per_read or (p0.num_alignments if p0.num_alignments > 0 else 32)
     engine.upload_reads(reads, slots)
     n_idx = len(index_parts)
+    single = sum(len(parts) for parts in index_parts) == 1
     for idx_num, parts in enumerate(index_parts):
         for part, ix in enumerate(parts):
             p = params_per_index[idx_num]
@@ -436,11 +475,23 @@ def align(engine, reads, index_parts, params_per_index, with_cigar=True, max_ali
             engine.align_part(0, p)
             if with_cigar:
                 engine.traceback(0, p)
+            if id_cov is not None and single:
+                engine.idcov_part(0, p, id_cov[0], id_cov[1])
             engine.unload_index(0)
+    if id_cov is not None and not single:
+        # the pass counts the FINAL alignments (the reference's denovo_stats runs after align): every part's references once more
+        for idx_num, parts in enumerate(index_parts):
+            for part, ix in enumerate(parts):
+                p = params_per_index[idx_num]
+                p.index_num = idx_num
+                p.part = part
+                engine.upload_index(ix, 0)
+                engine.idcov_part(0, p, id_cov[0], id_cov[1])
+                engine.unload_index(0)
     engine.fetch()
 
 
-def align_resident(engine, index_slots, params_per_index, with_cigar=True):
+def align_resident(engine, index_slots, params_per_index, with_cigar=True, id_cov=None):
     """Same loop over (index, part) for reads AND index parts that are already resident in HBM: index_slots is either a
     flat list of slots (one --ref, its parts in order) or a list of such lists (one per --ref).  Acts on the selected
     batch; the caller resets its state first when the batch is reused."""
@@ -456,4 +507,13 @@ def align_resident(engine, index_slots, params_per_index, with_cigar=True):
             engine.align_part(slot, p)
             if with_cigar:
                 engine.traceback(slot, p)
+    if id_cov is not None:
+        if not with_cigar:
+            raise SmrError("align_resident: id_cov needs the CIGARs (with_cigar=True)")
+        for idx_num, slots in enumerate(index_slots):
+            for part, slot in enumerate(slots):
+                p = params_per_index[idx_num]
+                p.index_num = idx_num
+                p.part = part
+                engine.idcov_part(slot, p, id_cov[0], id_cov[1])
     engine.fetch()

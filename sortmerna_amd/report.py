@@ -16,9 +16,11 @@ def corrected_sizes(K, info, all_reads_count, all_reads_len, full_read_scale=1):
 
 class Report:
     def __init__(self, out_dir, is_fastq, fastx=True, other=True, blast_cols=None, sam=False, blast_pairwise=False, sam_sq=False, cmdline=None,
-                 paired_in=False, paired_out=False, out2=False, sout=False, zip_out=False):
+                 paired_in=False, paired_out=False, out2=False, sout=False, zip_out=False, otu_map=False, denovo=False, min_id=0.0, min_cov=0.0):
         """blast_cols: None = no tabular BLAST report, else a list out of "cigar", "qcov", "qstrand" (output order);
-        blast_pairwise: the `-blast 0` text instead; sam_sq: @SQ header lines (-SQ); cmdline: text of the SAM @PG CL: field"""
+        blast_pairwise: the `-blast 0` text instead; sam_sq: @SQ header lines (-SQ); cmdline: text of the SAM @PG CL: field;
+        otu_map / denovo: otu_map.txt / aligned_denovo.fa|fq from records on which Engine.idcov_part ran with (min_id, min_cov); after close(),
+        self.total_otu holds the number of groups written"""
         self.L = capi.load()
         o = capi.ReportOpts()
         o.fastx, o.other, o.sam = int(fastx), int(other), int(sam)
@@ -27,12 +29,16 @@ class Report:
         o.blast_pairwise, o.sam_sq = int(blast_pairwise), int(sam_sq)
         o.paired_in, o.paired_out, o.out2, o.sout = int(paired_in), int(paired_out), int(out2), int(sout)
         o.zip_out = int(zip_out)
+        o.otu_map, o.denovo, o.min_id, o.min_cov = int(otu_map), int(denovo), float(min_id), float(min_cov)
+        self._otu = C.c_uint64(0)
+        self.total_otu = 0
         h = C.c_void_p()
         err = C.create_string_buffer(512)
         rc = self.L.smr_report_open(out_dir.encode(), C.byref(o), int(is_fastq), C.byref(h), err, 512)
         if rc != 0:
             raise SmrError("smr_report_open: %s (rc=%d)" % (err.value.decode(), rc))
         self.h = h
+        self._chk(self.L.smr_report_otu_count(self.h, C.byref(self._otu)), "smr_report_otu_count")
         if cmdline is not None:
             self._chk(self.L.smr_report_set_cmdline(self.h, cmdline.encode()), "smr_report_set_cmdline")
 
@@ -56,17 +62,24 @@ class Report:
         self._chk(self.L.smr_report_add_pair(self.h, h1.encode(), s1.encode(), q1.encode() if q1 else None, r1, len(r1),
                                              h2.encode(), s2.encode(), q2.encode() if q2 else None, r2, len(r2)), "smr_report_add_pair")
 
+    def merge_otu_from(self, other):
+        """the OTU map entries of `other` (the next shard of the reads, in input order) behind this report's; `other` then writes no map"""
+        self._chk(self.L.smr_report_otu_merge(self.h, other.h), "smr_report_otu_merge")
+
     def close(self):
         if self.h:
             rc = self.L.smr_report_close(self.h)
             self.h = None
+            self.total_otu = int(self._otu.value)
             if rc != 0:
                 raise SmrError("smr_report_close rc=%d" % rc)
 
 
 def write_summary(path, dbs, reads_files, total_reads, num_aligned, all_reads_len, min_read_len, max_read_len, seed_len=18, num_seeds=2, edges=4,
-                  match=2, mismatch=-3, gap_open=5, gap_ext=2, score_N=-3, sam_sq=False, threads=1, cmdline="", pid="", timestamp=""):
-    """aligned.log (summary.cpp:102-175).  dbs: list of dicts {ref_file, skiplengths, lam, K, minimal_score, reads_matched}"""
+                  match=2, mismatch=-3, gap_open=5, gap_ext=2, score_N=-3, sam_sq=False, threads=1, cmdline="", pid="", timestamp="",
+                  total_denovo=None, total_id_cov=None, total_otu=0):
+    """aligned.log (summary.cpp:102-175).  dbs: list of dicts {ref_file, skiplengths, lam, K, minimal_score, reads_matched}; total_denovo (-de_novo_otu) / total_id_cov + total_otu (-otu_map): the two
+    optional Results lines, None = not printed"""
     L = capi.load()
     arr = (capi.SummaryDb * len(dbs))()
     for i, d in enumerate(dbs):
@@ -82,6 +95,8 @@ def write_summary(path, dbs, reads_files, total_reads, num_aligned, all_reads_le
     s.reads_files, s.n_reads_files = rf, len(reads_files)
     s.total_reads, s.num_aligned, s.all_reads_len, s.min_read_len, s.max_read_len = total_reads, num_aligned, all_reads_len, min_read_len, max_read_len
     s.dbs, s.n_dbs = arr, len(dbs)
+    s.is_denovo, s.total_denovo = int(total_denovo is not None), total_denovo or 0
+    s.is_otu_map, s.total_id_cov, s.total_otu = int(total_id_cov is not None), total_id_cov or 0, total_otu
     rc = L.smr_summary_write(path.encode(), C.byref(s))
     if rc != 0:
         raise SmrError("smr_summary_write rc=%d" % rc)
