@@ -330,10 +330,35 @@ int smr_sw_mode(smr_ctx*, int set_to);
 int smr_walk_rounds(const smr_ctx*, uint32_t out[3]);
 /* The SW kernels at the ssw.h seam: for n independent pairs (read / reference window in the 0..4 alphabet, pair i = bytes [off[i], off[i+1])),
  * what ssw_align(prof, ref, refLen, gapO, gapE, flag = 2, filters, 0, 0) returns without the CIGAR (ssw.h:118-140, ssw.c:834-941):
- * out[5 i ..] = {score1, ref_begin1, ref_end1, read_begin1, read_end1}, begins = -1 when score1 < filters.  mode 0 / 1 / 2 = 32-bit / packed / packed wave_ror kernel, 3 = four pairs per wave (the fast kernels: only under the
- * schemes whose answers they share with ssw.c, SMR_ERR_ARG otherwise); mode 4 = the slow path that reproduces ssw.c's stripe geometry, any scheme. */
+ * out[5 i ..] = {score1, ref_begin1, ref_end1, read_begin1, read_end1}, begins = -1 when score1 < filters (a pair without a positive cell: {0, -1, -1, -1, 0}, as ssw.c).  mode 0 / 1 / 2 = 32-bit / packed / packed wave_ror kernel, 3 = four pairs per wave (the fast kernels: only under the
+ * schemes whose answers they share with ssw.c, SMR_ERR_ARG otherwise); mode 4 = the slow path that reproduces ssw.c's stripe geometry, any scheme;
+ * mode 5 = the long-read strips (see smr_sw_long_rows below), a fast kernel like 0 - 3. */
 int smr_ssw_batch(smr_ctx*, uint32_t n_pairs, const uint8_t* reads, const uint64_t* read_off, const uint8_t* refs, const uint64_t* ref_off,
                   int match, int mismatch, int score_N, int gap_open, int gap_ext, uint32_t filters, int mode, int32_t* out);   /* set_to 0 / 1: use the 32-bit / the packed kernel; other values: query; returns the mode in use */
+/* mode 5 of smr_ssw_batch = what k_chain<LONG> and k_begins<LONG> call for the reads of a batch with long reads (sw_wave_any_t under the packed
+ * wave_ror kernel): spans of more than 512 rows go through the strips of 128 virtual lanes x R rows, R = smr_sw_long_rows(m) in 8, 10 ... 24. */
+int smr_sw_long_rows(int m);
+/* The sixteen-problems-per-wave kernel k_sw16<rows> (smr_walk.hpp) at the same seam, launched as the candidate walk launches it: over the packed
+ * records of the SELECTED batch (smr_reads_pack + smr_reads_upload) and a task list.  Task i scores rows [aq, aq + m) of read `read` (on its
+ * reverse-complement strand when reversed = 1: row k is letter len - 1 - k, complemented) against ref[win_off, win_off + nref), `ref` (0..4
+ * alphabet, ref_len bytes) standing in for the reference letters of an index part.  list_b = 0: the task goes to the list scored with end cells
+ * and, when its score reaches `filters`, through the begin-cell pass (a second launch over tasks that run backwards from the end cell, as
+ * k_begins_prep makes them): out[5 i ..] = {score1, ref_begin1, ref_end1, read_begin1, read_end1} as ssw_align returns them for the span and
+ * the window (begins = -1 when score1 < filters).  list_b = 1: the score-only list, out[5 i ..] = {score1, -1, -1, -1, -1}.
+ * rows = 13 / 19 / 26 / 32 (spans up to 8 x rows letters); blocks = 0: the grid the walk uses, else that many blocks (a small number = several
+ * passes per block); force_any_n = 1: the kernel looks for ambiguous letters in every window even when `ref` has none.
+ * SMR_ERR_ARG (with a message) for a task outside the kernel's stated range: m > 8 x rows or > 256, !sw_pk_fits, a scheme the fast kernels
+ * do not take, rows outside the read, a window outside `ref`. */
+typedef struct {
+  uint32_t read, win_off;
+  uint16_t aq, m, nref;
+  uint8_t reversed, list_b;
+} smr_sw16_task;
+int smr_sw16_batch(smr_ctx*, uint32_t n_tasks, const smr_sw16_task* tasks, const uint8_t* ref, uint64_t ref_len, int force_any_n,
+                   int match, int mismatch, int score_N, int gap_open, int gap_ext, uint32_t filters, int rows, uint32_t blocks, int32_t* out);
+/* Launches of k_sw16<13 | 19 | 26 | 32> since smr_create: out[0..3] by the rounds of the candidate walk, out[4..7] by the begin-cell stage
+ * (which instantiation a batch gets follows from its longest read; a batch that never takes the walk path counts nothing). */
+int smr_sw16_launches(const smr_ctx*, uint64_t out[8]);
 /* The traceback kernels at the same seam: for n independent triples (read window, reference window -- both exactly the aligned spans
  * [begin1, end1] -- and the alignment's score1) the CIGAR that banded_sw returns for them (ssw.c:577-773 as called from ssw_align,
  * ssw.c:919-926): BAM-style u32 operations (length << 4 | op, op 0/1/2 = M/I/D), pair i at cigar_out[cigar_off_out[i] .. cigar_off_out[i+1]).

@@ -138,6 +138,7 @@ struct smr_ctx {
   uint2* d_wlist[2] = {nullptr, nullptr}; WState* d_wstate[2] = {nullptr, nullptr}; WTask* d_wtask[2] = {nullptr, nullptr}; uint2* d_wres[2] = {nullptr, nullptr};
   uint32_t* d_wtidx = nullptr; uint32_t* d_wslow = nullptr; unsigned long long* d_wctr = nullptr; size_t walk_cap = 0; uint32_t walk_kcap = 0, walk_rcap = 0;
   size_t walk_lds_attr = 0, pg_lds_attr = 0, search_lds_attr = 0;
+  uint64_t sw16_launches[8] = {};          // k_sw16<13 | 19 | 26 | 32> launched by the walk rounds [0..3] and by the begin-cell stage [4..7] (smr_sw16_launches)
   // rounds per (strand, pass): without SMR_WALK_ROUNDS the number adapts to what the previous part needed (the last round with more than a few
   // reads listed + the closing one: an empty round still costs three launches, ~70 us of stream time; 8 -> 4 rounds = 3 % of the bench step)
   bool walk_rounds_fixed = getenv("SMR_WALK_ROUNDS") != nullptr;
@@ -795,6 +796,7 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
             else if (swr == 26) hipLaunchKernelGGL(k_sw16<26>, dim3(sw_blocks), dim3(64), 0, c->stream, SW16_ARGS);
             else hipLaunchKernelGGL(k_sw16<32>, dim3(sw_blocks), dim3(64), 0, c->stream, SW16_ARGS);
 #undef SW16_ARGS
+            c->sw16_launches[4 + (swr == 13 ? 0 : swr == 19 ? 1 : swr == 26 ? 2 : 3)]++;
             hipLaunchKernelGGL(k_begins_apply, dim3((uint32_t)c->n_cu * 4u), dim3(256), 0, c->stream, (const uint32_t*)c->d_tasks, (const unsigned long long*)&c->b->d_ctr[C_BEGIN_N], c->b->d_work_aln, stage,
                                (const WTask*)c->d_wtask[0], (const uint2*)c->d_wres[0], c->b->d_ctr);
           }

@@ -126,6 +126,7 @@ int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, int pass, int
         else if (swr == 26) hipLaunchKernelGGL(k_sw16<26>, dim3(sw_blocks), dim3(64), 0, c->stream, SW16_ARGS);
         else hipLaunchKernelGGL(k_sw16<32>, dim3(sw_blocks), dim3(64), 0, c->stream, SW16_ARGS);
 #undef SW16_ARGS
+        c->sw16_launches[swr == 13 ? 0 : swr == 19 ? 1 : swr == 26 ? 2 : 3]++;
         ev_mark(c, KP_WNEXT);
         hipLaunchKernelGGL(k_wnext, dim3((uint32_t)c->n_cu * 2u), dim3(1024), 0, c->stream, P, is_last_strand, c->b->d_work, c->b->d_rw, c->b->d_ctr, (const uint2*)c->d_wlist[cur], (const WState*)c->d_wstate[cur],
                            (const uint2*)c->d_wres[cur], c->d_wlist[prv], (const unsigned long long*)wc, wc + WC_STRIDE, WK, (unsigned long long)n_tix, (int)rnd);

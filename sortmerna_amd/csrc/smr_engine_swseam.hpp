@@ -1,4 +1,4 @@
-// smr_engine_swseam.hpp -- the Smith-Waterman kernels at the ssw.h seam (included by smr_engine.hip): the device self-check of the packed kernels, smr_ssw_batch, smr_sw_mode,
+// smr_engine_swseam.hpp -- the Smith-Waterman kernels at the ssw.h seam (included by smr_engine.hip): the device self-check of the packed kernels, smr_ssw_batch, smr_sw16_batch, smr_sw_mode,
 // smr_walk_rounds.
 // (one translation unit: no include guard games -- this file is text of smr_engine.hip, cut out along its stages)
 
@@ -86,6 +86,9 @@ extern "C" int smr_sw_selfcheck(smr_ctx* c, uint32_t n_cases, uint32_t seed, uin
 // refLen, gapO, gapE, flag = 2, filters, 0, 0) (ssw.c:834-941) without the CIGAR -- for n independent (read, reference window) pairs,
 // one wave per pair.  A unit-test surface for the SW kernels against the reference's own ssw.c (tests/golden/ssw_pairs.json).
 // =================================================================================================
+// A pair without any positive cell: the kernels return {0, -1, m - 1}, a value none of their callers reads (a score of 0 is never accepted); ssw_align
+// returns read_end1 = 0 for it (its scan for the end row meets a column of zeros, ssw.c:329-335), and that is what the seam reports.
+__device__ __forceinline__ int ssw_end_read(const smr::SwRes& fw) { return fw.score > 0 ? fw.end_read : 0; }
 template <bool STRIPED>
 __global__ void __launch_bounds__(64) k_ssw_batch(uint32_t n_pairs, const uint8_t* __restrict__ reads, const unsigned long long* __restrict__ read_off,
                                                   const uint8_t* __restrict__ refs, const unsigned long long* __restrict__ ref_off, uint32_t lds_m, uint32_t lds_n,
@@ -105,9 +108,41 @@ __global__ void __launch_bounds__(64) k_ssw_batch(uint32_t n_pairs, const uint8_
     if (m > 0 && n > 0) {
       const smr::SwRes fw = smr::sw_wave_t<STRIPED>(rdq, m, 0, 1, rfq, n, 0, 1, bound, match, mismatch, scoreN, go, ge, mode, 0, 0, scr);
       __syncthreads();
-      res[0] = fw.score > 65535 ? 65535 : fw.score; res[2] = fw.end_ref; res[4] = fw.end_read;
+      res[0] = fw.score > 65535 ? 65535 : fw.score; res[2] = fw.end_ref; res[4] = ssw_end_read(fw);
       if ((uint32_t)res[0] >= filters && fw.score > 0) {
         const smr::SwRes bw = smr::sw_wave_t<STRIPED>(rdq, fw.end_read + 1, fw.end_read, -1, rfq, fw.end_ref + 1, fw.end_ref, -1, bound, match, mismatch, scoreN, go, ge, mode, res[0], fw.word, scr);
+        __syncthreads();
+        res[1] = fw.end_ref - bw.end_ref; res[3] = fw.end_read - bw.end_read;
+      }
+    }
+    if (lane < 5) out[(size_t)pi * 5 + lane] = res[lane];
+    __syncthreads();
+  }
+}
+
+// mode 5: through sw_wave_any_t, the entry k_chain<LONG> and k_begins<LONG> use (spans of more than 512 rows take the strips of sw_wave_long).  A kernel of
+// its own with their three waves per SIMD: the strips are noinline functions shared with them, and the compiler gives such a function the loosest
+// register budget among its callers (without the bound here k_chain<LONG> went from 168 to 280 registers: tests/test_kernel_resources.py).
+__global__ void __launch_bounds__(64, 3) k_ssw_long(uint32_t n_pairs, const uint8_t* __restrict__ reads, const unsigned long long* __restrict__ read_off,
+                                                   const uint8_t* __restrict__ refs, const unsigned long long* __restrict__ ref_off, uint32_t lds_m, uint32_t lds_n,
+                                                   int match, int mismatch, int scoreN, int go, int ge, uint32_t filters, int* __restrict__ out) {
+  SMR_DYN_LDS(unsigned char, lds_raw);
+  uint8_t* rdq = lds_raw;
+  uint8_t* rfq = rdq + lds_m;
+  int* bound = (int*)(rfq + lds_n);
+  const int lane = smr::lane_id();
+  for (uint32_t pi = blockIdx.x; pi < n_pairs; pi += gridDim.x) {
+    const int m = (int)(read_off[pi + 1] - read_off[pi]), n = (int)(ref_off[pi + 1] - ref_off[pi]);
+    for (int q = lane; q < m; q += 64) rdq[q] = reads[read_off[pi] + q];
+    for (int q = lane; q < n; q += 64) rfq[q] = refs[ref_off[pi] + q];
+    __syncthreads();
+    int res[5] = {0, -1, -1, -1, m - 1};
+    if (m > 0 && n > 0) {
+      const smr::SwRes fw = smr::sw_wave_any_t<false>(rdq, m, 0, 1, rfq, n, 0, 1, bound, match, mismatch, scoreN, go, ge, 2);
+      __syncthreads();
+      res[0] = fw.score > 65535 ? 65535 : fw.score; res[2] = fw.end_ref; res[4] = ssw_end_read(fw);
+      if ((uint32_t)res[0] >= filters && fw.score > 0) {
+        const smr::SwRes bw = smr::sw_wave_any_t<false>(rdq, fw.end_read + 1, fw.end_read, -1, rfq, fw.end_ref + 1, fw.end_ref, -1, bound, match, mismatch, scoreN, go, ge, 2);
         __syncthreads();
         res[1] = fw.end_ref - bw.end_ref; res[3] = fw.end_read - bw.end_read;
       }
@@ -141,7 +176,7 @@ __global__ void __launch_bounds__(64) k_ssw_batch_x4(uint32_t n_pairs, const uin
     const bool hn = __any(hasn);
     int res[5] = {0, -1, -1, -1, m - 1};
     const smr::SwRes fw = smr::sw_wave_x4(rdq, m, 0, 1, rfq, n, 0, 1, match, mismatch, scoreN, go, ge, mm, hn);
-    res[0] = fw.score > 65535 ? 65535 : fw.score; res[2] = fw.end_ref; res[4] = fw.end_read;
+    res[0] = fw.score > 65535 ? 65535 : fw.score; res[2] = fw.end_ref; res[4] = m > 0 ? ssw_end_read(fw) : -1;
     const bool rev = m > 0 && (uint32_t)res[0] >= filters && fw.score > 0;
     const smr::SwRes bw = smr::sw_wave_x4(rdq, rev ? fw.end_read + 1 : 0, fw.end_read, -1, rfq, rev ? fw.end_ref + 1 : 0, fw.end_ref, -1, match, mismatch, scoreN, go, ge, mm, hn);
     if (rev) { res[1] = fw.end_ref - bw.end_ref; res[3] = fw.end_read - bw.end_read; }
@@ -151,7 +186,7 @@ __global__ void __launch_bounds__(64) k_ssw_batch_x4(uint32_t n_pairs, const uin
 
 extern "C" int smr_ssw_batch(smr_ctx* c, uint32_t n_pairs, const uint8_t* reads, const uint64_t* read_off, const uint8_t* refs, const uint64_t* ref_off,
                              int match, int mismatch, int score_N, int gap_open, int gap_ext, uint32_t filters, int mode, int32_t* out) {
-  if (!c || !read_off || !ref_off || !out || mode < 0 || mode > 4) return SMR_ERR_ARG;
+  if (!c || !read_off || !ref_off || !out || mode < 0 || mode > 5) return SMR_ERR_ARG;
   // (modes 0 - 3 are the fast kernels: only under the schemes whose answers they share with ssw.c; mode 4 = the striped slow path, any scheme)
   if (mode != 4) if (const char* why = scheme_unsupported(mismatch, score_N, gap_open, gap_ext)) { set_err(c, why); return SMR_ERR_ARG; }
   if (n_pairs == 0) return SMR_OK;
@@ -183,13 +218,143 @@ extern "C" int smr_ssw_batch(smr_ctx* c, uint32_t n_pairs, const uint8_t* reads,
     const uint32_t gb = std::min<uint32_t>(n_pairs, (uint32_t)c->n_cu * 8u), stride = 5u * 16u * ((uint32_t)(mx_m + 7) / 8u + 1u);
     uint16_t* d_scr = nullptr;
     if (mode == 4) { IB_GET(d_scr_, uint16_t, (size_t)gb * stride); d_scr = d_scr_; }
-    if (mode == 4) hipLaunchKernelGGL(k_ssw_batch<true>, dim3(gb), dim3(64), lds, c->stream, n_pairs, (const uint8_t*)d_reads,
+    if (mode == 5) hipLaunchKernelGGL(k_ssw_long, dim3(gb), dim3(64), lds, c->stream, n_pairs, (const uint8_t*)d_reads,
+                       (const unsigned long long*)d_ro, (const uint8_t*)d_refs, (const unsigned long long*)d_fo, lm, ln, match, mismatch, score_N, gap_open, gap_ext, filters, d_out);
+    else if (mode == 4) hipLaunchKernelGGL(k_ssw_batch<true>, dim3(gb), dim3(64), lds, c->stream, n_pairs, (const uint8_t*)d_reads,
                        (const unsigned long long*)d_ro, (const uint8_t*)d_refs, (const unsigned long long*)d_fo, lm, ln, match, mismatch, score_N, gap_open, gap_ext, filters, -1, d_out, d_scr, stride);
     else hipLaunchKernelGGL(k_ssw_batch<false>, dim3(gb), dim3(64), lds, c->stream, n_pairs, (const uint8_t*)d_reads,
                        (const unsigned long long*)d_ro, (const uint8_t*)d_refs, (const unsigned long long*)d_fo, lm, ln, match, mismatch, score_N, gap_open, gap_ext, filters, mode, d_out, d_scr, stride);
   }
   HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)n_pairs * 5 * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SMR_OK;
+}
+
+extern "C" int smr_sw_long_rows(int m) { return smr::sw_long_rows(m); }
+
+// =================================================================================================
+// k_sw16 at the same seam: the kernel as the candidate walk launches it (smr_walk.hpp) -- packed records of the selected batch, WTasks, the two
+// index lists and the counters as k_walk leaves them -- and, for the tasks scored with end cells, the begin-cell tasks as k_begins_prep makes them.
+// =================================================================================================
+namespace {
+int sw16_launch(smr_ctx* c, int rows, uint32_t blocks, const DReads& rd, const DIndex& ix, const DParams& P, const WTask* tk, const uint32_t* t1, const uint32_t* t2,
+                const unsigned long long* wc, uint2* res) {
+  const uint32_t gb = blocks ? blocks : (uint32_t)c->n_cu * 4u * (uint32_t)SW16_WAVES(rows);
+#define SW16_ARGS rd, ix, P, tk, t1, t2, wc, res
+  if (rows == 13) hipLaunchKernelGGL(k_sw16<13>, dim3(gb), dim3(64), 0, c->stream, SW16_ARGS);
+  else if (rows == 19) hipLaunchKernelGGL(k_sw16<19>, dim3(gb), dim3(64), 0, c->stream, SW16_ARGS);
+  else if (rows == 26) hipLaunchKernelGGL(k_sw16<26>, dim3(gb), dim3(64), 0, c->stream, SW16_ARGS);
+  else hipLaunchKernelGGL(k_sw16<32>, dim3(gb), dim3(64), 0, c->stream, SW16_ARGS);
+#undef SW16_ARGS
+  HIPCHK(c, hipGetLastError());
+  return SMR_OK;
+}
+}  // namespace
+
+extern "C" int smr_sw16_batch(smr_ctx* c, uint32_t n_tasks, const smr_sw16_task* tasks, const uint8_t* ref, uint64_t ref_len, int force_any_n,
+                              int match, int mismatch, int score_N, int gap_open, int gap_ext, uint32_t filters, int rows, uint32_t blocks, int32_t* out) {
+  if (!c || (n_tasks && (!tasks || !out)) || (ref_len && !ref)) return SMR_ERR_ARG;
+  if (rows != 13 && rows != 19 && rows != 26 && rows != 32) { set_err(c, "smr_sw16_batch: rows must be 13, 19, 26 or 32"); return SMR_ERR_ARG; }
+  if (blocks > 65536u) { set_err(c, "smr_sw16_batch: at most 65536 blocks"); return SMR_ERR_ARG; }
+  if (match <= 0 || match > 127 || mismatch > 0 || mismatch < -127 || score_N < -127 || gap_open < 0 || gap_open > 255 || gap_ext < 0 || gap_ext > 255) { set_err(c, "smr_sw16_batch: bad scoring options"); return SMR_ERR_ARG; }
+  if (const char* why = scheme_unsupported(mismatch, score_N, gap_open, gap_ext)) { set_err(c, why); return SMR_ERR_ARG; }
+  if (!c->b->used || !c->b->d_words) { set_err(c, "smr_sw16_batch: no reads uploaded into the selected batch"); return SMR_ERR_STATE; }
+  (void)hipSetDevice(c->device);
+  const uint32_t n_reads = c->b->n;
+  std::vector<uint32_t> len(n_reads);
+  if (n_reads) HIPCHK(c, hipMemcpyAsync(len.data(), c->b->d_len, (size_t)n_reads * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<WTask> tk(std::max<uint32_t>(n_tasks, 1));
+  std::vector<uint32_t> ia, ib;
+  for (uint32_t i = 0; i < n_tasks; i++) {
+    const smr_sw16_task& t = tasks[i];
+    const char* why = nullptr;
+    if (t.read >= n_reads) why = "read index outside the batch";
+    else if (t.m == 0 || t.nref == 0) why = "empty span or window";
+    else if (t.m > WK_MAX_ROWS || (int)t.m > 8 * rows) why = "span longer than the kernel takes (8 x rows, at most WK_MAX_ROWS)";
+    else if ((uint64_t)t.aq + t.m > len[t.read]) why = "rows outside the read";
+    else if ((uint64_t)t.win_off + t.nref > ref_len) why = "window outside the reference letters";
+    else if (!sw_pk_fits((int)t.m, (int)t.nref, match, mismatch, score_N, gap_open)) why = "numbers outside the packed representation (sw_pk_fits)";
+    else if (t.reversed > 1 || t.list_b > 1) why = "reversed / list_b must be 0 or 1";
+    if (why) { set_err(c, std::string("smr_sw16_batch: task ") + std::to_string(i) + ": " + why); return SMR_ERR_ARG; }
+    WTask o;
+    memset(&o, 0, sizeof o);
+    o.r = t.read; o.max_ref = 0; o.rf_start = t.win_off; o.ars = 0; o.head = 0; o.aq = t.aq; o.m = t.m; o.nref = t.nref; o.flags = t.reversed ? 1 : 0;
+    tk[i] = o;
+    (t.list_b ? ib : ia).push_back(i);
+  }
+  if (n_tasks == 0) return SMR_OK;
+  DevPool pool;
+  IB_GET(d_ref, uint8_t, ref_len + 8); IB_GET(d_tk, WTask, n_tasks); IB_GET(d_ia, uint32_t, n_tasks); IB_GET(d_ib, uint32_t, n_tasks);
+  IB_GET(d_wc, unsigned long long, WC_STRIDE); IB_GET(d_res, uint2, n_tasks);
+  HIPCHK(c, hipMemsetAsync(d_ref, 0, ref_len + 8, c->stream));
+  if (ref_len) HIPCHK(c, hipMemcpyAsync(d_ref, ref, ref_len, hipMemcpyHostToDevice, c->stream));
+  DIndex ix;
+  memset(&ix, 0, sizeof ix);
+  ix.ref_seq = d_ref;
+  ix.ref_any_n = (force_any_n || (ref_len && memchr(ref, 4, ref_len))) ? 1u : 0u;          // (as smr_index_upload sets it for an index part)
+  DParams P;
+  memset(&P, 0, sizeof P);
+  P.match = match; P.mismatch = mismatch; P.score_N = score_N; P.gap_open = gap_open; P.gap_ext = gap_ext; P.sw_mode = c->sw_mode;
+  unsigned long long wc[WC_STRIDE] = {};
+  std::vector<uint2> res(n_tasks);
+  // forward: list A with end cells, list B score only
+  wc[WC_NTASK] = ia.size(); wc[WC_NTASK2] = ib.size();
+  HIPCHK(c, hipMemcpyAsync(d_tk, tk.data(), (size_t)n_tasks * sizeof(WTask), hipMemcpyHostToDevice, c->stream));
+  if (!ia.empty()) HIPCHK(c, hipMemcpyAsync(d_ia, ia.data(), ia.size() * 4, hipMemcpyHostToDevice, c->stream));
+  if (!ib.empty()) HIPCHK(c, hipMemcpyAsync(d_ib, ib.data(), ib.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_wc, wc, sizeof wc, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(d_res, 0xEE, (size_t)n_tasks * sizeof(uint2), c->stream));
+  { int rc = sw16_launch(c, rows, blocks, dreads(c), ix, P, d_tk, d_ia, d_ib, d_wc, d_res); if (rc) return rc; }
+  HIPCHK(c, hipMemcpyAsync(res.data(), d_res, (size_t)n_tasks * sizeof(uint2), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // begin cells (k_begins_prep, stage 1): rows back from the end row, columns back from the end column, all in the list with end cells
+  std::vector<uint32_t> beg;
+  std::vector<WTask> tb(tk);
+  for (uint32_t i = 0; i < n_tasks; i++) {
+    int32_t* o = out + (size_t)i * 5;
+    const int score = res[i].x > 65535u ? 65535 : (int)res[i].x;
+    o[0] = score; o[1] = o[2] = o[3] = o[4] = -1;
+    if (tasks[i].list_b) {
+      if (res[i].y != 0xFFFFFFFFu) { set_err(c, "smr_sw16_batch: a score-only task came back with an end cell"); return SMR_ERR_DEVICE; }
+      continue;
+    }
+    if (res[i].y == 0xFFFFFFFFu || res[i].y == 0xEEEEEEEEu) { set_err(c, "smr_sw16_batch: a task of the end-cell list came back without one"); return SMR_ERR_DEVICE; }
+    const int end_ref = (int)(res[i].y >> 16) - 1, end_read = (int)(res[i].y & 0xFFFFu);
+    o[2] = end_ref; o[4] = score > 0 ? end_read : 0;          // (no positive cell: ssw_align's read_end1 is 0, see ssw_end_read above)
+    // (the second launch reads the read and the window back from this cell: a cell outside the task would send it outside the buffers)
+    if (end_ref < -1 || end_ref >= (int)tk[i].nref || end_read >= (int)tk[i].m || (score > 0 && end_ref < 0)) {
+      set_err(c, "smr_sw16_batch: task " + std::to_string(i) + " came back with an end cell outside its span and window"); return SMR_ERR_DEVICE;
+    }
+    if ((uint32_t)score >= filters && score > 0) {
+      WTask& b = tb[i];
+      b.m = (uint16_t)(end_read + 1); b.nref = (uint16_t)(end_ref + 1);
+      b.aq = (uint16_t)(tk[i].aq + end_read); b.rf_start = tk[i].rf_start + (uint64_t)end_ref; b.flags = (uint16_t)(tk[i].flags | 2u);
+      beg.push_back(i);
+    }
+  }
+  if (beg.empty()) return SMR_OK;
+  memset(wc, 0, sizeof wc);
+  wc[WC_NTASK] = beg.size();
+  HIPCHK(c, hipMemcpyAsync(d_tk, tb.data(), (size_t)n_tasks * sizeof(WTask), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_ia, beg.data(), beg.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_wc, wc, sizeof wc, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(d_res, 0xEE, (size_t)n_tasks * sizeof(uint2), c->stream));
+  { int rc = sw16_launch(c, rows, blocks, dreads(c), ix, P, d_tk, d_ia, d_ib, d_wc, d_res); if (rc) return rc; }
+  HIPCHK(c, hipMemcpyAsync(res.data(), d_res, (size_t)n_tasks * sizeof(uint2), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (uint32_t i : beg) {
+    int32_t* o = out + (size_t)i * 5;
+    if (res[i].y == 0xFFFFFFFFu || res[i].y == 0xEEEEEEEEu) { set_err(c, "smr_sw16_batch: a begin-cell task came back without a cell"); return SMR_ERR_DEVICE; }
+    const int b_ref = (int)(res[i].y >> 16) - 1, b_read = (int)(res[i].y & 0xFFFFu);
+    o[1] = o[2] - b_ref; o[3] = o[4] - b_read;
+  }
+  return SMR_OK;
+}
+
+extern "C" int smr_sw16_launches(const smr_ctx* c, uint64_t out[8]) {
+  if (!c || !out) return SMR_ERR_ARG;
+  for (int k = 0; k < 8; k++) out[k] = c->sw16_launches[k];
   return SMR_OK;
 }
 

@@ -287,7 +287,7 @@ class Engine:
 
     def ssw_batch(self, reads, refs, match=2, mismatch=-3, score_N=-3, gap_open=5, gap_ext=2, filters=0, mode=1):
         """reads / refs: lists of byte strings in the 0..4 alphabet; -> int32 array (n, 5): score1, ref_begin1, ref_end1, read_begin1, read_end1
-        (ssw_align with flag 2, without the CIGAR), computed by the 32-bit (mode 0) or the packed (mode 1) SW kernel"""
+        (ssw_align with flag 2, without the CIGAR), computed by the 32-bit (mode 0) or the packed (mode 1) SW kernel; mode 5: through the long-read strips"""
         import numpy as np
         n = len(reads)
         ro = np.zeros(n + 1, dtype=np.uint64); fo = np.zeros(n + 1, dtype=np.uint64)
@@ -297,6 +297,33 @@ class Engine:
         self._chk(self.L.smr_ssw_batch(self.h, n, rb.ctypes.data, ro.ctypes.data, fb.ctypes.data, fo.ctypes.data, match, mismatch, score_N,
                                        gap_open, gap_ext, filters, mode, out.ctypes.data), "smr_ssw_batch")
         return out
+
+    # one task of sw16_batch: smr_sw16_task of include/smr_hip.h
+    SW16_TASK = np.dtype([("read", "<u4"), ("win_off", "<u4"), ("aq", "<u2"), ("m", "<u2"), ("nref", "<u2"), ("reversed", "u1"), ("list_b", "u1")])
+
+    def sw16_batch(self, tasks, ref, rows, match=2, mismatch=-3, score_N=-3, gap_open=5, gap_ext=2, filters=0, blocks=0, force_any_n=False):
+        """k_sw16<rows> over the reads of the selected batch (upload_reads) as the candidate walk launches it (smr_sw16_batch).  tasks: tuples
+        (read, aq, m, reversed, win_off, nref, list_b); ref: bytes in the 0..4 alphabet that stand in for an index part's reference letters;
+        -> int32 array (n, 5): score1, ref_begin1, ref_end1, read_begin1, read_end1 of the span against the window (list_b: the score, then -1)"""
+        n = len(tasks)
+        t = np.zeros(max(n, 1), dtype=self.SW16_TASK)
+        for i, (r, aq, m, rev, wo, nref, lb) in enumerate(tasks):
+            t[i] = (r, wo, aq, m, nref, rev, lb)
+        rf = np.frombuffer(bytes(ref) + b"\0", dtype=np.uint8).copy()
+        out = np.zeros((max(n, 1), 5), dtype=np.int32)
+        self._chk(self.L.smr_sw16_batch(self.h, n, t.ctypes.data, rf.ctypes.data, len(ref), int(bool(force_any_n)), match, mismatch, score_N, gap_open, gap_ext,
+                                        filters, rows, blocks, out.ctypes.data), "smr_sw16_batch")
+        return out[:n]
+
+    def sw16_launches(self):
+        """launches of k_sw16<13 | 19 | 26 | 32> since the engine was created: ({rows: by the walk rounds}, {rows: by the begin-cell stage})"""
+        out = (C.c_uint64 * 8)()
+        self._chk(self.L.smr_sw16_launches(self.h, out), "smr_sw16_launches")
+        return dict(zip((13, 19, 26, 32), out[:4])), dict(zip((13, 19, 26, 32), out[4:]))
+
+    def sw_long_rows(self, m):
+        """the strip height (8, 10 ... 24) the long-read Smith-Waterman scores a span of m rows with (smr_sw_long_rows)"""
+        return self.L.smr_sw_long_rows(int(m))
 
     def cigar_batch(self, reads, refs, scores, match=2, mismatch=-3, score_N=-3, gap_open=5, gap_ext=2):
         """reads / refs: the aligned spans (byte strings in the 0..4 alphabet), scores: their score1; -> list of u32 CIGAR arrays (len << 4 | op),

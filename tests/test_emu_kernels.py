@@ -21,6 +21,7 @@ from test_gpu_parity import (test_seed_scan_matches_oracle, test_multi_part_inde
                              test_a_window_with_hundreds_of_hits, test_rounds_adapt_from_part_to_part_without_changing_a_record,
                              test_edges_outside_what_the_reference_defines_are_refused)
 from test_gpu_parity import test_align_records_match_oracle as _align_body
+from test_gpu_parity import test_read_lengths_at_the_boundaries_of_the_sixteen_task_kernel as _sw16_boundary_body
 from test_gpu_golden import test_gpu_records_equal_reference_records as _golden_body
 
 FULL = os.environ.get("SMR_EMU_FULL", "0") == "1"
@@ -34,6 +35,12 @@ from test_gpu_parity import (test_skewed_batch_sorted_by_several_blocks_and_sear
                          ids=lambda v: ",".join("%s=%s" % (k.replace("SMR_SEED_", ""), x) for k, x in v.items()) if isinstance(v, dict) else ("dfs" if v else "pg"))
 def test_skewed_batch_sorted_by_several_blocks_and_searched_once_per_seed(tmp_path, monkeypatch, env, mode):
     _skew_body(tmp_path, monkeypatch, env, mode)
+
+
+# (the host's choice of k_sw16<13 | 19 | 26 | 32> at its boundaries: one length per instantiation by default, both sides of every boundary with SMR_EMU_FULL=1)
+@pytest.mark.parametrize("max_len", [104, 105, 152, 153, 208, 209, 256] if FULL else [104, 105, 208, 209])
+def test_read_lengths_at_the_boundaries_of_the_sixteen_task_kernel(engine, tmp_path, max_len):
+    _sw16_boundary_body(engine, tmp_path, max_len)
 
 
 @pytest.mark.parametrize("mode", ["1", "0"] if FULL else ["1"], ids=lambda m: "shared" if m == "1" else "per-part")

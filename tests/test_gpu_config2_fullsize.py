@@ -66,6 +66,7 @@ def test_config2_fullsize_records_equal_the_reference(setup, run, seed_mode):
     e.set_seed_mode(0)
     assert ctr["num_aligned"] == r["num_aligned"] and sum(1 for x in recs if x) == r["n_records"]
     tot, chunks = digests(recs, g["chunk"])
+    assert len(chunks) == len(r["md5_chunks"]), "%d chunks of records against %d stored ones" % (len(chunks), len(r["md5_chunks"]))
     bad = [k for k, (a, b) in enumerate(zip(chunks, r["md5_chunks"])) if a != b]
     assert not bad, "%d of %d chunks of %d reads differ from the reference's records; first: reads %d.." % (len(bad), len(chunks), g["chunk"], bad[0] * g["chunk"])
     assert tot == r["md5_total"]
@@ -104,6 +105,7 @@ def test_config2_read_set_twelve_times_over_at_the_shipped_thresholds(setup):
     assert e.counters(1)["num_aligned"] == copies * r["num_aligned"]
     for k in range(copies):
         tot, chunks = digests(recs[k * g["n_reads"]:(k + 1) * g["n_reads"]], g["chunk"])
+        assert len(chunks) == len(r["md5_chunks"]), "copy %d of the read set: %d chunks of records against %d stored ones" % (k, len(chunks), len(r["md5_chunks"]))
         assert tot == r["md5_total"], "copy %d of the read set: chunks %s differ" % (k, [i for i, (a, b) in enumerate(zip(chunks, r["md5_chunks"])) if a != b][:5])
     # the sorted tuples of one seed stage at this size: most are repeats (k_seed_dedup ran at its shipped threshold)
     e.upload_reads(big, 1)

@@ -24,6 +24,7 @@ def test_gpu_records_equal_reference_records(engine, case, tmp_path):
     g = golden.load()[case]
     o = gpu_run(engine, case, tmp_path)
     exp = golden.records(case)
+    assert len(o["records"]) == len(exp), "%d records against %d stored ones" % (len(o["records"]), len(exp))
     bad = [i for i, (a, b) in enumerate(zip(o["records"], exp)) if a != b]
     assert not bad, "%s: %d records differ, first %d\n gpu=%s\n ref=%s" % (
         case, len(bad), bad[0], refrun.parse_record(o["records"][bad[0]]), refrun.parse_record(exp[bad[0]]))

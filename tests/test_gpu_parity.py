@@ -29,6 +29,7 @@ def wl(tmp_path_factory):
 
 
 def _compare(recs_gpu, recs_orc, what):
+    assert len(recs_gpu) == len(recs_orc), "%s: %d records against the oracle's %d" % (what, len(recs_gpu), len(recs_orc))
     bad = [i for i, (a, b) in enumerate(zip(recs_gpu, recs_orc)) if a != b]
     msg = ""
     if bad:
@@ -167,6 +168,27 @@ def test_mixed_read_lengths(engine, tmp_path):
     assert ctr_g["num_aligned"] == ctr_o["num_aligned"] > 300
     lens = [len(s) for s, r in zip(w.seqs, recs_o) if r]
     assert min(lens) < 200 and max(lens) > 300
+
+
+@pytest.mark.parametrize("max_len", [104, 105, 152, 153, 208, 209, 256])
+def test_read_lengths_at_the_boundaries_of_the_sixteen_task_kernel(engine, tmp_path, max_len):
+    """the host picks k_sw16<13 | 19 | 26 | 32> from the batch's longest read (<= 104 / 152 / 208 / 256 letters): batches cut to each boundary and to one
+    letter more give the oracle's records, through the walk path and through the instantiation the length calls for (smr_sw16_launches)"""
+    w = Workload(str(tmp_path), db_nt=200_000, n_reads=1200, read_len=260, seed=97, frac_db=0.5)
+    rng = np.random.Generator(np.random.PCG64(max_len))
+    w.seqs = [s[:max_len] if k % 3 else s[: int(rng.integers(40, max_len + 1))] for k, s in enumerate(w.seqs)]
+    w.reads = smr.Reads.from_seqs(w.seqs)
+    assert w.reads.max_len == max_len
+    w.minimal_score = smr.minimal_score(0.618874, 0.343238, w.parts[0].info(), len(w.seqs), sum(map(len, w.seqs)))
+    walk0, begins0 = engine.sw16_launches()
+    recs_o, ctr_o = w.oracle_records()
+    recs_g, ctr_g = w.gpu_records(engine)
+    _compare(recs_g, recs_o, "reads of at most %d letters" % max_len)
+    assert ctr_g["num_aligned"] == ctr_o["num_aligned"] > 200
+    walk1, begins1 = engine.sw16_launches()
+    rows = 13 if max_len <= 104 else 19 if max_len <= 152 else 26 if max_len <= 208 else 32
+    assert walk1[rows] > walk0[rows] and begins1[rows] > begins0[rows], (rows, walk0, walk1, begins0, begins1)
+    assert all(walk1[r] == walk0[r] and begins1[r] == begins0[r] for r in (13, 19, 26, 32) if r != rows), (rows, walk0, walk1, begins0, begins1)
 
 
 @pytest.mark.parametrize("lnwin", [10, 12, 14, 16])

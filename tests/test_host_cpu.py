@@ -295,3 +295,21 @@ def test_flat_index_cache_round_trip(tmp_path):
         smr.Index.load_flat(str(tmp_path / "absent.flat"), stamp=77)
     for ix in parts + flats:
         ix.free()
+
+
+@pytest.mark.parametrize("fixture", ["ssw_pairs.json", "sw16_pairs.json"])
+def test_plain_dp_returns_the_five_numbers_of_ssw_c_on_every_stored_pair(fixture):
+    """helpers/swdp.py (the textbook affine recurrence in 64-bit integers; end cell = earliest column that reaches the maximum, smallest row in it;
+    begin cell by the same recurrence over the reversed prefixes) against the stored answers of the reference's own ssw.c: every pair of both
+    files, every scheme in them -- the claim of smr_engine.hip's scheme_unsupported (the fast kernels' recurrence gives ssw.c's answers under every
+    scheme they accept) as a test, and the licence to compare the kernels with this DP where no stored answer exists.
+    Finding kept as stored pairs: a pair without any positive cell has read_end1 = 0 in ssw.c (its scan for the end row meets a column of zeros)."""
+    from helpers import sswgold, swdp
+    n = 0
+    for c in sswgold.load(fixture):
+        sc = c["scoring"]
+        for r, f, e in zip(c["reads_b"], c["refs_b"], c["expected"]):
+            got = swdp.align(r, f, sc["match"], sc["mismatch"], sc["score_N"], sc["gap_open"], sc["gap_ext"], sc["filters"])
+            assert got == e, "scoring %s, m=%d, n=%d: DP %s, ssw.c %s" % (sc, len(r), len(f), got, e)
+            n += 1
+    assert n == {"ssw_pairs.json": 320, "sw16_pairs.json": 324}[fixture]

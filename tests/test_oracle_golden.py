@@ -22,6 +22,7 @@ def test_oracle_records_equal_reference_records(case, tmp_path):
     o = oracle_run(case, tmp_path)
     assert max(o["nparts"]) == g["index_parts"]
     exp = golden.records(case)
+    assert len(o["records"]) == len(exp), "%d records against %d stored ones" % (len(o["records"]), len(exp))
     bad = [i for i, (a, b) in enumerate(zip(o["records"], exp)) if a != b]
     assert not bad, "%s: %d records differ, first %d\n orc=%s\n ref=%s" % (
         case, len(bad), bad[0], refrun.parse_record(o["records"][bad[0]]), refrun.parse_record(exp[bad[0]]))
