@@ -29,7 +29,11 @@
  *   resident batches      16 per context (smr_batch_select), resident index parts 64 per context (smr_index_upload slot 0..63)
  *   seed length           8..20, even; < 2^31 - 1 distinct seeds (ids) per index part
  *   seed hits             no limit: the lane-local hit lists grow to what a half-seed search can accept at most (31 L/2 - 20 strings, smr_prof.hit_list_cap)
- *   candidate references  <= 49 152 references sharing seeds with ONE read on one strand (the per-block global table of k_chain<EXT>)
+ *   candidate references  <= 49 152 references that occur at least twice among the seed positions of ONE read on one strand (3/4 of the 65 536 slots of
+ *                         the per-block global table of k_chain<EXT>; the 49 153rd is SMR_ERR_CAPACITY, the context stays usable: tests/test_gpu_cand_limits.py);
+ *                         (a lower bound of what counts: a reference that occurs once is a member too when its bit of the set's Bloom filter collides,
+ *                         which is why the error message speaks of references that "share seeds with one read");
+ *                         up to 384 of them stay in the LDS table of a wave, the first read with more switches the context to the global tables (one retry)
  *   alignments per read   max_alignments_per_read given to smr_reads_upload (the reference's -num_alignments, or 256 for "all")
  *   scoring               match <= 127, |mismatch|, |score_N| <= 127, gaps <= 255.  With 2 * gap_open, 2 * gap_ext >= |mismatch|, gap_open > gap_ext and score_N <= 0 the
  *                         affine recurrence of the fast kernels equals the reference's striped kernels cell for cell; outside those conditions ssw.c's scores
@@ -208,6 +212,19 @@ int smr_seed_tuples_fetch(smr_ctx*, uint64_t* tuples, uint64_t cap_tuples, uint3
 /* Test seam of the seed-hit pool (SMR_SEED_POOL_WORDS=<n> starts it at n words, clamped to [64, 0x7FFFFFF0]): info = {pool words, regrows
  * since smr_create, one past the highest pool word the selected batch's last seed stage handed out, 1 if that stage inlined one-hit windows}. */
 int smr_seed_pool_info(smr_ctx*, uint64_t info[4]);
+/* Test seam of the candidate stage (tests/test_gpu_cand_limits.py).  smr_cand_info: info = {attempts of the last smr_align_part, how many of them
+ * were redone because of HITCAP, POOL, PAIRS, REDO, SCAP (five words), then chain_ext, chain_scap, keys_cap, pairs_cap, hits_cap of the context as
+ * they stand, 1 if the route bytes are switched on, the number of reads they cover}.  After smr_cand_info_enable(ctx, 1) every smr_align_part also
+ * keeps one byte per read, OR-ed over the (strand, pass) launches of its final attempt, which smr_cand_routes copies out (n = reads of the batch):
+ * SMR_ROUTE_RECORD / SMR_ROUTE_GATHER = listed for the walk rounds with / without a record of k_cand, SMR_ROUTE_CHAIN = walked by k_chain on its
+ * wave's LDS table, SMR_ROUTE_EXT = by its second launch on the block's global table.  Switched off (the default) no kernel is launched for it. */
+#define SMR_ROUTE_RECORD 1u
+#define SMR_ROUTE_GATHER 2u
+#define SMR_ROUTE_CHAIN 4u
+#define SMR_ROUTE_EXT 8u
+int smr_cand_info_enable(smr_ctx*, int on);
+int smr_cand_info(smr_ctx*, uint64_t info[13]);
+int smr_cand_routes(smr_ctx*, uint8_t* out, uint32_t n);
 int smr_index_unload(smr_ctx*, int slot);
 
 /* Several read batches (0..15) can be resident at once, so the host can upload batch k+1 while batch k is being

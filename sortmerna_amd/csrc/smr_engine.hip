@@ -153,6 +153,10 @@ struct smr_ctx {
   double kp_ms[KP_COUNT] = {}; uint64_t kp_l[KP_COUNT] = {};       // HIP-event time and launches per kernel family (smr_prof_kernels)
   hipStream_t upload_stream = nullptr;     // smr_reads_upload_batch: H2D of batch k+1 while batch k is aligned on `stream`
   unsigned long long* d_ctr_snap = nullptr; // counters of the selected batch at the start of smr_align_part (restored when an attempt is redone)
+  // smr_cand_info (a test seam): what the retry ladder of the last smr_align_part did, and -- once switched on by smr_cand_info_enable -- one byte per
+  // read that says which way it went through the candidate stage in the launches of the final attempt (k_cand_route; no other kernel knows of it)
+  bool cinfo_on = false; uint8_t* d_croute = nullptr; size_t croute_cap = 0; uint32_t croute_n = 0;
+  uint32_t cinfo_attempts = 0, cinfo_retry[5] = {0, 0, 0, 0, 0};       // attempts; redone because of HITCAP, POOL, PAIRS, REDO, SCAP
 };
 struct KpSave { double ms[KP_COUNT]; uint64_t l[KP_COUNT]; };
 
@@ -365,7 +369,7 @@ extern "C" void smr_destroy(smr_ctx* c) {
   dev_free(&c->d_bound); dev_free(&c->d_rdq); dev_free(&c->d_mrec); dev_free(&c->d_mpool);
   for (int q = 0; q < 2; q++) { dev_free(&c->d_wlist[q]); dev_free(&c->d_wstate[q]); dev_free(&c->d_wtask[q]); dev_free(&c->d_wres[q]); }
   dev_free(&c->d_wstat);
-  dev_free(&c->d_wtidx); dev_free(&c->d_wslow); dev_free(&c->d_wctr);
+  dev_free(&c->d_wtidx); dev_free(&c->d_wslow); dev_free(&c->d_wctr); dev_free(&c->d_croute);
   dev_free(&c->sb.chist); dev_free(&c->sb.cbase); dev_free(&c->sb.rows); dev_free(&c->sb.bcnt); dev_free(&c->sb.tmp); dev_free(&c->sb.mid);
   dev_free(&c->sb.srt); dev_free(&c->sb.hpre); dev_free(&c->sb.hlist); dev_free(&c->sb.hh); dev_free(&c->sb.pieces); dev_free(&c->sb.redo); dev_free(&c->sb.sn); dev_free(&c->sb.wbin); dev_free(&c->sb.emap); dev_free(&c->sb.zbits); dev_free(&c->sb.gflag);
   for (int d = 0; d < 2; d++) { dev_free(&c->sb.wseg[d]); dev_free(&c->sb.fbits[d]); }
@@ -705,8 +709,16 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
   const uint32_t tb = 256, nb = (c->b->n + tb - 1) / tb;
   const int single = (p->is_forward != 0) ^ (p->is_reverse != 0);
   const int num_strands = single ? 1 : 2;
+  c->cinfo_attempts = 0;
+  for (int q = 0; q < 5; q++) c->cinfo_retry[q] = 0;
   for (int attempt = 0; attempt < 16; attempt++) {            // (the hit-list ladder of the DFS kernel alone has seven steps: grow_hcap)
     if ((rc = ensure_chain_scratch(c, di))) return rc;
+    c->cinfo_attempts++;
+    if (c->cinfo_on) {                                        // the route bytes start over with every attempt: they describe the one that is kept
+      if (c->croute_cap < c->b->n) { if ((rc = dev_alloc(c, &c->d_croute, (size_t)c->b->n))) return rc; c->croute_cap = c->b->n; }
+      HIPCHK(c, hipMemsetAsync(c->d_croute, 0, (size_t)c->b->n, c->stream));
+      c->croute_n = c->b->n;
+    }
     const KpSave kp0 = kp_save(c);
     c->wstat_n = 0;
     // restore counters (retry) and clear the per-part ones (processor.cpp:230 resets num_short per part)
@@ -725,14 +737,15 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
     if ((rc = read_ctr(c, h))) return rc;
     ev_collect(c);
     bool retry = false;
-    if (h[C_ERR_HITCAP]) { if (!grow_hcap(c, P.partialwin)) return SMR_ERR_CAPACITY; retry = true; }
-    if (h[C_ERR_POOL]) { if ((rc = grow_pool(c))) return rc; retry = true; }
+    if (h[C_ERR_HITCAP]) { c->cinfo_retry[0]++; if (!grow_hcap(c, P.partialwin)) return SMR_ERR_CAPACITY; retry = true; }
+    if (h[C_ERR_POOL]) { c->cinfo_retry[1]++; if ((rc = grow_pool(c))) return rc; retry = true; }
     if (h[C_ERR_PAIRS]) {
+      c->cinfo_retry[2]++;
       c->pairs_cap *= 4; c->hits_cap *= 4; dev_free(&c->d_pairs); dev_free(&c->d_lis); dev_free(&c->d_hits); dev_free(&c->d_tuples); dev_free(&c->d_tuples2);
       if (c->pairs_cap > (1u << 22)) { set_err(c, "per-read candidate scratch exceeds capacity"); return SMR_ERR_CAPACITY; }
       retry = true;
     }
-    if (h[C_ERR_REDO]) { c->seed_exact = 1; retry = true; }     // too many overflowing waves for the redo list: use the DFS kernel throughout
+    if (h[C_ERR_REDO]) { c->cinfo_retry[3]++; c->seed_exact = 1; retry = true; }     // too many overflowing waves for the redo list: use the DFS kernel throughout
     {
       // k_seed_pg's candidate pool: when more than 1/64 of this part's waves overflowed it (they were searched again by the DFS kernel:
       // right, but slow), the next launches get twice the pool
@@ -748,7 +761,7 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
       // a read shares seeds with more references than the LDS table of its wave holds (384): from now on such reads build their set in a
       // per-block table in global memory; the candidate keys need room for as many members
       if (c->chain_ext) { set_err(c, "more than 49152 references share seeds with one read (candidate set capacity)"); return SMR_ERR_CAPACITY; }
-      c->chain_ext = true; retry = true;
+      c->chain_ext = true; retry = true; c->cinfo_retry[4]++;
       if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: a read shares seeds with more references than its wave's LDS table holds: per-block global candidate tables enabled (%.1f GB)\n",
                                          (double)c->chain_blocks * (4.0 * CH_EXT_CAP * 4 + (double)c->pairs_cap * 8 + (double)CH_EXT_CAP * 8) / 1e9);
       if (c->keys_cap < CH_EXT_CAP) { dev_free(&c->d_keys); c->keys_cap = 0; c->keys_need = CH_EXT_CAP; }
@@ -1036,6 +1049,34 @@ extern "C" int smr_seed_pool_info(smr_ctx* c, uint64_t info[4]) {
   uint64_t hi = 0;
   for (int s = 0; s < C_NSHARD; s++) if (cur[s * C_PCUR_STRIDE]) hi = std::max<uint64_t>(hi, s * region + cur[s * C_PCUR_STRIDE]);
   info[0] = c->pool_words; info[1] = c->n_pool_grown; info[2] = hi; info[3] = c->pool_inline;
+  return SMR_OK;
+}
+
+// Test seam (tests/test_gpu_cand_limits.py, the candidate stage at its path boundaries).  smr_cand_info_enable switches the per-read route bytes
+// on or off for the calls that follow; the counts of smr_cand_info are kept either way (host integers).
+//   info = {attempts of the last smr_align_part, of which redone because of HITCAP, POOL, PAIRS, REDO, SCAP (five words),
+//           chain_ext, chain_scap, keys_cap, pairs_cap, hits_cap as they stand now, 1 if the route bytes are on, reads the route bytes cover}
+//   smr_cand_routes: the byte of every read, OR-ed over the (strand, pass) launches of the last attempt of the last smr_align_part --
+//           SMR_ROUTE_RECORD | SMR_ROUTE_GATHER (listed for k_walk with / without a record of k_cand), SMR_ROUTE_CHAIN (k_chain<false>), SMR_ROUTE_EXT (k_chain<true>)
+extern "C" int smr_cand_info_enable(smr_ctx* c, int on) {
+  if (!c) return SMR_ERR_ARG;
+  c->cinfo_on = on != 0;
+  if (!c->cinfo_on) c->croute_n = 0;
+  return SMR_OK;
+}
+extern "C" int smr_cand_info(smr_ctx* c, uint64_t info[13]) {
+  if (!c || !info) return SMR_ERR_ARG;
+  info[0] = c->cinfo_attempts;
+  for (int q = 0; q < 5; q++) info[1 + q] = c->cinfo_retry[q];
+  info[6] = c->chain_ext ? 1 : 0; info[7] = c->chain_scap; info[8] = c->keys_cap; info[9] = c->pairs_cap; info[10] = c->hits_cap;
+  info[11] = c->cinfo_on ? 1 : 0; info[12] = c->croute_n;
+  return SMR_OK;
+}
+extern "C" int smr_cand_routes(smr_ctx* c, uint8_t* out, uint32_t n) {
+  if (!c || !out) return SMR_ERR_ARG;
+  if (!c->cinfo_on || !c->d_croute || n != c->croute_n) { set_err(c, "smr_cand_routes: no route bytes for that many reads (smr_cand_info_enable before smr_align_part)"); return SMR_ERR_STATE; }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (n) { HIPCHK(c, hipMemcpyAsync(out, c->d_croute, (size_t)n, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); }
   return SMR_OK;
 }
 

@@ -107,6 +107,7 @@ int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, int pass, int
     // rounds of walk -> Smith-Waterman -> next list (smr_walk.hpp); the last round scores in the walk kernel, so every listed read ends its pass here
     ev_mark(c, KP_WNEXT);
     hipLaunchKernelGGL(k_wlist, dim3((c->b->n + 1023u) / 1024u), dim3(1024), 0, c->stream, dreads(c), c->b->d_marks, (const uint2*)mrec, (uint32_t)WK_MAX_ROWS, c->d_wlist[0], c->d_wslow, c->d_wctr, n_slow, getenv("SMR_WALK_DEBUG") ? n_slow + 8 : (unsigned long long*)nullptr, (P.num_seeds >= 2 && c->walk_gather) ? 1 : 0);
+    if (c->cinfo_on) hipLaunchKernelGGL(k_cand_route, dim3((c->b->n + 255u) / 256u), dim3(256), 0, c->stream, c->b->n, (const uint8_t*)c->b->d_marks, (const uint2*)mrec, (const uint2*)c->d_wlist[0], (const unsigned long long*)c->d_wctr, 0, c->d_croute);
     const int swr = wmq <= 104 ? 13 : wmq <= 152 ? 19 : wmq <= 208 ? 26 : 32;
     const uint32_t walk_blocks = (uint32_t)c->n_cu * 4u * SMR_WALK_WAVES_PER_SIMD, sw_blocks = (uint32_t)c->n_cu * 4u * (uint32_t)SW16_WAVES(swr);
     for (uint32_t rnd = 0; rnd < RM; rnd++) {
@@ -151,6 +152,7 @@ int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, int pass, int
 #define CHAIN_ARGS(stab, t2) dreads(c), dindex(di), P, pass, is_last_strand, c->b->d_work, c->b->d_work_aln, c->b->d_rw, c->d_pool, c->b->d_ctr, c->d_tuples, c->d_keys, c->d_pairs, \
                              c->d_lis, c->d_hits, c->keys_cap, c->pairs_cap, c->hits_cap, ml, rf, c->chain_scap, stab, t2, rq, gb, grd, c->b->d_marks, (const uint2*)mrec, (const uint32_t*)c->d_mpool, \
                              (const uint32_t*)(split ? c->d_wslow : nullptr), (const unsigned long long*)n_slow
+  if (c->cinfo_on) hipLaunchKernelGGL(k_cand_route, dim3((c->b->n + 255u) / 256u), dim3(256), 0, c->stream, c->b->n, (const uint8_t*)c->b->d_marks, (const uint2*)nullptr, (const uint2*)nullptr, (const unsigned long long*)nullptr, 1, c->d_croute);
   // (LONG: the batch has reads of more than one Smith-Waterman strip; the short-read instantiation carries none of their state)
   const bool striped = P.sw_mode < 0;                        // (the slow path that reproduces ssw.c's stripe geometry: instantiations of its own)
   if (striped) {
@@ -162,6 +164,7 @@ int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, int pass, int
   if (c->chain_ext) {
     // the reads whose candidate set outgrew the LDS table of the first launch: same walk, set in the block's global table
     HIPCHK(c, hipMemsetAsync(&c->b->d_ctr[C_WORK_NEXT], 0, 8, c->stream));
+    if (c->cinfo_on) hipLaunchKernelGGL(k_cand_route, dim3((c->b->n + 255u) / 256u), dim3(256), 0, c->stream, c->b->n, (const uint8_t*)c->b->d_marks, (const uint2*)nullptr, (const uint2*)nullptr, (const unsigned long long*)nullptr, 2, c->d_croute);
     if (striped) {
       if (gb) hipLaunchKernelGGL((k_chain<true, true, true>), dim3(blocks), dim3(64), lds, c->stream, CHAIN_ARGS(c->d_stab, c->d_tuples2));
       else hipLaunchKernelGGL((k_chain<true, false, true>), dim3(blocks), dim3(64), lds, c->stream, CHAIN_ARGS(c->d_stab, c->d_tuples2));

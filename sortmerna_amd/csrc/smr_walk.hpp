@@ -76,6 +76,18 @@ __global__ void __launch_bounds__(1024) k_wlist(DReads rd, uint8_t* __restrict__
   }
 }
 
+// k_cand_route (a test seam, smr_cand_info; launched only when it is switched on): what the launches around it are about to do with each read, from
+// what they read themselves.  stage 0, after k_wlist: the reads of the round-0 list, with or without a record of k_cand; stage 1, before
+// k_chain<false>: the reads whose mark is 1; stage 2, before k_chain<true>: the reads the first launch left to it (mark 2).
+// (the bits: SMR_ROUTE_* of smr_hip.h)
+__global__ void __launch_bounds__(256) k_cand_route(uint32_t n, const uint8_t* __restrict__ marks, const uint2* __restrict__ mrec, const uint2* __restrict__ list0,
+                                                    const unsigned long long* __restrict__ wc0, int stage, uint8_t* __restrict__ route) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (stage == 0) {
+    if (i < n && i < (uint32_t)wc0[WC_NLIST]) { const uint32_t r = list0[i].x; if (r < n) route[r] |= (uint8_t)(mrec[r].x != NONE ? SMR_ROUTE_RECORD : SMR_ROUTE_GATHER); }
+  } else if (i < n && marks[i] == (stage == 1 ? 1u : 2u)) route[i] |= (uint8_t)(stage == 1 ? SMR_ROUTE_CHAIN : SMR_ROUTE_EXT);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Sixteen Smith-Waterman problems per wave.  A QUAD of lanes is one systolic array of 8 virtual lanes (low halves = virtual lanes 0..3, high
 // halves 4..7) with R consecutive read rows each: n + 7 steps for n columns instead of the n + 31 of the four-problem kernel, and the ~14

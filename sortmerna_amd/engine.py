@@ -231,6 +231,9 @@ def pigeonhole_layout(index):
     return np.ctypeslib.as_array(pg, shape=(npg.value,)), np.ctypeslib.as_array(r3, shape=(nr3.value,))
 
 
+ROUTE_RECORD, ROUTE_GATHER, ROUTE_CHAIN, ROUTE_EXT = 1, 2, 4, 8      # SMR_ROUTE_* of smr_hip.h (Engine.cand_routes)
+
+
 class Engine:
     """One GPU.  Fails loudly when no HIP device / library is available (no CPU fallback)."""
 
@@ -459,6 +462,25 @@ class Engine:
         info = (C.c_uint64 * 4)()
         self._chk(self.L.smr_seed_pool_info(self.h, info), "smr_seed_pool_info")
         return dict(words=info[0], grown=info[1], hi=info[2], inline=bool(info[3]))
+
+    def cand_info_enable(self, on=True):
+        """switch the per-read route bytes of the candidate stage on or off for the align_part calls that follow (smr_cand_info_enable: a test seam)"""
+        self._chk(self.L.smr_cand_info_enable(self.h, int(bool(on))), "smr_cand_info_enable")
+
+    def cand_info(self):
+        """dict of the last align_part's retry ladder and the context's candidate-stage capacities (smr_cand_info: a test seam): attempts,
+        retries = {HITCAP, POOL, PAIRS, REDO, SCAP: attempts redone for that cause}, chain_ext, chain_scap, keys_cap, pairs_cap, hits_cap"""
+        info = (C.c_uint64 * 13)()
+        self._chk(self.L.smr_cand_info(self.h, info), "smr_cand_info")
+        return dict(attempts=info[0], retries=dict(HITCAP=info[1], POOL=info[2], PAIRS=info[3], REDO=info[4], SCAP=info[5]), chain_ext=bool(info[6]),
+                    chain_scap=info[7], keys_cap=info[8], pairs_cap=info[9], hits_cap=info[10], routes_on=bool(info[11]), routes_n=info[12])
+
+    def cand_routes(self):
+        """uint8[n_reads]: per read the ROUTE_* bits OR-ed over the launches of the last align_part's final attempt (smr_cand_routes; needs cand_info_enable)"""
+        n = self.cand_info()["routes_n"]
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        self._chk(self.L.smr_cand_routes(self.h, out.ctypes.data, n), "smr_cand_routes")
+        return out[:n]
 
     def prof_reset(self):
         self._chk(self.L.smr_prof_reset(self.h), "smr_prof_reset")

@@ -144,9 +144,17 @@ def test_reads_sharing_seeds_with_thousands_of_references(engine, tmp_path):
                  db_kw=dict(sub_lo=0.005, sub_hi=0.02))
     assert w.parts[0].info().numseq >= 1400
     recs_o, ctr_o = w.oracle_records()
+    engine.prof_reset()
+    engine.cand_info_enable(True)
     recs_g, ctr_g = w.gpu_records(engine)
+    routes = engine.cand_routes()
+    engine.cand_info_enable(False)
     _compare(recs_g, recs_o, "1500-member family")
     assert ctr_g["num_aligned"] == ctr_o["num_aligned"] > 80
+    # the counters after the part that was redone with the global tables, and that it was (smr_cand_info: a test seam)
+    assert ctr_g["reads_matched_per_db"][0] == ctr_o["per_db"] and engine.prof().n_sw_fwd == ctr_o["n_sw_fwd"], (ctr_g, engine.prof().n_sw_fwd, ctr_o)
+    # (chain_ext stays on for the life of a context, and this one is shared: what says that THIS call used the global tables is the way its reads took)
+    assert engine.cand_info()["chain_ext"] and sum(1 for r in routes if r & smr.engine.ROUTE_EXT) > 80, (engine.cand_info(), sum(1 for r in routes if r & 8))
     recs_o, ctr_o = w.oracle_records(num_alignments=5)
     recs_g, ctr_g = w.gpu_records(engine, num_alignments=5)
     _compare(recs_g, recs_o, "1500-member family, best 5")

@@ -21,6 +21,12 @@ import sortmerna_amd as smr  # noqa: E402
 from helpers import emu, orc  # noqa: E402
 from helpers.workload import Workload  # noqa: E402
 
+# the crafted shapes of the candidate stage, one more kind of workload.  Only a tests/ tree that has no such FILE (an older suite run against this tool)
+# goes without, and every case that would have drawn the kind says so; a helper that is there and does not import is an error like any other.
+candcase = None
+if os.path.isfile(os.path.join(ROOT, "tests", "helpers", "candcase.py")):
+    from helpers import candcase  # noqa: E402
+
 SCHEMES = [(2, -3, 5, 2), (2, -3, 5, 2), (2, -3, 3, 2), (3, -4, 6, 3), (5, -4, 5, 2), (1, -2, 3, 1), (2, -3, 4, 3), (4, -5, 7, 3), (2, -3, 10, 2), (1, -1, 2, 1),
            (2, -3, 3, 3), (2, -5, 2, 1)]      # the last two (round 6): schemes that go through the striped slow path (smr_sw_striped.hpp)
 
@@ -57,7 +63,15 @@ def case(seed, tmp):
         wk["db_ambiguous"] = float(pick([0.0005, 0.003]))
     if pick([0, 0, 0, 1]):
         wk["max_mb"] = float(pick([0.4, 0.8, 1.5]))          # several index parts
-    w = Workload(tmp, **wk)
+    crafted = pick([0, 0, 0, 1])        # (drawn in every case: the draws of a seed do not depend on what is installed)
+    if crafted and candcase is None:
+        print("seed %d: tests/helpers/candcase.py is not there, the seeded random workload instead of the crafted one" % seed, flush=True)
+    if lnwin == 18 and "max_mb" not in wk and crafted and candcase is not None:
+        # the crafted shapes of the candidate stage (tests/helpers/candcase.py: reads at 63..257 positions, 63..65 hits, tandem references), seeded by the case
+        w = candcase.mixed_workload(tmp, seed=seed)
+        wk = dict(crafted="candcase.mixed_workload", seed=seed, lnwin=18)
+    else:
+        w = Workload(tmp, **wk)
     ms = max(1, int(w.minimal_score) + delta)
     return w, wk, opts, ms
 
