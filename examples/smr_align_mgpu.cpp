@@ -32,6 +32,14 @@
 //                              written) and aligned_denovo.fa|fq, and aligned.log with the two Results lines.  Defaults and refusals are the
 //                              reference's (options.cpp:1623-1628, 1667-1674, 1744-1757): 0.97 / 0.97 under -otu_map, else 0; -id / -coverage
 //                              without -otu_map and -otu_map with -no-best are errors
+//          --state-out FILE    after the last part: the stored state of the whole run -- magic "SMRSTATE1", u64 n_reads, u64 digest of the reads
+//                              (smr_reads_digest over the whole input), u64 n_db, the counter block of smr_counters (2 + n_db u64), u64 off[n_reads + 1],
+//                              the records (Read::toBinString bytes) back to back -- what the reference leaves in its key-value store
+//          --state-in FILE     continue the run that wrote FILE on further databases (the reference re-run with further --ref, Read::load_db
+//                              read.cpp:467-539): --ref names only the further DBs, their index_num continues after the stored n_db, and every chunk
+//                              gets its slice of the records (smr_state_import) before its first part.  A file for other reads (count or digest)
+//                              is refused before anything is aligned.  Not together with the report files or the %id / %coverage pass, which
+//                              need the references of the earlier DBs as well
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 
@@ -114,12 +122,37 @@ void all_reduce_sum_u64(Shared& S, int rank, void* dptr, size_t n, hipStream_t s
   if (hipMemcpy(dptr, h.data(), n * 8, hipMemcpyHostToDevice) != hipSuccess) die("hipMemcpy H2D (host reduction) failed");
 }
 
+// --state-in: the file --state-out wrote
+struct StateIn {
+  uint64_t n_reads = 0, digest = 0, n_db = 0;
+  std::vector<uint64_t> counters, off;
+  std::vector<uint8_t> bytes;
+};
+void load_state(const std::string& path, StateIn& st) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) die("cannot read " + path);
+  char magic[9];
+  uint64_t h[3];
+  if (fread(magic, 1, 9, f) != 9 || memcmp(magic, "SMRSTATE1", 9) != 0 || fread(h, 8, 3, f) != 3) die(path + " is not a state file (--state-out writes them)");
+  st.n_reads = h[0]; st.digest = h[1]; st.n_db = h[2];
+  if (st.n_db > 64 || st.n_reads > 0xFFFFFFFFull) die(path + ": damaged header");
+  st.counters.resize(2 + st.n_db); st.off.resize(st.n_reads + 1);
+  if (fread(st.counters.data(), 8, st.counters.size(), f) != st.counters.size() || fread(st.off.data(), 8, st.off.size(), f) != st.off.size()) die(path + " is cut short");
+  for (uint64_t i = 0; i < st.n_reads; i++) if (st.off[i] > st.off[i + 1]) die(path + ": record offsets decrease");
+  if (st.off[0] != 0) die(path + ": damaged offsets");
+  st.bytes.resize(st.off[st.n_reads]);
+  if (fread(st.bytes.data(), 1, st.bytes.size(), f) != st.bytes.size() || fgetc(f) != EOF) die(path + " is cut short or has trailing bytes");
+  fclose(f);
+}
+
 struct RankOut {
   std::vector<uint8_t> records;        // concatenated (u64 klen, key, u64 vlen, value) entries of the shard
   uint64_t n_records = 0;
   std::vector<uint64_t> counters;      // reduced: identical on every rank
   uint64_t idcov[4] = {0, 0, 0, 0};    // reduced n_yid_ycov, n_yid_ncov, n_nid_ycov, num_denovo
   smr_report* rep = nullptr;           // -otu_map: kept open until the shards' maps are merged
+  std::vector<uint64_t> state_len;     // --state-out: record length of every read of the shard, the bytes back to back in state_bytes
+  std::vector<uint8_t> state_bytes;
   double t_upload = 0, t_align = 0, t_fetch = 0, t_write = 0;
   int sw_kernel = -1;                     // smr_sw_mode of the rank's context: 0 = 32-bit kernel only (the packed kernel failed its self-check or was switched off)
   uint32_t minimal_score0 = 0;
@@ -130,7 +163,7 @@ struct RankOut {
 int main(int argc, char** argv) {
   const double t_main = now_s();
   std::vector<Db> dbs;
-  std::string reads_path, out_dir = ".", reduce = "auto", devlist, flat_dir;
+  std::string reads_path, out_dir = ".", reduce = "auto", devlist, flat_dir, state_out, state_in;
   smr_params base; smr_params_default(&base);
   double evalue = 1.0;
   int world = 0;
@@ -155,6 +188,8 @@ int main(int argc, char** argv) {
     else if (a == "--devices" || a == "-devices") devlist = val();
     else if (a == "--reduce" || a == "-reduce") reduce = val();
     else if (a == "--chunk-reads" || a == "-chunk-reads") chunk_reads = strtoull(val().c_str(), nullptr, 10);
+    else if (a == "--state-out" || a == "-state-out") state_out = val();
+    else if (a == "--state-in" || a == "-state-in") state_in = val();
     else if (a == "-fastx" || a == "--fastx") ro.fastx = 1;
     else if (a == "-other" || a == "--other") ro.other = 1;
     else if (a == "-blast" || a == "--blast") {            // "1 [cigar] [qcov] [qstrand]" = tabular (options.cpp opt_blast)
@@ -179,6 +214,8 @@ int main(int argc, char** argv) {
   if (ro.otu_map) { if (!id_given) ro.min_id = 0.97; if (!cov_given) ro.min_cov = 0.97; }
   if (!(ro.min_id >= 0 && ro.min_id <= 1 && ro.min_cov >= 0 && ro.min_cov <= 1)) die("-id and -coverage take a value within [0, 1]");
   const bool idcov = ro.otu_map || ro.denovo;
+  if (!state_in.empty() && (ro.fastx || ro.other || ro.blast_tabular || ro.sam || idcov))
+    die("--state-in continues the alignment only: the report files and the %id / %coverage pass need the references of the earlier databases as well");
   if (const char* why = smr_params_refused(&base)) die(std::string("these options are outside what libsmr_hip aligns (the reference accepts them): ") + why);
   for (auto& d : dbs) if (!d.has_gumbel) die("--gumbel LAMBDA K is required for every --ref (the reference computes them with its vendored ALP library, refstats.cpp:194-233; minimal_score depends on them)");
   int ndev = 0;
@@ -283,6 +320,15 @@ int main(int argc, char** argv) {
   rccl_thread.join();
   if (reads_rc != SMR_OK) die(rerr);
   const uint64_t n = smr_reads_count(all);
+  // --state-in: the stored state must be that of THESE reads, said before anything is aligned
+  StateIn st_in;
+  if (!state_in.empty()) {
+    load_state(state_in, st_in);
+    if (st_in.n_reads != n) die(state_in + " holds the state of " + std::to_string(st_in.n_reads) + " reads, the input has " + std::to_string(n));
+    if (st_in.digest != smr_reads_digest(all)) die(state_in + " was written for other reads (the digests of the packed reads differ)");
+    if (st_in.n_db + dbs.size() > 64) die("more than 64 databases with those of " + state_in);
+  }
+  const size_t n_db0 = (size_t)st_in.n_db, n_db_all = n_db0 + dbs.size();      // the stored run's databases come first (index_num 0 .. n_db0 - 1)
   const int is_fastq = want_reports ? smr_reads_is_fastq(all) : 0;
   const double t_host = now_s() - t0;
   size_t total_parts = 0;
@@ -334,7 +380,7 @@ int main(int argc, char** argv) {
     for (size_t k = 0; k < dbs.size(); k++) {
       smr_index_info info; smr_index_get_info(dbs[k].parts[0], &info);
       pk[k].minimal_score = smr_minimal_score(dbs[k].lambda, dbs[k].K, info.bg, info.full_len, info.numseq, tot[0], tot[1], evalue);
-      pk[k].index_num = (uint32_t)k;
+      pk[k].index_num = (uint32_t)(n_db0 + k);
     }
     O.minimal_score0 = pk[0].minimal_score;
     for (size_t k = 0; k < dbs.size(); k++) O.minimal_score_db.push_back(pk[k].minimal_score);
@@ -373,6 +419,7 @@ int main(int argc, char** argv) {
         pcv.notify_all();
       }
     });
+    if (!state_out.empty()) O.state_len.assign(count, 0);
     std::thread Wt([&] {
       std::vector<uint8_t> rec; std::vector<char> hh, ss, qq;
       for (size_t c = 0; c < n_chunks; c++) {
@@ -394,6 +441,7 @@ int main(int argc, char** argv) {
             if (smr_report_add(rep, hh.data(), ss.data(), is_fastq ? qq.data() : nullptr, len ? rec.data() : nullptr, len) != SMR_OK) die(smr_report_last_error(rep));
           }
           if (!len) continue;
+          if (!state_out.empty()) { O.state_len[gi - first] = len; O.state_bytes.insert(O.state_bytes.end(), rec.begin(), rec.begin() + len); }
           const std::string key = "0_" + std::to_string(gi);
           const uint64_t kl = key.size(), vl = len;
           const size_t o = O.records.size();
@@ -417,6 +465,9 @@ int main(int argc, char** argv) {
       { std::unique_lock<std::mutex> l(pm); pcv.wait(l, [&] { return uploaded > c; }); }
       t = now_s();
       if (smr_batch_select(gpu, (int)(c % NS)) != SMR_OK) die(smr_last_error(gpu));
+      // the chunk's slice of the stored records (their offsets serve as they are).  The stored counters are sums over the whole run and are
+      // added once, by main: the chunks count from zero
+      if (!state_in.empty() && smr_state_import(gpu, st_in.bytes.data(), st_in.off.data() + chunk_first(c), (uint32_t)chunk_count(c)) != SMR_OK) die(smr_last_error(gpu));
       for (size_t k = 0; k < dbs.size(); k++)
         for (size_t part = 0; part < dbs[k].parts.size(); part++) {
           smr_params p = pk[k];
@@ -446,9 +497,9 @@ int main(int argc, char** argv) {
     {
       std::vector<uint64_t> hc(nctr);
       if (hipMemcpy(hc.data(), d_acc, (size_t)nctr * 8, hipMemcpyDeviceToHost) != hipSuccess) die("hipMemcpy failed");
-      O.counters.assign(2 + dbs.size(), 0);
+      O.counters.assign(2 + n_db_all, 0);
       O.counters[0] = hc[0]; O.counters[1] = hc[1];
-      for (size_t k = 0; k < dbs.size(); k++) O.counters[2 + k] = hc[2 + k];
+      for (size_t k = 0; k < n_db_all; k++) O.counters[2 + k] = hc[2 + k];
       if (idcov) for (int q = 0; q < 4; q++) O.idcov[q] = hc[nctr0 + q];
     }
     (void)hipFree(d_acc);
@@ -508,6 +559,11 @@ int main(int argc, char** argv) {
   }
   // ---- rank 0's view of the reduced counters is everybody's; shards concatenate in rank order ----
   for (int r = 1; r < world; r++) if (outs[r].counters != outs[0].counters) die("the ranks disagree on the reduced counters");
+  // --state-in: what the stored run had counted (num_aligned, reads_matched_per_db of its databases; num_short is the last part's, this run's)
+  if (!state_in.empty()) {
+    outs[0].counters[0] += st_in.counters[0];
+    for (size_t k = 0; k < n_db0; k++) outs[0].counters[2 + k] += st_in.counters[2 + k];
+  }
   const std::string rp = out_dir + "/records.bin", sp = out_dir + "/summary.txt";
   FILE* f = fopen(rp.c_str(), "wb");
   if (!f) die("cannot write " + rp);
@@ -519,9 +575,21 @@ int main(int argc, char** argv) {
   f = fopen(sp.c_str(), "w");
   if (!f) die("cannot write " + sp);
   const auto& ctr = outs[0].counters;
+  if (!state_out.empty()) {
+    FILE* g = fopen(state_out.c_str(), "wb");
+    if (!g) die("cannot write " + state_out);
+    const uint64_t hd[3] = {n, smr_reads_digest(all), (uint64_t)n_db_all};
+    std::vector<uint64_t> off(n + 1, 0);
+    uint64_t i = 0;
+    for (auto& o : outs) for (uint64_t l : o.state_len) { off[i + 1] = off[i] + l; i++; }      // shards in rank order = input order
+    if (i != n) die("--state-out: the shards do not cover the input");
+    bool ok = fwrite("SMRSTATE1", 1, 9, g) == 9 && fwrite(hd, 8, 3, g) == 3 && fwrite(ctr.data(), 8, ctr.size(), g) == ctr.size() && fwrite(off.data(), 8, off.size(), g) == off.size();
+    for (auto& o : outs) if (ok && !o.state_bytes.empty()) ok = fwrite(o.state_bytes.data(), 1, o.state_bytes.size(), g) == o.state_bytes.size();
+    if (fclose(g) != 0 || !ok) die("cannot write " + state_out);
+  }
   fprintf(f, "Total reads = %llu\nTotal reads passing E-value threshold = %llu\nToo short reads (last part) = %llu\n", (unsigned long long)n,
           (unsigned long long)ctr[0], (unsigned long long)ctr[1]);
-  for (size_t k = 0; k < dbs.size(); k++) fprintf(f, "%s\t%llu\n", dbs[k].fasta.c_str(), (unsigned long long)ctr[2 + k]);
+  for (size_t k = 0; k < dbs.size(); k++) fprintf(f, "%s\t%llu\n", dbs[k].fasta.c_str(), (unsigned long long)ctr[2 + n_db0 + k]);
   if (idcov) fprintf(f, "num_yid_ycov = %llu\nnum_yid_ncov = %llu\nnum_nid_ycov = %llu\nnum_denovo = %llu\nTotal OTUs = %llu\n", (unsigned long long)outs[0].idcov[0],
                      (unsigned long long)outs[0].idcov[1], (unsigned long long)outs[0].idcov[2], (unsigned long long)outs[0].idcov[3], (unsigned long long)total_otu);
   fclose(f);
@@ -533,7 +601,7 @@ int main(int argc, char** argv) {
       smr_index_info info; smr_index_get_info(dbs[k].parts[0], &info);
       sd[k].ref_file = dbs[k].fasta.c_str();
       sd[k].skiplengths[0] = info.lnwin; sd[k].skiplengths[1] = info.lnwin / 2; sd[k].skiplengths[2] = 3;
-      sd[k].lambda = dbs[k].lambda; sd[k].K = dbs[k].K; sd[k].minimal_score = outs[0].minimal_score_db[k]; sd[k].reads_matched = ctr[2 + k];
+      sd[k].lambda = dbs[k].lambda; sd[k].K = dbs[k].K; sd[k].minimal_score = outs[0].minimal_score_db[k]; sd[k].reads_matched = ctr[2 + n_db0 + k];
     }
     const time_t tt = time(nullptr);
     const std::string stamp = ctime(&tt);

@@ -21,6 +21,7 @@
  *                    traverse_bursttrie.cpp:100-298, alignment.cpp:100-509, ssw.c:834-941
  *   smr_result_*     Read::toBinString() / kvdb.put()         read.cpp:429-462, processor.cpp:150-155
  *   smr_counters     Readstats atomics                        readstats.hpp:77-85
+ *   smr_state_import  Read::load_db  read.cpp:467-539, processor.cpp:116-126
  *   smr_idcov_*      denovo_stats: %id / %coverage of every stored alignment, the four per-read and Readstats counters of -otu_map / -de_novo_otu
  *                    processor.cpp:287-438, Read::calc_miss_gap_match read.cpp:547-589
  *
@@ -308,6 +309,29 @@ size_t smr_result_record(const smr_ctx*, uint32_t read_idx, uint8_t* buf, size_t
  * thread works the same way behind its aligners, output.cpp:169-272). */
 size_t smr_result_record_batch(const smr_ctx*, int batch, uint32_t read_idx, uint8_t* buf, size_t cap);
 int    smr_result_is_hit(const smr_ctx*, uint32_t read_idx);
+
+/* Resuming a run (the reference restores every read from its key-value store at the start of every (index, part), Read::load_db, read.cpp:467-539,
+ * skips the reads stored as done, processor.cpp:116-126, and so continues a run that an earlier process stopped after any part -- e.g. on further --ref files).
+ * Inverse of smr_result_record for the selected batch.  bytes = the records back to back; off[0..n]:
+ * record i is bytes[off[i], off[i+1]) and off[i] == off[i+1] means "read i has no stored record" (off[0] need not be 0: the offsets of a
+ * chunk of reads within the records of a whole run serve as they are; only bytes[off[0], off[n]) are read).
+ * n must equal the batch's read count.  Replaces the batch's whole stored state: a read without a record
+ * gets the state of a fresh upload.  The bytes are copied to the device once and parsed there.
+ * Call order: after smr_reads_upload[_batch] (or smr_state_reset, or any smr_align_part / smr_traceback, whose results it replaces) and before the first
+ * smr_idcov_part that counted an alignment of the batch; otherwise SMR_ERR_STATE.  Afterwards smr_align_part, smr_traceback, smr_results_fetch and
+ * smr_result_record behave as if this context had produced the state itself: a part continues from it, an alignment stored with its CIGAR keeps it, one
+ * stored without (a record taken before smr_traceback) stays without, and smr_traceback of a later part touches only that part's alignments.  The
+ * records' num_alignments field becomes what smr_result_record writes, so import -> fetch -> record is the identity.
+ * Refused, each with a message, the batch left as an upload leaves it and the context usable: records whose lengths (alignment_size, an alignment's
+ * length, a CIGAR length) do not add up to off[i+1] - off[i] -- cut short, trailing bytes -- SMR_ERR_ARG; more alignments in a record than
+ * max_alignments_per_read SMR_ERR_CAPACITY; an alignment's readlen that is not the uploaded read's length SMR_ERR_ARG; a non-zero id / coverage counter
+ * (a record taken after smr_idcov_part: resuming there is not supported) SMR_ERR_ARG; records that disagree on num_alignments SMR_ERR_ARG; n that is
+ * not the batch's read count SMR_ERR_ARG.  Every field is checked against the end of its record before it is read: nothing beyond bytes + off[n] is touched.
+ * NOT part of the stored state and not imported: the Readstats counters (smr_counters_import below sets them; smr_state_import leaves them alone, so the
+ * two calls come in either order) and the work counters of smr_prof (n_hit, n_sw_fwd, ...), which count what THIS context did. */
+int smr_state_import(smr_ctx*, const uint8_t* bytes, const uint64_t* off, uint32_t n);
+/* Inverse of smr_counters: same layout, same n_db (<= 64; reads_matched_per_db beyond n_db become 0).  Same call order as smr_state_import. */
+int smr_counters_import(smr_ctx*, const uint64_t* in, uint32_t n_db);
 
 /* Seed hits of the last smr_seed_scan call (kernel-level parity + roofline bench of the seed-scan kernel).
  * Runs ONLY the window-scan/burst-trie kernel for (strand, pass) over every read of the resident batch. */

@@ -13,6 +13,7 @@
 
 #include "smr_kernels.hpp"
 #include "smr_idcov.hpp"
+#include "smr_import.hpp"
 #include "smr_ibuild.hpp"
 #include "smr_pgbuild.hpp"
 #include "smr_hostmem.hpp"
@@ -836,6 +837,7 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
 
 #include "smr_engine_trace.hpp"
 #include "smr_engine_idcov.hpp"
+#include "smr_engine_import.hpp"
 extern "C" int smr_counters(smr_ctx* c, uint64_t* out, uint32_t n_db) {
   if (!c || !out) return SMR_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));

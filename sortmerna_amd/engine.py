@@ -357,6 +357,24 @@ class Engine:
     def reset_state(self):
         self._chk(self.L.smr_state_reset(self.h), "smr_state_reset")
 
+    def import_state(self, records):
+        """the inverse of records(): one byte string per read of the selected batch, b"" = no stored record (smr_state_import).  The batch
+        then continues as if this engine had produced that state itself"""
+        off = np.zeros(len(records) + 1, dtype=np.uint64)
+        if records:
+            off[1:] = np.cumsum([len(r) for r in records], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(records) + b"\0", dtype=np.uint8)
+        self._chk(self.L.smr_state_import(self.h, blob.ctypes.data, off.ctypes.data, len(records)), "smr_state_import")
+
+    def import_counters(self, values, n_db):
+        """the inverse of counters(n_db): the dict it returns, or the flat sequence num_aligned, num_short, reads_matched_per_db[0..n_db)"""
+        if isinstance(values, dict):
+            values = [values["num_aligned"], values["num_short"]] + list(values["reads_matched_per_db"])
+        if len(values) != 2 + n_db:
+            raise SmrError("import_counters: %d values for n_db = %d (expected %d)" % (len(values), n_db, 2 + n_db))
+        arr = (C.c_uint64 * (2 + n_db))(*[int(v) for v in values])
+        self._chk(self.L.smr_counters_import(self.h, arr, n_db), "smr_counters_import")
+
     def align_part(self, slot, params):
         self._chk(self.L.smr_align_part(self.h, slot, C.byref(params)), "smr_align_part")
 
@@ -503,21 +521,31 @@ class Engine:
             self.h = None
 
 
-def align(engine, reads, index_parts, params_per_index, with_cigar=True, max_alignments_per_read=None, id_cov=None):
+def align(engine, reads, index_parts, params_per_index, with_cigar=True, max_alignments_per_read=None, id_cov=None, resume=None, first_index_num=0):
     """processor.cpp:align(): index_parts = [[Index part0, part1, ...] per --ref], params_per_index = [Params per --ref]
     (each carrying that DB's minimal_score).  Returns nothing; results stay in `engine` (fetch()/record()).
-    id_cov = (min_id, min_cov): the %id / %coverage pass (denovo_stats) over every (index, part) once all of them are aligned."""
+    id_cov = (min_id, min_cov): the %id / %coverage pass (denovo_stats) over every (index, part) once all of them are aligned.
+    resume = (records, counters): what records() and counters(n_db) of an earlier run over the same reads gave; imported after the upload, before
+    the first part, so that this call continues that run on further --ref (counters: the dict of counters(n_db), or None to leave them at 0).
+    first_index_num: the index_num of index_parts[0] -- the number of --ref the earlier run went through."""
     if id_cov is not None and not with_cigar:
         raise SmrError("align: id_cov needs the CIGARs (with_cigar=True)")
+    if id_cov is not None and resume is not None:
+        raise SmrError("align: id_cov with resume is not supported here (the pass needs the references of the earlier --ref as well)")
     p0 = params_per_index[0]
     slots = max_alignments_per_read or (p0.num_alignments if p0.num_alignments > 0 else 32)
     engine.upload_reads(reads, slots)
+    if resume is not None:
+        records, counters = resume
+        engine.import_state(records)
+        if counters is not None:
+            engine.import_counters(counters, len(counters["reads_matched_per_db"]) if isinstance(counters, dict) else len(counters) - 2)
     n_idx = len(index_parts)
     single = sum(len(parts) for parts in index_parts) == 1
     for idx_num, parts in enumerate(index_parts):
         for part, ix in enumerate(parts):
             p = params_per_index[idx_num]
-            p.index_num = idx_num
+            p.index_num = first_index_num + idx_num
             p.part = part
             p.is_last_index_part = int(idx_num == n_idx - 1 and part == len(parts) - 1)
             engine.upload_index(ix, 0)
@@ -532,7 +560,7 @@ def align(engine, reads, index_parts, params_per_index, with_cigar=True, max_ali
         for idx_num, parts in enumerate(index_parts):
             for part, ix in enumerate(parts):
                 p = params_per_index[idx_num]
-                p.index_num = idx_num
+                p.index_num = first_index_num + idx_num
                 p.part = part
                 engine.upload_index(ix, 0)
                 engine.idcov_part(0, p, id_cov[0], id_cov[1])
