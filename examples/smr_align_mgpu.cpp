@@ -40,6 +40,9 @@
 //                              gets its slice of the records (smr_state_import) before its first part.  A file for other reads (count or digest)
 //                              is refused before anything is aligned.  Not together with the report files or the %id / %coverage pass, which
 //                              need the references of the earlier DBs as well
+//          --records bulk|per-read   how a chunk's records reach the writer thread.  per-read (default): smr_results_fetch, then the writer
+//                              serialises read after read (smr_result_record_batch).  bulk: smr_state_export leaves the chunk's records back to back
+//                              in a host buffer of its batch slot, serialised on the device, and the writer slices it.  Same files either way
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 
@@ -163,7 +166,7 @@ struct RankOut {
 int main(int argc, char** argv) {
   const double t_main = now_s();
   std::vector<Db> dbs;
-  std::string reads_path, out_dir = ".", reduce = "auto", devlist, flat_dir, state_out, state_in;
+  std::string reads_path, out_dir = ".", reduce = "auto", devlist, flat_dir, state_out, state_in, records_mode = "per-read";
   smr_params base; smr_params_default(&base);
   double evalue = 1.0;
   int world = 0;
@@ -190,6 +193,7 @@ int main(int argc, char** argv) {
     else if (a == "--chunk-reads" || a == "-chunk-reads") chunk_reads = strtoull(val().c_str(), nullptr, 10);
     else if (a == "--state-out" || a == "-state-out") state_out = val();
     else if (a == "--state-in" || a == "-state-in") state_in = val();
+    else if (a == "--records" || a == "-records") { records_mode = val(); if (records_mode != "bulk" && records_mode != "per-read") die("--records: bulk or per-read, not '" + records_mode + "'"); }
     else if (a == "-fastx" || a == "--fastx") ro.fastx = 1;
     else if (a == "-other" || a == "--other") ro.other = 1;
     else if (a == "-blast" || a == "--blast") {            // "1 [cigar] [qcov] [qstrand]" = tabular (options.cpp opt_blast)
@@ -208,6 +212,7 @@ int main(int argc, char** argv) {
     else die("unknown option " + a);
   }
   if (dbs.empty() || reads_path.empty()) die("--ref and --reads are required");
+  const bool bulk = records_mode == "bulk";
   // the reference's rules for the four options (options.cpp:1623-1628, 1667-1674, 1744-1757)
   if ((id_given || cov_given) && !ro.otu_map) die("options '-id' and '-coverage' can only be used together with '-otu_map': they are the thresholds of the OTU map");
   if (ro.otu_map && !base.is_best) die("option '-otu_map' cannot be used with '-no-best': the OTU map is built from the best alignments");
@@ -420,6 +425,8 @@ int main(int argc, char** argv) {
       }
     });
     if (!state_out.empty()) O.state_len.assign(count, 0);
+    // --records bulk: the records of chunk c as smr_state_export left them, back to back, in the buffers of its batch slot
+    std::vector<uint8_t> xbytes[NS]; std::vector<uint64_t> xoff[NS];
     std::thread Wt([&] {
       std::vector<uint8_t> rec; std::vector<char> hh, ss, qq;
       for (size_t c = 0; c < n_chunks; c++) {
@@ -428,25 +435,30 @@ int main(int argc, char** argv) {
         const uint32_t cnt = smr_reads_count(cr[c]);
         for (uint32_t i = 0; i < cnt; i++) {
           // results of the shard (kvdb.put(read.id, read.toBinString()), processor.cpp:150-155), keys carry the GLOBAL read number
-          const size_t len = smr_result_record_batch(gpu, (int)(c % NS), i, nullptr, 0);
+          const size_t len = bulk ? (size_t)(xoff[c % NS][i + 1] - xoff[c % NS][i]) : smr_result_record_batch(gpu, (int)(c % NS), i, nullptr, 0);
           if (!len && !(rep && ro.other)) continue;
-          rec.resize(len);
-          if (len) smr_result_record_batch(gpu, (int)(c % NS), i, rec.data(), len);
+          const uint8_t* rp = nullptr;
+          if (bulk) rp = xbytes[c % NS].data() + xoff[c % NS][i];
+          else {
+            rec.resize(len);
+            if (len) smr_result_record_batch(gpu, (int)(c % NS), i, rec.data(), len);
+            rp = rec.data();
+          }
           const uint64_t gi = chunk_first(c) + i;
           if (rep) {
             size_t tl[3];
             smr_reads_record_text(all, (uint32_t)gi, nullptr, 0, nullptr, 0, nullptr, 0, tl);
             hh.resize(tl[0] + 1); ss.resize(tl[1] + 1); qq.resize(tl[2] + 1);
             smr_reads_record_text(all, (uint32_t)gi, hh.data(), hh.size(), ss.data(), ss.size(), qq.data(), qq.size(), tl);
-            if (smr_report_add(rep, hh.data(), ss.data(), is_fastq ? qq.data() : nullptr, len ? rec.data() : nullptr, len) != SMR_OK) die(smr_report_last_error(rep));
+            if (smr_report_add(rep, hh.data(), ss.data(), is_fastq ? qq.data() : nullptr, len ? rp : nullptr, len) != SMR_OK) die(smr_report_last_error(rep));
           }
           if (!len) continue;
-          if (!state_out.empty()) { O.state_len[gi - first] = len; O.state_bytes.insert(O.state_bytes.end(), rec.begin(), rec.begin() + len); }
+          if (!state_out.empty()) { O.state_len[gi - first] = len; O.state_bytes.insert(O.state_bytes.end(), rp, rp + len); }
           const std::string key = "0_" + std::to_string(gi);
           const uint64_t kl = key.size(), vl = len;
           const size_t o = O.records.size();
           O.records.resize(o + 16 + kl + vl);
-          memcpy(&O.records[o], &kl, 8); memcpy(&O.records[o + 8], key.data(), kl); memcpy(&O.records[o + 8 + kl], &vl, 8); memcpy(&O.records[o + 16 + kl], rec.data(), vl);
+          memcpy(&O.records[o], &kl, 8); memcpy(&O.records[o + 8], key.data(), kl); memcpy(&O.records[o + 8 + kl], &vl, 8); memcpy(&O.records[o + 16 + kl], rp, vl);
           O.n_records++;
         }
         smr_reads_free(cr[c]); cr[c] = nullptr;
@@ -483,7 +495,18 @@ int main(int argc, char** argv) {
             p.part = (uint32_t)part;
             if (smr_idcov_part(gpu, slot[k][part], &p, ro.min_id, ro.min_cov) != SMR_OK) die(smr_last_error(gpu));
           }
-      if (smr_counters_accumulate(gpu, d_acc, nctr) != SMR_OK || smr_results_fetch(gpu) != SMR_OK) die(smr_last_error(gpu));
+      if (smr_counters_accumulate(gpu, d_acc, nctr) != SMR_OK) die(smr_last_error(gpu));
+      if (bulk) {
+        // one call where the buffer of the slot is large enough (it grows to the largest chunk's records), a second one after it has grown
+        std::vector<uint8_t>& xb = xbytes[c % NS]; std::vector<uint64_t>& xo = xoff[c % NS];
+        const uint32_t cn = (uint32_t)chunk_count(c);
+        xo.resize((size_t)cn + 1);
+        uint64_t need = 0;
+        if (xb.empty()) xb.resize(4096);
+        int rc = smr_state_export(gpu, xb.data(), xb.size(), xo.data(), cn, &need);
+        if (rc == SMR_ERR_CAPACITY) { xb.resize((size_t)(need + need / 8)); rc = smr_state_export(gpu, xb.data(), xb.size(), xo.data(), cn, &need); }
+        if (rc != SMR_OK) die(smr_last_error(gpu));
+      } else if (smr_results_fetch(gpu) != SMR_OK) die(smr_last_error(gpu));
       if (smr_batch_select(gpu, 15) != SMR_OK) die(smr_last_error(gpu));          // nothing of slot c % NS is "selected" while the uploader refills it later
       O.t_align += now_s() - t;
       { std::lock_guard<std::mutex> l(pm); fetched = c + 1; }

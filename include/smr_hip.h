@@ -22,6 +22,7 @@
  *   smr_result_*     Read::toBinString() / kvdb.put()         read.cpp:429-462, processor.cpp:150-155
  *   smr_counters     Readstats atomics                        readstats.hpp:77-85
  *   smr_state_import  Read::load_db  read.cpp:467-539, processor.cpp:116-126
+ *   smr_state_export  Read::toBinString  read.cpp:429-462, for a whole batch
  *   smr_idcov_*      denovo_stats: %id / %coverage of every stored alignment, the four per-read and Readstats counters of -otu_map / -de_novo_otu
  *                    processor.cpp:287-438, Read::calc_miss_gap_match read.cpp:547-589
  *
@@ -330,6 +331,17 @@ int    smr_result_is_hit(const smr_ctx*, uint32_t read_idx);
  * NOT part of the stored state and not imported: the Readstats counters (smr_counters_import below sets them; smr_state_import leaves them alone, so the
  * two calls come in either order) and the work counters of smr_prof (n_hit, n_sw_fwd, ...), which count what THIS context did. */
 int smr_state_import(smr_ctx*, const uint8_t* bytes, const uint64_t* off, uint32_t n);
+/* The other direction: the records of the whole selected batch in one call, sized and serialised on the device (csrc/smr_export.hpp), back to back in
+ * bytes with their offsets in off[0..n] (off[0] = 0; off[i] == off[i+1]: read i has no alignment and no record).  The (bytes, off) pair is what
+ * smr_state_import takes and what a state file or a key-value writer wants.  Acts on the selected batch on the engine's stream (the threading rule of
+ * smr_results_fetch, which it neither needs nor disturbs) and is allowed wherever smr_results_fetch is: before smr_traceback (CIGAR length 0), after it,
+ * after smr_idcov_part (the four id / coverage counters are then the read's, else 0).  n must be the batch's read count, else SMR_ERR_ARG; without an
+ * uploaded batch SMR_ERR_STATE.  off (n + 1 entries) and need may each be NULL; what is given is always filled, *need = off[n] = the bytes of all records.
+ * bytes == NULL: sizes only.  cap < *need: SMR_ERR_CAPACITY, nothing is written to bytes, off and *need are valid.  Otherwise exactly *need bytes are
+ * written and nothing at or behind bytes + *need is touched; bytes may be pinned memory.
+ * Invariants: for every i, bytes[off[i], off[i+1]) is what smr_results_fetch + smr_result_record(i) give, byte for byte; and
+ * smr_state_export -> smr_state_import restores the batch's stored state wherever smr_state_import accepts the records. */
+int smr_state_export(smr_ctx*, uint8_t* bytes, uint64_t cap, uint64_t* off, uint32_t n, uint64_t* need);
 /* Inverse of smr_counters: same layout, same n_db (<= 64; reads_matched_per_db beyond n_db become 0).  Same call order as smr_state_import. */
 int smr_counters_import(smr_ctx*, const uint64_t* in, uint32_t n_db);
 

@@ -14,6 +14,7 @@
 #include "smr_kernels.hpp"
 #include "smr_idcov.hpp"
 #include "smr_import.hpp"
+#include "smr_export.hpp"
 #include "smr_ibuild.hpp"
 #include "smr_pgbuild.hpp"
 #include "smr_hostmem.hpp"
@@ -122,6 +123,7 @@ struct smr_ctx {
   size_t chain_lds_attr = 0, begins_lds_attr = 0, split_lds_attr = 0, bins_lds_attr = 0;
   uint32_t* d_fidx = nullptr; RState* d_fstate = nullptr; AlignRec* d_faln = nullptr; size_t fetch_cap_r = 0, fetch_cap_a = 0;   // staging of smr_results_fetch
   uint32_t* d_fidcov = nullptr; size_t fetch_cap_i = 0;                                                                              // ... of the per-read id / coverage counters
+  uint8_t* d_xbytes = nullptr; unsigned long long* d_xoff = nullptr; unsigned long long* d_xpart = nullptr; uint64_t xbytes_cap = 0; size_t xoff_cap = 0;   // staging of smr_state_export
   int sw_mode = getenv("SMR_SW_PACKED") ? atoi(getenv("SMR_SW_PACKED")) : 2;   // 1 / 2: packed 16-bit Smith-Waterman kernels (smr_sw_pk.hpp; 2 = lane hand-over by wave_ror, measured faster) where they apply
   unsigned long long* d_keys = nullptr; uint32_t keys_cap = 0;
   unsigned long long* d_pairs = nullptr; uint32_t* d_lis = nullptr; uint32_t pairs_cap = 0;
@@ -384,6 +386,7 @@ extern "C" void smr_destroy(smr_ctx* c) {
   for (auto& m : c->events) (void)hipEventDestroy(m.e);
   for (auto& e : c->ev_pool) (void)hipEventDestroy(e);
   dev_free(&c->d_ctr_snap); dev_free(&c->d_fidx); dev_free(&c->d_fstate); dev_free(&c->d_faln); dev_free(&c->d_fidcov);
+  dev_free(&c->d_xbytes); dev_free(&c->d_xoff); dev_free(&c->d_xpart);
   (void)hipStreamDestroy(c->upload_stream);
   (void)hipStreamDestroy(c->stream);
   delete c;
@@ -838,6 +841,7 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
 #include "smr_engine_trace.hpp"
 #include "smr_engine_idcov.hpp"
 #include "smr_engine_import.hpp"
+#include "smr_engine_export.hpp"
 extern "C" int smr_counters(smr_ctx* c, uint64_t* out, uint32_t n_db) {
   if (!c || !out) return SMR_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));

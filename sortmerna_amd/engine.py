@@ -358,13 +358,39 @@ class Engine:
         self._chk(self.L.smr_state_reset(self.h), "smr_state_reset")
 
     def import_state(self, records):
-        """the inverse of records(): one byte string per read of the selected batch, b"" = no stored record (smr_state_import).  The batch
-        then continues as if this engine had produced that state itself"""
+        """the inverse of records(): one byte string per read of the selected batch, b"" = no stored record (smr_state_import), or the
+        (blob, off) pair that export_state() returns.  The batch then continues as if this engine had produced that state itself"""
+        if isinstance(records, tuple):
+            blob, off = records
+            blob = np.ascontiguousarray(blob, dtype=np.uint8)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+            if blob.size == 0:
+                blob = np.zeros(1, dtype=np.uint8)
+            self._chk(self.L.smr_state_import(self.h, blob.ctypes.data, off.ctypes.data, len(off) - 1), "smr_state_import")
+            return
         off = np.zeros(len(records) + 1, dtype=np.uint64)
         if records:
             off[1:] = np.cumsum([len(r) for r in records], dtype=np.uint64)
         blob = np.frombuffer(b"".join(records) + b"\0", dtype=np.uint8)
         self._chk(self.L.smr_state_import(self.h, blob.ctypes.data, off.ctypes.data, len(records)), "smr_state_import")
+
+    def export_state(self):
+        """the records of the selected batch, sized and serialised on the device (smr_state_export; no fetch() needed): -> (blob, off), record i
+        is blob[off[i]:off[i + 1]], empty for a read without alignments.  What import_state takes and a state file holds"""
+        n = self.n_reads
+        off = np.zeros(n + 1, dtype=np.uint64)
+        need = C.c_uint64(0)
+        self._chk(self.L.smr_state_export(self.h, None, 0, off.ctypes.data, n, C.byref(need)), "smr_state_export")
+        blob = np.zeros(need.value, dtype=np.uint8)
+        if need.value:
+            self._chk(self.L.smr_state_export(self.h, blob.ctypes.data, need.value, off.ctypes.data, n, C.byref(need)), "smr_state_export")
+        return blob, off
+
+    def export_records(self):
+        """export_state() cut into one byte string per read: what fetch() + records() give"""
+        blob, off = self.export_state()
+        raw = blob.tobytes()
+        return [raw[int(off[i]):int(off[i + 1])] for i in range(len(off) - 1)]
 
     def import_counters(self, values, n_db):
         """the inverse of counters(n_db): the dict it returns, or the flat sequence num_aligned, num_short, reads_matched_per_db[0..n_db)"""
