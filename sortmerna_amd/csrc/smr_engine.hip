@@ -18,6 +18,7 @@
 #include "smr_ibuild.hpp"
 #include "smr_pgbuild.hpp"
 #include "smr_hostmem.hpp"
+#include "smr_devbuf.hpp"
 
 using namespace smr;
 
@@ -25,15 +26,22 @@ namespace {
 
 struct DevIndex {
   bool used = false;
-  Lookup* lookup = nullptr; uint32_t* trie = nullptr; uint32_t* pos_off = nullptr; uint2* pos_arr = nullptr;
-  uint32_t* pg = nullptr; uint32_t* root3 = nullptr; uint32_t* lkc = nullptr;
-  uint8_t* ref_seq = nullptr; uint64_t* ref_off = nullptr;
+  DevBuf<Lookup> lookup; DevBuf<uint32_t> trie, pos_off; DevBuf<uint2> pos_arr;
+  DevBuf<uint32_t> pg, root3, lkc;
+  DevBuf<uint8_t> ref_seq; DevBuf<uint64_t> ref_off;
   uint32_t n_refs = 0, n_ids = 0, lnwin = 0;
   uint32_t ref_any_n = 1;     // does any reference hold an ambiguous letter (0 only when the upload looked and found none)
   uint64_t trie_words = 0, n_pos = 0, ref_bytes = 0, pg_words = 0;
 };
 
 struct EvMark { hipEvent_t e; int kind; };        // kind < 0: end of a run of intervals
+struct EvPool {                                   // the marks in flight and the events to be used again
+  std::vector<EvMark> events; std::vector<hipEvent_t> pool;
+  EvPool() = default;
+  EvPool(const EvPool&) = delete;
+  EvPool& operator=(const EvPool&) = delete;
+  ~EvPool() { for (auto& m : events) (void)hipEventDestroy(m.e); for (auto& e : pool) (void)hipEventDestroy(e); }
+};
 
 }  // namespace
 
@@ -52,15 +60,16 @@ struct Batch {
   uint32_t min_ge[7] = {~0u, ~0u, ~0u, ~0u, ~0u, ~0u, ~0u};     // the shortest read of at least 8, 10, ... 20 letters (~0: none): what `--edges N%` is smallest for
   uint64_t gen = 0;                        // counts the uploads and state resets of this batch (what a shared seed sort was built for)
   bool min_ge_known = false;               // (computed when a call with is_as_percent asks for it: one pass over the lengths, which the default options never need)
-  uint32_t* d_words = nullptr; uint64_t* d_rec_off = nullptr; uint32_t* d_len = nullptr;
-  RState* d_saved = nullptr; RState* d_work = nullptr; RWork* d_rw = nullptr;
-  uint8_t* d_marks = nullptr;              // per read: k_chain has to walk it in this (strand, pass) (k_cand)
-  AlignRec* d_saved_aln = nullptr; AlignRec* d_work_aln = nullptr;
-  unsigned long long* d_ctr = nullptr;
-  uint32_t* d_cigar = nullptr; uint64_t cigar_words = 0;
+  // (grow-only: a re-upload into the same batch allocates nothing unless it is larger)
+  DevBuf<uint32_t> d_words; DevBuf<uint64_t> d_rec_off; DevBuf<uint32_t> d_len;
+  DevBuf<RState> d_saved, d_work; DevBuf<RWork> d_rw;
+  DevBuf<uint8_t> d_marks;                 // per read: k_chain has to walk it in this (strand, pass) (k_cand)
+  DevBuf<AlignRec> d_saved_aln, d_work_aln;
+  DevBuf<unsigned long long> d_ctr;
+  DevBuf<uint32_t> d_cigar; uint64_t cigar_words = 0;      // (cigar_words: the pool's size as the kernels are told it)
   // the %id / %coverage pass (smr_idcov.hpp): per read {c_yid_ycov, n_yid_ncov, n_nid_ycov, n_denovo} of Read (read.hpp), part of what round-trips
   // through the reference's KVDB; allocated by the first smr_idcov_part of the batch (a run that never asks for the pass pays nothing)
-  uint32_t* d_idcov = nullptr; size_t cap_idcov = 0; bool idcov_ran = false;
+  DevBuf<uint32_t> d_idcov; bool idcov_ran = false;
   std::vector<uint32_t> h_idcov;           // of the reads with alignments, packed like h_state (empty: all zero)
   // host copies of results
   std::vector<RState> h_state; std::vector<AlignRec> h_aln; std::vector<uint32_t> h_cigar;       // of the reads with alignments, packed
@@ -68,23 +77,26 @@ struct Batch {
   uint32_t last_num_alignments = 1;
   unsigned long long redo_seen = 0, win_seen = 0;        // C_SEED_REDO / C_WINDOWS at the end of the previous part (smr_align_part sizes k_seed_pg's candidate pool from the increments)
   bool fetched = false;
-  // capacities of the device arrays above (grow-only: a re-upload into the same batch allocates nothing unless it is larger)
-  size_t cap_words = 0, cap_reads = 0, cap_aln = 0;
 };
 
 // (one seed sort for the index parts of a batch: see ensure_shared_sort)
-struct SharedSet { SeedTup* srt = nullptr; uint16_t* wbin = nullptr; uint32_t* cbase = nullptr; uint32_t* sn = nullptr; uint32_t maxwin = 0; bool built = false; };
+struct SharedSet { DevBuf<SeedTup> srt; DevBuf<uint16_t> wbin; DevBuf<uint32_t> cbase, sn; uint32_t maxwin = 0; bool built = false; };
 struct SharedSort {
   SharedSet set[2][3];
   const void* batch = nullptr; uint64_t gen = 0; uint32_t lnwin = 0, skip[3] = {0, 0, 0}, n = 0, max_len = 0;
   uint64_t cap[3] = {0, 0, 0};
   bool usable = false;
-  uint32_t* abits = nullptr; size_t abits_words = 0;
+  DevBuf<uint32_t> abits;
+};
+// the owner of the seed-stage scratch; SeedBufs (smr_seed.hpp) is the view of it that the kernels take by value
+struct SeedScratch {
+  DevBuf<uint32_t> chist, cbase, rows, bcnt, wseg[2], fbits[2], zbits, gflag, emap, sn, redo, hpre, hlist, hh;
+  DevBuf<SeedTup> tmp, mid, srt; DevBuf<uint16_t> wbin; DevBuf<uint2> pieces;
 };
 
 struct smr_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;
+  DevStream stream, upload_stream;        // upload_stream: smr_reads_upload_batch, H2D of batch k+1 while batch k is aligned on `stream`
   std::string err;                        // last error; written under err_m (smr_reads_upload_batch runs on a second host thread)
   std::mutex err_m, sel_m;                // sel_m: which batch is selected (read by smr_reads_upload_batch)
   int n_cu = 256;
@@ -92,7 +104,7 @@ struct smr_ctx {
   Batch bt[SMR_MAX_BATCHES];
   Batch* b = &bt[0];
   // pools / scratch (shared by all batches: one batch is aligned at a time)
-  uint32_t* d_pool = nullptr; uint64_t pool_words = 0;
+  DevBuf<uint32_t> d_pool; uint64_t pool_words = 0;
   uint64_t n_pool_grown = 0;              // seed-hit pool regrows (C_ERR_POOL) since smr_create (smr_seed_pool_info)
   uint32_t pool_inline = 0;               // SeedBufs::seg_inline of the last seed-stage launch (smr_seed_pool_info)
   uint32_t hcap = 4;                      // lane-local hit list capacity of k_seed_search; doubles (and the part is redone) on overflow
@@ -105,89 +117,96 @@ struct smr_ctx {
   uint32_t hot_min = getenv("SMR_SEED_DEDUP") ? (uint32_t)std::max(0, atoi(getenv("SMR_SEED_DEDUP"))) : 1024u;
   // one seed sort for the index parts of a batch (SharedSort below): 0 off, 1 when the part in hand is not the batch's last, 2 always (tests)
   int seed_shared = getenv("SMR_SEED_SHARED") ? atoi(getenv("SMR_SEED_SHARED")) : 1;
-  uint16_t* d_sw_scr = nullptr; uint32_t sw_scr_stride = 0; size_t sw_scr_words = 0;      // scratch rows of the striped Smith-Waterman slow path (smr_sw_striped.hpp), one per block
+  DevBuf<uint16_t> d_sw_scr; uint32_t sw_scr_stride = 0;      // scratch rows of the striped Smith-Waterman slow path (smr_sw_striped.hpp), one per block
   int last_seed_slot = -1;                 // index slot of the last smr_seed_scan (smr_seed_hits_fetch translates its ids back)
-  SharedSort* shared = nullptr;
+  SharedSort shared;
   uint64_t n_seed_shared = 0, n_seed_shared_builds = 0;      // smr_prof
   uint32_t ccap = PG_CAND_CAP0;           // candidate records per wave of k_seed_pg; doubles when more than 1/64 of the waves of a part overflow
   // k_seed_pg: waves of the launch (0: one per wave chunk the batch can have; else a wave walks chunks it, it + grid, ...), XCD-aware chunk order
   uint32_t pg_grid = getenv("SMR_PG_GRID") ? (uint32_t)atoi(getenv("SMR_PG_GRID")) : 262144u;
   int pg_swz = getenv("SMR_PG_SWZ") ? atoi(getenv("SMR_PG_SWZ")) : 0;
-  SeedBufs sb = {};                       // seed-stage scratch (smr_seed.hpp)
+  SeedScratch seed; SeedBufs sb = {};     // seed-stage scratch and the kernels' view of it (smr_seed.hpp)
   uint64_t sb_slots = 0; uint32_t sb_nk = 0;
   uint32_t chain_blocks = 0;
-  unsigned long long* d_tuples = nullptr; uint32_t chain_scap = 512;   // (pos, slot, win) tuples; slots of the candidate set S in LDS
+  DevBuf<unsigned long long> d_tuples; uint32_t chain_scap = 512;   // (pos, slot, win) tuples; slots of the candidate set S in LDS
   uint32_t keys_need = 0;
   bool chain_ext = false;                                              // a read's candidate set has outgrown the LDS table once: global tables are on
-  uint32_t* d_stab = nullptr; unsigned long long* d_tuples2 = nullptr; // per block: CH_EXT_CAP-slot table (4 arrays), tuples grouped by member
+  DevBuf<uint32_t> d_stab; DevBuf<unsigned long long> d_tuples2;       // per block: CH_EXT_CAP-slot table (4 arrays), tuples grouped by member
   size_t chain_lds_attr = 0, begins_lds_attr = 0, split_lds_attr = 0, bins_lds_attr = 0;
-  uint32_t* d_fidx = nullptr; RState* d_fstate = nullptr; AlignRec* d_faln = nullptr; size_t fetch_cap_r = 0, fetch_cap_a = 0;   // staging of smr_results_fetch
-  uint32_t* d_fidcov = nullptr; size_t fetch_cap_i = 0;                                                                              // ... of the per-read id / coverage counters
-  uint8_t* d_xbytes = nullptr; unsigned long long* d_xoff = nullptr; unsigned long long* d_xpart = nullptr; uint64_t xbytes_cap = 0; size_t xoff_cap = 0;   // staging of smr_state_export
+  DevBuf<uint32_t> d_fidx; DevBuf<RState> d_fstate; DevBuf<AlignRec> d_faln;       // staging of smr_results_fetch
+  DevBuf<uint32_t> d_fidcov;                                                       // ... of the per-read id / coverage counters
+  DevBuf<uint8_t> d_xbytes; DevBuf<unsigned long long> d_xoff, d_xpart;            // staging of smr_state_export (d_xpart grows with d_xoff)
   int sw_mode = getenv("SMR_SW_PACKED") ? atoi(getenv("SMR_SW_PACKED")) : 2;   // 1 / 2: packed 16-bit Smith-Waterman kernels (smr_sw_pk.hpp; 2 = lane hand-over by wave_ror, measured faster) where they apply
-  unsigned long long* d_keys = nullptr; uint32_t keys_cap = 0;
-  unsigned long long* d_pairs = nullptr; uint32_t* d_lis = nullptr; uint32_t pairs_cap = 0;
-  uint2* d_hits = nullptr; uint32_t hits_cap = 0;
-  uint8_t* d_rdq = nullptr; size_t rdq_cap = 0;
+  // (keys_cap, pairs_cap, hits_cap: per block of k_chain, the layout its kernels are told)
+  DevBuf<unsigned long long> d_keys; uint32_t keys_cap = 0;
+  DevBuf<unsigned long long> d_pairs; DevBuf<uint32_t> d_lis; uint32_t pairs_cap = 0;
+  DevBuf<uint2> d_hits; uint32_t hits_cap = 0;
+  DevBuf<uint8_t> d_rdq;
   // k_cand -> k_chain hand-over (smr_chain.hpp): {offset, npos} per read, the records (SMR_HANDOVER=0 switches it off)
   int handover = getenv("SMR_HANDOVER") ? atoi(getenv("SMR_HANDOVER")) : 1;
-  uint2* d_mrec = nullptr; uint32_t* d_mpool = nullptr; size_t mrec_cap = 0, mpool_words = 0;
+  DevBuf<uint2> d_mrec; DevBuf<uint32_t> d_mpool;
   // the candidate walk in rounds (smr_walk.hpp): walk kernel -> Smith-Waterman over a task list -> next list; SMR_WALK_SPLIT=0: k_chain walks every marked read
   int walk_split = getenv("SMR_WALK_SPLIT") ? atoi(getenv("SMR_WALK_SPLIT")) : 1;
   uint32_t walk_rounds = getenv("SMR_WALK_ROUNDS") ? (uint32_t)std::max(1, std::min(32, atoi(getenv("SMR_WALK_ROUNDS")))) : 8u;      // the last one scores in the kernel
   uint32_t walk_k = getenv("SMR_WALK_K") ? (uint32_t)std::max(1, std::min((int)WK_MAX, atoi(getenv("SMR_WALK_K")))) : 4u;           // tasks a read leaves per round, at least (smr_walk.hpp walk_tasks_per_read)
   int walk_gather = getenv("SMR_WALK_GATHER") ? atoi(getenv("SMR_WALK_GATHER")) : 1;     // 0: only reads with a record of k_cand go through the rounds (at most 64 positions)
   uint32_t walk_assume = getenv("SMR_WALK_ASSUME") ? (uint32_t)atoi(getenv("SMR_WALK_ASSUME")) : 3u;                                 // round 0 predicts "aligns" from this many seeds of the best candidate
-  uint2* d_wlist[2] = {nullptr, nullptr}; WState* d_wstate[2] = {nullptr, nullptr}; WTask* d_wtask[2] = {nullptr, nullptr}; uint2* d_wres[2] = {nullptr, nullptr};
-  uint32_t* d_wtidx = nullptr; uint32_t* d_wslow = nullptr; unsigned long long* d_wctr = nullptr; size_t walk_cap = 0; uint32_t walk_kcap = 0, walk_rcap = 0;
+  DevBuf<uint2> d_wlist[2]; DevBuf<WState> d_wstate[2]; DevBuf<WTask> d_wtask[2]; DevBuf<uint2> d_wres[2];
+  DevBuf<uint32_t> d_wtidx, d_wslow; DevBuf<unsigned long long> d_wctr; size_t walk_cap = 0; uint32_t walk_kcap = 0;      // walk_cap x walk_kcap: the layout of d_wtidx
   size_t walk_lds_attr = 0, pg_lds_attr = 0, search_lds_attr = 0;
   uint64_t sw16_launches[8] = {};          // k_sw16<13 | 19 | 26 | 32> launched by the walk rounds [0..3] and by the begin-cell stage [4..7] (smr_sw16_launches)
   // rounds per (strand, pass): without SMR_WALK_ROUNDS the number adapts to what the previous part needed (the last round with more than a few
   // reads listed + the closing one: an empty round still costs three launches, ~70 us of stream time; 8 -> 4 rounds = 3 % of the bench step)
   bool walk_rounds_fixed = getenv("SMR_WALK_ROUNDS") != nullptr;
   uint32_t walk_need[3] = {0, 0, 0};
-  unsigned long long* d_wstat = nullptr; uint32_t wstat_n = 0; int wstat_pass[8] = {}; uint32_t wstat_rm[8] = {};
-  int* d_bound = nullptr; size_t bound_cap = 0;                        // strip-boundary rows of the SW kernels (reads of more than one strip), per block
-  uint32_t* d_tasks = nullptr; uint64_t tasks_cap = 0;
-  uint8_t* d_trflags = nullptr; uint64_t trflags_bytes = 0;            // direction flags of k_trace_wide (one tile per block)
-  int* d_trrows = nullptr; uint64_t trrows_ints = 0;                   // its DP rows when the band does not fit LDS
+  DevBuf<unsigned long long> d_wstat; uint32_t wstat_n = 0; int wstat_pass[8] = {}; uint32_t wstat_rm[8] = {};
+  DevBuf<int> d_bound;                                                 // strip-boundary rows of the SW kernels (reads of more than one strip), per block
+  DevBuf<uint32_t> d_tasks;                                            // two lists of reads x slots entries
+  DevBuf<uint8_t> d_trflags;                                           // direction flags of k_trace_wide (one tile per block)
+  DevBuf<int> d_trrows;                                                // its DP rows when the band does not fit LDS
   // profiling
-  std::vector<EvMark> events; std::vector<hipEvent_t> ev_pool;
+  EvPool ev;
   double kp_ms[KP_COUNT] = {}; uint64_t kp_l[KP_COUNT] = {};       // HIP-event time and launches per kernel family (smr_prof_kernels)
-  hipStream_t upload_stream = nullptr;     // smr_reads_upload_batch: H2D of batch k+1 while batch k is aligned on `stream`
-  unsigned long long* d_ctr_snap = nullptr; // counters of the selected batch at the start of smr_align_part (restored when an attempt is redone)
+  DevBuf<unsigned long long> d_ctr_snap;    // counters of the selected batch at the start of smr_align_part (restored when an attempt is redone)
   // smr_cand_info (a test seam): what the retry ladder of the last smr_align_part did, and -- once switched on by smr_cand_info_enable -- one byte per
   // read that says which way it went through the candidate stage in the launches of the final attempt (k_cand_route; no other kernel knows of it)
-  bool cinfo_on = false; uint8_t* d_croute = nullptr; size_t croute_cap = 0; uint32_t croute_n = 0;
+  bool cinfo_on = false; DevBuf<uint8_t> d_croute; uint32_t croute_n = 0;
   uint32_t cinfo_attempts = 0, cinfo_retry[5] = {0, 0, 0, 0, 0};       // attempts; redone because of HITCAP, POOL, PAIRS, REDO, SCAP
 };
 struct KpSave { double ms[KP_COUNT]; uint64_t l[KP_COUNT]; };
 
 #define SEED_REDO_CAP 16384u
 
+int dev_fail(smr_ctx* c, const char* call, hipError_t e) {
+  std::lock_guard<std::mutex> l_(c->err_m);
+  c->err = std::string(call) + ": " + hipGetErrorString(e);
+  return SMR_ERR_DEVICE;
+}
+
 namespace {
 
-#define HIPCHK(ctx, call)                                                                        \
-  do {                                                                                           \
-    hipError_t e_ = (call);                                                                      \
-    if (e_ != hipSuccess) {                                                                      \
-      std::lock_guard<std::mutex> l_((ctx)->err_m);                                              \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                            \
-      return SMR_ERR_DEVICE;                                                                     \
-    }                                                                                            \
+#define HIPCHK(ctx, call)                                          \
+  do {                                                             \
+    hipError_t e_ = (call);                                        \
+    if (e_ != hipSuccess) return dev_fail((ctx), #call, e_);       \
   } while (0)
 
 // every write of the context's error string goes through here (smr_reads_upload_batch runs on a second host thread)
 void set_err(smr_ctx* c, const std::string& msg) { std::lock_guard<std::mutex> l_(c->err_m); c->err = msg; }
 
-template <class T> int dev_alloc(smr_ctx* c, T** p, size_t count) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  if (count == 0) count = 1;
-  HIPCHK(c, hipMalloc((void**)p, count * sizeof(T)));
+
+// a kernel on the engine's stream; the kernel's own parameter types convert the arguments (a DevBuf<T> to T* or const T*)
+template <class T> struct arg_of { typedef T type; };
+template <class... P> void launch(smr_ctx* c, void (*k)(P...), dim3 grid, dim3 block, size_t lds, typename arg_of<P>::type... a) {
+  hipLaunchKernelGGL(k, grid, block, lds, c->stream, a...);
+}
+// "the dynamic-LDS limit of these kernels is at least `bytes`": set once per high-water mark, and only above what every kernel may use anyway
+template <class... F> int raise_lds_limit(smr_ctx* c, size_t& high_water, size_t bytes, size_t free_bytes, F... kernels) {
+  if (bytes <= free_bytes || bytes <= high_water) return SMR_OK;
+  for (const void* k : {(const void*)kernels...}) HIPCHK(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  high_water = bytes;
   return SMR_OK;
 }
-template <class T> void dev_free(T** p) { if (*p) { (void)hipFree(*p); *p = nullptr; } }
-
 
 const char* scheme_unsupported(int mismatch, int score_N, int gap_open, int gap_ext);
 DParams make_dparams(const smr_ctx* c, const DevIndex& di, const smr_params* p) {
@@ -243,29 +262,31 @@ int check_params(smr_ctx* c, const smr_params* p, bool sw = true) {
 }
 
 DIndex dindex(const DevIndex& d) {
-  DIndex x; x.lookup = d.lookup; x.trie = d.trie; x.pg = d.pg; x.lkc = d.lkc; x.root3 = reinterpret_cast<const uint2*>(d.root3); x.pos_off = d.pos_off; x.pos_arr = d.pos_arr; x.ref_seq = d.ref_seq; x.ref_off = d.ref_off;
+  DIndex x; x.lookup = d.lookup; x.trie = d.trie; x.pg = d.pg; x.lkc = d.lkc; x.root3 = reinterpret_cast<const uint2*>(d.root3.get()); x.pos_off = d.pos_off; x.pos_arr = d.pos_arr; x.ref_seq = d.ref_seq; x.ref_off = d.ref_off;
   x.n_refs = d.n_refs; x.n_ids = d.n_ids; x.lnwin = d.lnwin; x.partialwin = d.lnwin / 2; x.ref_any_n = d.ref_any_n;
   return x;
 }
 DReads dreads(const smr_ctx* c) { DReads r; r.words = c->b->d_words; r.rec_off = c->b->d_rec_off; r.len = c->b->d_len; r.n = c->b->n; r.max_len = c->b->max_len; return r; }
 
-int ensure_chain_scratch(smr_ctx* c, const DevIndex& di) {
-  if (c->chain_blocks == 0) c->chain_blocks = (uint32_t)c->n_cu * (getenv("SMR_CHAIN_WPC") ? atoi(getenv("SMR_CHAIN_WPC")) : 12);     // k_chain: 3 waves per SIMD by registers
-  (void)di;
-  uint32_t need_keys = std::max(std::max(c->chain_scap, 1024u), c->keys_need);
-  if (c->keys_cap < need_keys) { int rc = dev_alloc(c, &c->d_keys, (size_t)c->chain_blocks * need_keys); if (rc) return rc; c->keys_cap = need_keys; }
+// blocks of k_chain (the one place that says how many): 3 waves per SIMD by registers
+uint32_t chain_blocks(smr_ctx* c) {
+  if (c->chain_blocks == 0) c->chain_blocks = (uint32_t)c->n_cu * (getenv("SMR_CHAIN_WPC") ? atoi(getenv("SMR_CHAIN_WPC")) : 12);
+  return c->chain_blocks;
+}
+// k_chain's scratch per block; the retry ladder of smr_align_part releases an array (and changes its *_cap) to have it made again here
+int ensure_chain_scratch(smr_ctx* c) {
+  const size_t nb = chain_blocks(c);
+  int rc;
+  const uint32_t need_keys = std::max(std::max(c->chain_scap, 1024u), c->keys_need);
+  if (c->keys_cap < need_keys) { if ((rc = c->d_keys.alloc(c, nb * need_keys))) return rc; c->keys_cap = need_keys; }
   if (c->pairs_cap == 0) c->pairs_cap = 4096;
-  if (!c->d_pairs) {
-    int rc = dev_alloc(c, &c->d_pairs, (size_t)c->chain_blocks * c->pairs_cap); if (rc) return rc;
-    rc = dev_alloc(c, &c->d_lis, (size_t)c->chain_blocks * 2 * c->pairs_cap); if (rc) return rc;
-    rc = dev_alloc(c, &c->d_tuples, (size_t)c->chain_blocks * c->pairs_cap); if (rc) return rc;
-  }
+  if (!c->d_pairs && ((rc = c->d_pairs.alloc(c, nb * c->pairs_cap)) || (rc = c->d_lis.alloc(c, nb * 2 * c->pairs_cap)) || (rc = c->d_tuples.alloc(c, nb * c->pairs_cap)))) return rc;
   if (c->chain_ext) {
-    if (!c->d_stab) { int rc = dev_alloc(c, &c->d_stab, (size_t)c->chain_blocks * 4 * CH_EXT_CAP); if (rc) return rc; }
-    if (!c->d_tuples2) { int rc = dev_alloc(c, &c->d_tuples2, (size_t)c->chain_blocks * c->pairs_cap); if (rc) return rc; }
+    if (!c->d_stab && (rc = c->d_stab.alloc(c, nb * 4 * CH_EXT_CAP))) return rc;
+    if (!c->d_tuples2 && (rc = c->d_tuples2.alloc(c, nb * c->pairs_cap))) return rc;
   }
   if (c->hits_cap == 0) c->hits_cap = 4096;
-  if (!c->d_hits) { int rc = dev_alloc(c, &c->d_hits, (size_t)c->chain_blocks * c->hits_cap); if (rc) return rc; }
+  if (!c->d_hits && (rc = c->d_hits.alloc(c, nb * c->hits_cap))) return rc;
   return SMR_OK;
 }
 
@@ -273,26 +294,25 @@ int ensure_chain_scratch(smr_ctx* c, const DevIndex& di) {
 // family k; ev_stop ends a run.  (Kernels of one stream run back to back anyway: a mark costs a barrier packet, no bubble.)
 void ev_mark(smr_ctx* c, int kind) {
   EvMark m; m.kind = kind;
-  if (!c->ev_pool.empty()) { m.e = c->ev_pool.back(); c->ev_pool.pop_back(); }
+  if (!c->ev.pool.empty()) { m.e = c->ev.pool.back(); c->ev.pool.pop_back(); }
   else (void)hipEventCreate(&m.e);
   (void)hipEventRecord(m.e, c->stream);
-  c->events.push_back(m);
+  c->ev.events.push_back(m);
 }
 void ev_stop(smr_ctx* c) { ev_mark(c, -1); }
-void ev_collect(smr_ctx* c) {
-  for (size_t i = 0; i + 1 < c->events.size(); i++) {
-    const int k = c->events[i].kind;
-    float ms = 0;
-    if (k >= 0 && hipEventElapsedTime(&ms, c->events[i].e, c->events[i + 1].e) == hipSuccess) { c->kp_ms[k] += ms; c->kp_l[k]++; }
-  }
-  for (auto& m : c->events) c->ev_pool.push_back(m.e);
-  c->events.clear();
-}
 // marks a call that failed half-way left behind (an error return between ev_mark and ev_stop): dropped at the start of the next timed call, or
 // ev_collect would pair the dangling mark with the first one of an unrelated run and charge the gap to a kernel family
 void ev_drop(smr_ctx* c) {
-  for (auto& m : c->events) c->ev_pool.push_back(m.e);
-  c->events.clear();
+  for (auto& m : c->ev.events) c->ev.pool.push_back(m.e);
+  c->ev.events.clear();
+}
+void ev_collect(smr_ctx* c) {
+  for (size_t i = 0; i + 1 < c->ev.events.size(); i++) {
+    const int k = c->ev.events[i].kind;
+    float ms = 0;
+    if (k >= 0 && hipEventElapsedTime(&ms, c->ev.events[i].e, c->ev.events[i + 1].e) == hipSuccess) { c->kp_ms[k] += ms; c->kp_l[k]++; }
+  }
+  ev_drop(c);
 }
 KpSave kp_save(const smr_ctx* c) { KpSave k; memcpy(k.ms, c->kp_ms, sizeof k.ms); memcpy(k.l, c->kp_l, sizeof k.l); return k; }
 void kp_restore(smr_ctx* c, const KpSave& k) { memcpy(c->kp_ms, k.ms, sizeof k.ms); memcpy(c->kp_l, k.l, sizeof k.l); }
@@ -328,20 +348,19 @@ extern "C" int smr_create(int device, smr_ctx** out, char* err, size_t errcap) {
     return SMR_ERR_DEVICE;
   }
   if (device < 0 || device >= ndev) { if (err && errcap) snprintf(err, errcap, "device %d out of range (%d devices)", device, ndev); return SMR_ERR_ARG; }
-  auto c = new smr_ctx();
-  c->shared = new SharedSort();
+  auto c = new smr_ctx();                                 // (deleting it releases whatever the steps below have made)
   c->device = device;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess || hipStreamCreate(&c->upload_stream) != hipSuccess ||
-      hipMalloc((void**)&c->d_ctr_snap, C_TOTAL * 8) != hipSuccess) {
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&c->stream.s) != hipSuccess || hipStreamCreate(&c->upload_stream.s) != hipSuccess ||
+      c->d_ctr_snap.alloc(c, C_TOTAL) != SMR_OK) {
     if (err && errcap) snprintf(err, errcap, "cannot initialise device %d", device);
-    delete c->shared; delete c; return SMR_ERR_DEVICE;
+    delete c; return SMR_ERR_DEVICE;
   }
   if (const char* e = getenv("SMR_SEED_EXACT")) c->seed_exact = atoi(e) != 0;
   if (const char* e = getenv("SMR_CAND_BLOOM")) { uint32_t b = 64; while (b < CAND_BLOOM_WORDS && b < (uint32_t)atoi(e)) b <<= 1; c->cand_bloom = b; }      // measurement aid
   if (const char* e = getenv("SMR_PG_CAND_CAP")) c->ccap = std::min<uint32_t>(PG_CAND_CAP_MAX, std::max<uint32_t>(4u, (uint32_t)atoi(e)));      // test aid: a small candidate pool
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
-  if (hipMalloc((void**)&c->b->d_ctr, C_TOTAL * 8) != hipSuccess) { if (err && errcap) snprintf(err, errcap, "hipMalloc failed"); delete c; return SMR_ERR_DEVICE; }
+  if (c->b->d_ctr.alloc(c, C_TOTAL) != SMR_OK) { if (err && errcap) snprintf(err, errcap, "hipMalloc failed"); delete c; return SMR_ERR_DEVICE; }
   (void)hipMemset(c->b->d_ctr, 0, C_TOTAL * 8);
   c->b->used = true;
   if (c->sw_mode >= 1) {
@@ -362,33 +381,6 @@ extern "C" void smr_destroy(smr_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
-  for (int s = 0; s < 64; s++) if (c->idx[s].used) smr_index_unload(c, s);
-  for (int k = 0; k < SMR_MAX_BATCHES; k++) {
-    Batch& B = c->bt[k];
-    dev_free(&B.d_words); dev_free(&B.d_rec_off); dev_free(&B.d_len);
-    dev_free(&B.d_saved); dev_free(&B.d_work); dev_free(&B.d_rw); dev_free(&B.d_marks); dev_free(&B.d_saved_aln); dev_free(&B.d_work_aln); dev_free(&B.d_ctr);
-    dev_free(&B.d_cigar); dev_free(&B.d_idcov);
-  }
-  dev_free(&c->d_bound); dev_free(&c->d_rdq); dev_free(&c->d_mrec); dev_free(&c->d_mpool);
-  for (int q = 0; q < 2; q++) { dev_free(&c->d_wlist[q]); dev_free(&c->d_wstate[q]); dev_free(&c->d_wtask[q]); dev_free(&c->d_wres[q]); }
-  dev_free(&c->d_wstat);
-  dev_free(&c->d_wtidx); dev_free(&c->d_wslow); dev_free(&c->d_wctr); dev_free(&c->d_croute);
-  dev_free(&c->sb.chist); dev_free(&c->sb.cbase); dev_free(&c->sb.rows); dev_free(&c->sb.bcnt); dev_free(&c->sb.tmp); dev_free(&c->sb.mid);
-  dev_free(&c->sb.srt); dev_free(&c->sb.hpre); dev_free(&c->sb.hlist); dev_free(&c->sb.hh); dev_free(&c->sb.pieces); dev_free(&c->sb.redo); dev_free(&c->sb.sn); dev_free(&c->sb.wbin); dev_free(&c->sb.emap); dev_free(&c->sb.zbits); dev_free(&c->sb.gflag);
-  for (int d = 0; d < 2; d++) { dev_free(&c->sb.wseg[d]); dev_free(&c->sb.fbits[d]); }
-  dev_free(&c->d_pool); dev_free(&c->d_tuples); dev_free(&c->d_tuples2); dev_free(&c->d_stab); dev_free(&c->d_keys); dev_free(&c->d_pairs); dev_free(&c->d_lis); dev_free(&c->d_hits);
-  dev_free(&c->d_tasks); dev_free(&c->d_trflags); dev_free(&c->d_trrows); dev_free(&c->d_sw_scr);
-  if (c->shared) {
-    for (int s = 0; s < 2; s++) for (int p = 0; p < 3; p++) { SharedSet& T = c->shared->set[s][p]; dev_free(&T.srt); dev_free(&T.wbin); dev_free(&T.cbase); dev_free(&T.sn); }
-    dev_free(&c->shared->abits);
-    delete c->shared;
-  }
-  for (auto& m : c->events) (void)hipEventDestroy(m.e);
-  for (auto& e : c->ev_pool) (void)hipEventDestroy(e);
-  dev_free(&c->d_ctr_snap); dev_free(&c->d_fidx); dev_free(&c->d_fstate); dev_free(&c->d_faln); dev_free(&c->d_fidcov);
-  dev_free(&c->d_xbytes); dev_free(&c->d_xoff); dev_free(&c->d_xpart);
-  (void)hipStreamDestroy(c->upload_stream);
-  (void)hipStreamDestroy(c->stream);
   delete c;
 }
 
@@ -418,18 +410,18 @@ int build_pigeonhole_device(smr_ctx* c, DevIndex& d, uint32_t nk, uint32_t pw) {
   const uint32_t nb = 2 * nk;
   IB_GET(cnt, uint32_t, nb); IB_GET(eoff, uint32_t, nb); IB_GET(words, smr::u64, nb); IB_GET(woff, smr::u64, nb); IB_GET(derr, uint32_t, 1);
   HIPCHK(c, hipMemsetAsync(derr, 0, 4, c->stream));
-  hipLaunchKernelGGL(smr::k_pgb_sizes, dim3((nb + 255) / 256), dim3(256), 0, c->stream, (const Lookup*)d.lookup, (const uint32_t*)d.trie, nk, pw, cnt, words);
+  launch(c, smr::k_pgb_sizes, dim3((nb + 255) / 256), dim3(256), 0, (const Lookup*)d.lookup, (const uint32_t*)d.trie, nk, pw, cnt, words);
   smr::u64 W = 0;
   int rc = dev_scan<smr::u64>(c, pool, words, woff, nb, &W); if (rc) return rc;
   if (W / 3 > 0xFFFFFFF0ull || W / 4 > 0xFFFFFFF0ull) { set_err(c, "pigeonhole arena exceeds 2^34 words"); return SMR_ERR_CAPACITY; }
   uint32_t E = 0;
   if ((rc = dev_scan<uint32_t>(c, pool, cnt, eoff, nb, &E))) return rc;
-  if ((rc = dev_alloc(c, &d.pg, (size_t)W + 4))) return rc;
-  if ((rc = dev_alloc(c, &d.root3, (size_t)2 * nb))) return rc;
+  if ((rc = d.pg.alloc(c, (size_t)W + 4))) return rc;
+  if ((rc = d.root3.alloc(c, (size_t)2 * nb))) return rc;
   HIPCHK(c, hipMemsetAsync(d.pg + W, 0, 16, c->stream));                 // one block of slack: a 16-byte read at the last word stays inside
   IB_GET(estr, uint32_t, E); IB_GET(eid, uint32_t, E); IB_GET(eblk, uint32_t, E);
   IB_GET(k0, smr::u64, E); IB_GET(k1, smr::u64, E); IB_GET(v0, uint32_t, E); IB_GET(v1, uint32_t, E);
-  hipLaunchKernelGGL(smr::k_pgb_collect, dim3((nb + 255) / 256), dim3(256), 0, c->stream, (const Lookup*)d.lookup, (const uint32_t*)d.trie, nk, pw,
+  launch(c, smr::k_pgb_collect, dim3((nb + 255) / 256), dim3(256), 0, (const Lookup*)d.lookup, (const uint32_t*)d.trie, nk, pw,
                      (const uint32_t*)cnt, (const uint32_t*)eoff, (const smr::u64*)woff, d.root3, d.pg, estr, eid, eblk, derr, (const uint32_t*)d.pos_off);
   uint32_t herr = 0;                                       // (a block k_pgb_collect refused has no entries written: nothing below may run on them)
   HIPCHK(c, hipMemcpyAsync(&herr, derr, 4, hipMemcpyDeviceToHost, c->stream));
@@ -440,12 +432,12 @@ int build_pigeonhole_device(smr_ctx* c, DevIndex& d, uint32_t nk, uint32_t pw) {
   for (int order = 0; order < 2 && E; order++) {
     const uint32_t kbits = order == 0 ? 2 * (pw + 1) : 2 * (pw - pw / 2);
     smr::u64 *ka = k0, *kb = k1; uint32_t *va = v0, *vb = v1;
-    if (order == 0) hipLaunchKernelGGL(smr::k_pgb_keys<0>, dim3(gE), dim3(256), 0, c->stream, (const uint32_t*)estr, (const uint32_t*)eblk, (smr::u64)E, pw, kbits, ka, va);
-    else hipLaunchKernelGGL(smr::k_pgb_keys<1>, dim3(gE), dim3(256), 0, c->stream, (const uint32_t*)estr, (const uint32_t*)eblk, (smr::u64)E, pw, kbits, ka, va);
+    if (order == 0) launch(c, smr::k_pgb_keys<0>, dim3(gE), dim3(256), 0, (const uint32_t*)estr, (const uint32_t*)eblk, (smr::u64)E, pw, kbits, ka, va);
+    else launch(c, smr::k_pgb_keys<1>, dim3(gE), dim3(256), 0, (const uint32_t*)estr, (const uint32_t*)eblk, (smr::u64)E, pw, kbits, ka, va);
     if ((rc = dev_radix_sort(c, pool, ka, kb, va, vb, E, 0, (int)kbits + blockbits))) return rc;
-    if (order == 0) hipLaunchKernelGGL(smr::k_pgb_emit<0>, dim3(gE), dim3(256), 0, c->stream, (const smr::u64*)ka, (const uint32_t*)va, (smr::u64)E, pw, kbits,
+    if (order == 0) launch(c, smr::k_pgb_emit<0>, dim3(gE), dim3(256), 0, (const smr::u64*)ka, (const uint32_t*)va, (smr::u64)E, pw, kbits,
                                        (const uint32_t*)estr, (const uint32_t*)eid, (const uint32_t*)eoff, (const uint32_t*)d.root3, d.pg);
-    else hipLaunchKernelGGL(smr::k_pgb_emit<1>, dim3(gE), dim3(256), 0, c->stream, (const smr::u64*)ka, (const uint32_t*)va, (smr::u64)E, pw, kbits,
+    else launch(c, smr::k_pgb_emit<1>, dim3(gE), dim3(256), 0, (const smr::u64*)ka, (const uint32_t*)va, (smr::u64)E, pw, kbits,
                             (const uint32_t*)estr, (const uint32_t*)eid, (const uint32_t*)eoff, (const uint32_t*)d.root3, d.pg);
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -463,24 +455,23 @@ extern "C" int smr_index_upload(smr_ctx* c, const smr_index* ix, int slot) {
   d.lnwin = ix->lnwin; d.n_refs = ix->n_refs(); d.n_ids = ix->n_ids(); d.trie_words = ix->trie.size(); d.n_pos = ix->pos_arr.size() / 2; d.ref_bytes = ix->ref_seq.size();
   int rc;
   smr_build_lkc(*const_cast<smr_index*>(ix));              // (cached in the smr_index under its mutex: concurrent uploads of one host index are safe)
-  if ((rc = dev_alloc(c, &d.lkc, ix->lkc.size()))) return rc;
+  if ((rc = d.lkc.alloc(c, ix->lkc.size()))) return rc;
   HIPCHK(c, hipMemcpyAsync(d.lkc, ix->lkc.data(), ix->lkc.size() * 4, hipMemcpyHostToDevice, c->stream));
-  if ((rc = dev_alloc(c, &d.lookup, ix->lookup.size()))) return rc;
-  if ((rc = dev_alloc(c, &d.trie, ix->trie.size()))) return rc;
+  if ((rc = d.lookup.alloc(c, ix->lookup.size()))) return rc;
+  if ((rc = d.trie.alloc(c, ix->trie.size()))) return rc;
   HIPCHK(c, hipMemcpyAsync(d.lookup, ix->lookup.data(), ix->lookup.size() * sizeof(Lookup), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d.trie, ix->trie.data(), ix->trie.size() * 4, hipMemcpyHostToDevice, c->stream));
   // the position lists: pos_off (which the layout build below and the DFS kernel translate ids with) and pos2 = {header, positions} per seed (k_pos2_build)
   if ((uint64_t)ix->pos_arr.size() / 2 + ix->n_ids() >= 0x7FFFFFF0ull) { set_err(c, "index part limit: positions + distinct seeds < 2^31"); return SMR_ERR_CAPACITY; }
-  if ((rc = dev_alloc(c, &d.pos_off, ix->pos_off.size()))) return rc;
+  if ((rc = d.pos_off.alloc(c, ix->pos_off.size()))) return rc;
   HIPCHK(c, hipMemcpyAsync(d.pos_off, ix->pos_off.data(), ix->pos_off.size() * 4, hipMemcpyHostToDevice, c->stream));
   {
-    uint2* raw = nullptr;
-    if ((rc = dev_alloc(c, &raw, ix->pos_arr.size() / 2))) return rc;
+    DevBuf<uint2> raw;                                      // (gone at the end of this block, however it is left)
+    if ((rc = raw.alloc(c, ix->pos_arr.size() / 2))) return rc;
     HIPCHK(c, hipMemcpyAsync(raw, ix->pos_arr.data(), ix->pos_arr.size() * 4, hipMemcpyHostToDevice, c->stream));
-    if ((rc = dev_alloc(c, &d.pos_arr, ix->pos_arr.size() / 2 + (size_t)d.n_ids + 1))) { dev_free(&raw); return rc; }
-    if (d.n_ids) hipLaunchKernelGGL(k_pos2_build, dim3((d.n_ids + 255u) / 256u), dim3(256), 0, c->stream, (const uint32_t*)d.pos_off, (const uint2*)raw, d.n_ids, d.pos_arr);
+    if ((rc = d.pos_arr.alloc(c, ix->pos_arr.size() / 2 + (size_t)d.n_ids + 1))) return rc;
+    if (d.n_ids) launch(c, k_pos2_build, dim3((d.n_ids + 255u) / 256u), dim3(256), 0, d.pos_off, raw, d.n_ids, d.pos_arr);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    dev_free(&raw);
   }
   // The pigeonhole layout of the tries (what k_seed_pg reads) is built on the device from the arena just uploaded (smr_pgbuild.hpp).  An index
   // that already carries the host-built layout (smr_index_selfcheck, SMR_PG_HOST=1) is uploaded as it is.
@@ -489,16 +480,16 @@ extern "C" int smr_index_upload(smr_ctx* c, const smr_index* ix, int slot) {
   if (host_pg) {
     std::string why;
     if (!smr_build_pigeonhole(*const_cast<smr_index*>(ix), 0, why)) { set_err(c, why); return SMR_ERR_CAPACITY; }
-    if ((rc = dev_alloc(c, &d.pg, ix->pg.size()))) return rc;
-    if ((rc = dev_alloc(c, &d.root3, ix->root3.size()))) return rc;
+    if ((rc = d.pg.alloc(c, ix->pg.size()))) return rc;
+    if ((rc = d.root3.alloc(c, ix->root3.size()))) return rc;
     HIPCHK(c, hipMemcpyAsync(d.pg, ix->pg.data(), ix->pg.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d.root3, ix->root3.data(), ix->root3.size() * 4, hipMemcpyHostToDevice, c->stream));
     d.pg_words = ix->pg.size() >= 4 ? ix->pg.size() - 4 : 0;
   } else if ((rc = build_pigeonhole_device(c, d, (uint32_t)ix->lookup.size(), ix->lnwin / 2))) return rc;
   if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: index part: tries %.2f GB, pigeonhole arena %.2f GB (%s), positions %.2f GB\n", ix->trie.size() * 4e-9, d.pg_words * 4e-9,
                                      host_pg ? "host-built" : "built on the device", ix->pos_arr.size() * 4e-9);
-  if ((rc = dev_alloc(c, &d.ref_seq, ix->ref_seq.size() + 64))) return rc;
-  if ((rc = dev_alloc(c, &d.ref_off, ix->ref_off.size()))) return rc;
+  if ((rc = d.ref_seq.alloc(c, ix->ref_seq.size() + 64))) return rc;
+  if ((rc = d.ref_off.alloc(c, ix->ref_off.size()))) return rc;
   HIPCHK(c, hipMemcpyAsync(d.ref_seq, ix->ref_seq.data(), ix->ref_seq.size(), hipMemcpyHostToDevice, c->stream));
   d.ref_any_n = (!ix->ref_seq.empty() && memchr(ix->ref_seq.data(), 4, ix->ref_seq.size())) ? 1u : 0u;      // (k_sw16 asks each window for its ambiguous letters only then)
   HIPCHK(c, hipMemcpyAsync(d.ref_off, ix->ref_off.data(), ix->ref_off.size() * 8, hipMemcpyHostToDevice, c->stream));
@@ -525,9 +516,7 @@ extern "C" int smr_index_check_device(smr_ctx* c, int slot, smr_index* ix) {
 
 extern "C" int smr_index_unload(smr_ctx* c, int slot) {
   if (!c || slot < 0 || slot >= 64) return SMR_ERR_ARG;
-  DevIndex& d = c->idx[slot];
-  dev_free(&d.lookup); dev_free(&d.trie); dev_free(&d.pg); dev_free(&d.root3); dev_free(&d.lkc); dev_free(&d.pos_off); dev_free(&d.pos_arr); dev_free(&d.ref_seq); dev_free(&d.ref_off);
-  d = DevIndex();
+  c->idx[slot] = DevIndex();
   return SMR_OK;
 }
 
@@ -536,7 +525,7 @@ extern "C" int smr_batch_select(smr_ctx* c, int batch) {
   HIPCHK(c, hipSetDevice(c->device));
   Batch& B = c->bt[batch];
   if (!B.d_ctr) {
-    HIPCHK(c, hipMalloc((void**)&B.d_ctr, C_TOTAL * 8));
+    int rc = B.d_ctr.alloc(c, C_TOTAL); if (rc) return rc;
     HIPCHK(c, hipMemset(B.d_ctr, 0, C_TOTAL * 8));
   }
   B.used = true;
@@ -561,39 +550,23 @@ int reset_batch(smr_ctx* c, Batch& B, hipStream_t st) {
   HIPCHK(c, hipMemsetAsync(B.d_ctr + C_ERR_HITCAP, 0, (size_t)(C_SW_SPEC - C_ERR_HITCAP) * 8, st));
   HIPCHK(c, hipMemsetAsync(B.d_ctr + C_PCUR, 0, (size_t)C_NSHARD * C_PCUR_STRIDE * 8, st));
   HIPCHK(c, hipMemsetAsync(B.d_ctr + C_IDCOV, 0, 4 * 8, st));
-  if (B.d_idcov) HIPCHK(c, hipMemsetAsync(B.d_idcov, 0, std::min(B.cap_idcov, (size_t)B.n) * 16, st));
+  if (B.d_idcov) HIPCHK(c, hipMemsetAsync(B.d_idcov, 0, std::min(B.d_idcov.cap() / 4, (size_t)B.n) * 16, st));
   B.idcov_ran = false;
   HIPCHK(c, hipStreamSynchronize(st));
   B.fetched = false;
-  return SMR_OK;
-}
-template <class T> int grow(smr_ctx* c, T** p, size_t& cap, size_t need) {        // grow-only device array
-  if (*p && cap >= need) return SMR_OK;
-  int rc = dev_alloc(c, p, need); if (rc) return rc;
-  cap = need;
   return SMR_OK;
 }
 // the packed reads of r into batch B (+ its per-read state, reset), all work on stream st; touches nothing but B
 int upload_into(smr_ctx* c, Batch& B, const smr_reads* r, uint32_t max_aln, hipStream_t st) {
   if (max_aln == 0) max_aln = 1;
   int rc;
-  if (!B.d_ctr) { HIPCHK(c, hipMalloc((void**)&B.d_ctr, C_TOTAL * 8)); HIPCHK(c, hipMemsetAsync(B.d_ctr, 0, C_TOTAL * 8, st)); }
+  if (!B.d_ctr) { if ((rc = B.d_ctr.alloc(c, C_TOTAL))) return rc; HIPCHK(c, hipMemsetAsync(B.d_ctr, 0, C_TOTAL * 8, st)); }
   const size_t nw = r->words.size() + 4, nr = (size_t)r->n + 1, na = std::max<size_t>((size_t)r->n * max_aln, 1);     // + slack: window extraction reads 2 words ahead
-  if (B.cap_words < nw) { if ((rc = dev_alloc(c, &B.d_words, nw))) return rc; B.cap_words = nw; }
-  if (B.cap_reads < nr) {
-    if ((rc = dev_alloc(c, &B.d_rec_off, nr))) return rc;
-    if ((rc = dev_alloc(c, &B.d_len, nr))) return rc;
-    if ((rc = dev_alloc(c, &B.d_saved, nr))) return rc;
-    if ((rc = dev_alloc(c, &B.d_work, nr))) return rc;
-    if ((rc = dev_alloc(c, &B.d_rw, nr))) return rc;
-    if ((rc = dev_alloc(c, &B.d_marks, nr))) return rc;
-    B.cap_reads = nr;
-  }
-  if (B.cap_aln < na) {
-    if ((rc = dev_alloc(c, &B.d_saved_aln, na))) return rc;
-    if ((rc = dev_alloc(c, &B.d_work_aln, na))) return rc;
-    B.cap_aln = na;
-  }
+  if ((rc = B.d_words.reserve(c, nw))) return rc;
+  // (the six per-read arrays are reserved for the same number in the same calls: they grow together)
+  if ((rc = B.d_rec_off.reserve(c, nr)) || (rc = B.d_len.reserve(c, nr)) || (rc = B.d_saved.reserve(c, nr)) || (rc = B.d_work.reserve(c, nr)) || (rc = B.d_rw.reserve(c, nr)) ||
+      (rc = B.d_marks.reserve(c, nr))) return rc;
+  if ((rc = B.d_saved_aln.reserve(c, na)) || (rc = B.d_work_aln.reserve(c, na))) return rc;
   B.n = r->n; B.max_len = r->max_len; B.slots = max_aln; B.used = true;
   for (int k = 0; k < 7; k++) B.min_ge[k] = ~0u;
   B.min_ge_known = false;
@@ -603,8 +576,8 @@ int upload_into(smr_ctx* c, Batch& B, const smr_reads* r, uint32_t max_aln, hipS
   if (r->n) HIPCHK(c, hipMemcpyAsync(B.d_len, r->len.data(), r->len.size() * 4, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemsetAsync(B.d_rw, 0, (size_t)B.n * sizeof(RWork), st));
   HIPCHK(c, hipMemsetAsync(B.d_work, 0, (size_t)B.n * sizeof(RState), st));
-  B.cigar_words = 0; dev_free(&B.d_cigar);
-  if (B.cap_idcov < (size_t)B.n) { dev_free(&B.d_idcov); B.cap_idcov = 0; }       // (the next smr_idcov_part allocates it for this batch size)
+  B.cigar_words = 0; B.d_cigar.release();
+  if (B.d_idcov.cap() < (size_t)B.n * 4) B.d_idcov.release();                     // (the next smr_idcov_part allocates it for this batch size)
   return reset_batch(c, B, st);
 }
 }  // namespace
@@ -645,14 +618,14 @@ int ensure_pool(smr_ctx* c) {          // seed-hit pool: scratch shared by all b
   uint64_t want_pool = std::max<uint64_t>((uint64_t)c->b->n * 64 + (1u << 20), 1u << 22);
   if (const char* e = getenv("SMR_SEED_POOL_WORDS"))          // test aid: start the pool small (regrow) or large (offsets above 2^30)
     want_pool = std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 0), C_NSHARD), 0x7FFFFFF0ull);
-  if (c->pool_words < want_pool) { int rc = dev_alloc(c, &c->d_pool, want_pool); if (rc) return rc; c->pool_words = want_pool; }
+  if (c->pool_words < want_pool) { int rc = c->d_pool.alloc(c, want_pool); if (rc) return rc; c->pool_words = want_pool; }
   return SMR_OK;
 }
 
 int grow_pool(smr_ctx* c) {            // a seed kernel found its shard of the pool full (C_ERR_POOL): twice the words, the attempt is redone
   const uint64_t w = c->pool_words * 2;
   if (w > 0x7FFFFFF0ull) { set_err(c, "seed-hit pool exceeds 8 GiB"); return SMR_ERR_CAPACITY; }
-  int rc = dev_alloc(c, &c->d_pool, w); if (rc) return rc;
+  int rc = c->d_pool.alloc(c, w); if (rc) return rc;
   c->pool_words = w; c->n_pool_grown++;
   return SMR_OK;
 }
@@ -665,6 +638,106 @@ __global__ void k_ctr_begin(unsigned long long* __restrict__ ctr, const unsigned
   }
 }
 
+namespace {
+// --edges N% of a read of fewer than 100 / N letters is 0, and 0 is not "no margin" in the reference: `tail > edges - 1` is an unsigned compare
+// (alignment.cpp:320,345), so such a read is aligned against the whole rest of its reference sequence.  Not built here (the windows of the
+// Smith-Waterman kernels are sized read + 2 x edges): said before anything runs, not as a capacity error of some kernel.
+int refuse_percent_edges(smr_ctx* c, const DevIndex& di, const smr_params* p) {
+  if (!p->is_as_percent) return SMR_OK;
+  Batch& B = *c->b;
+  if (!B.min_ge_known) {                                      // the shortest searchable read of the batch, per seed length: from the lengths on the device, once per batch
+    std::vector<uint32_t> len(B.n);
+    if (B.n) { HIPCHK(c, hipMemcpyAsync(len.data(), B.d_len, (size_t)B.n * 4, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); }
+    for (uint32_t l : len) for (int k = 0; k < 7; k++) if (l >= 8u + 2u * (uint32_t)k && l < B.min_ge[k]) B.min_ge[k] = l;
+    B.min_ge_known = true;
+  }
+  const uint32_t lmin = B.min_ge[(std::min<uint32_t>(std::max<uint32_t>(di.lnwin, 8u), 20u) - 8u) / 2u];
+  if (lmin != ~0u && (uint32_t)((p->edges / 100.0) * (double)lmin) == 0) {
+    set_err(c, "edges as a percentage: the batch has a searchable read so short that the percentage rounds to 0 letters; the reference then aligns it against the whole rest of the reference sequence (alignment.cpp:320,345), which is not supported -- use an absolute --edges");
+    return SMR_ERR_ARG;
+  }
+  return SMR_OK;
+}
+
+// the striped slow path: per block of k_chain / k_begins five arrays of 16 x ceil(len / 8) uint16 (smr_sw_striped.hpp)
+int ensure_striped_scratch(smr_ctx* c, DParams& P, const smr_params* p) {
+  const uint32_t stride = 5u * 16u * ((c->b->max_len + 7u) / 8u + 1u);
+  const size_t need = (size_t)std::max<uint32_t>(chain_blocks(c), (uint32_t)c->n_cu * 8u) * stride;
+  if (c->d_sw_scr.cap() < need || c->sw_scr_stride < stride) { int rc = c->d_sw_scr.alloc(c, need); if (rc) return rc; c->sw_scr_stride = stride; }
+  P.sw_scratch = c->d_sw_scr; P.sw_scratch_stride = c->sw_scr_stride;
+  if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: scoring scheme %d/%d/%d (N %d): %s -- Smith-Waterman through the slow path that reproduces ssw.c's stripe geometry\n",
+                                     p->match, p->mismatch, p->gap_open, p->score_N, scheme_unsupported(p->mismatch, p->score_N, p->gap_open, p->gap_ext));
+  return SMR_OK;
+}
+
+// one attempt at the part: the counters back to the snapshot, then the seed and the candidate stage of every (strand, pass)
+int run_attempt(smr_ctx* c, const DevIndex& di, const DParams& P, const smr_params* p, const AlignPlan& plan) {
+  Batch& B = *c->b;
+  int rc = ensure_chain_scratch(c); if (rc) return rc;
+  c->cinfo_attempts++;
+  if (c->cinfo_on) {                                          // the route bytes start over with every attempt: they describe the one that is kept
+    if ((rc = c->d_croute.reserve(c, B.n))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_croute, 0, (size_t)B.n, c->stream));
+    c->croute_n = B.n;
+  }
+  c->wstat_n = 0;
+  const uint32_t tb = 256, nb = (B.n + tb - 1) / tb;
+  const int single = (p->is_forward != 0) ^ (p->is_reverse != 0);
+  // restore counters (retry) and clear the per-part ones (processor.cpp:230 resets num_short per part)
+  launch(c, k_ctr_begin, dim3(1), dim3(256), 0, B.d_ctr, c->d_ctr_snap);
+  launch(c, k_begin_part, dim3(nb), dim3(tb), 0, dreads(c), P, B.d_saved, B.d_saved_aln, B.d_work, B.d_work_aln, B.d_rw, B.d_ctr);
+  for (int count = 0; count < (single ? 1 : 2); count++) {
+    launch(c, k_begin_strand, dim3(nb), dim3(tb), 0, B.n, P, count, B.d_work, B.d_rw);
+    HIPCHK(c, hipMemsetAsync(&B.d_ctr[C_PCUR], 0, C_NSHARD * C_PCUR_STRIDE * 8, c->stream));
+    for (int pass = 0; pass < 3; pass++) {
+      if (pass > 0 && P.skip[pass] == P.skip[pass - 1]) continue;     // equal strides are skipped (paralleltraversal.cpp:269-272)
+      if ((rc = launch_seed(c, di, P, pass, !p->is_last_index_part, ((single && p->is_reverse) || count == 1) ? 1 : 0))) return rc;
+      if ((rc = launch_chain(c, di, P, plan, pass, single || count == 1))) return rc;
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  return SMR_OK;
+}
+
+// The counters h of a finished attempt: what overflowed is enlarged and the attempt has to be redone (retry); what no retry cures is an error.
+int judge_attempt(smr_ctx* c, const DParams& P, const std::vector<unsigned long long>& h, bool& retry) {
+  int rc;
+  retry = false;
+  if (h[C_ERR_HITCAP]) { c->cinfo_retry[0]++; if (!grow_hcap(c, P.partialwin)) return SMR_ERR_CAPACITY; retry = true; }
+  if (h[C_ERR_POOL]) { c->cinfo_retry[1]++; if ((rc = grow_pool(c))) return rc; retry = true; }
+  if (h[C_ERR_PAIRS]) {                                       // (ensure_chain_scratch makes the released arrays again, for the new capacities)
+    c->cinfo_retry[2]++;
+    c->pairs_cap *= 4; c->hits_cap *= 4; c->d_pairs.release(); c->d_lis.release(); c->d_hits.release(); c->d_tuples.release(); c->d_tuples2.release();
+    if (c->pairs_cap > (1u << 22)) { set_err(c, "per-read candidate scratch exceeds capacity"); return SMR_ERR_CAPACITY; }
+    retry = true;
+  }
+  if (h[C_ERR_REDO]) { c->cinfo_retry[3]++; c->seed_exact = 1; retry = true; }     // too many overflowing waves for the redo list: use the DFS kernel throughout
+  {
+    // k_seed_pg's candidate pool: when more than 1/64 of this part's waves overflowed it (they were searched again by the DFS kernel:
+    // right, but slow), the next launches get twice the pool
+    Batch& B = *c->b;
+    if (h[C_SEED_REDO] < B.redo_seen || h[C_WINDOWS] < B.win_seen) B.redo_seen = B.win_seen = 0;       // counters were reset
+    const unsigned long long redo = h[C_SEED_REDO] - B.redo_seen, waves = (h[C_WINDOWS] - B.win_seen) / 32;   // forward + reverse search per window
+    B.redo_seen = h[C_SEED_REDO]; B.win_seen = h[C_WINDOWS];
+    if (!retry && redo * 64 > waves && c->ccap < PG_CAND_CAP_MAX) {
+      c->ccap *= 2;
+      if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: %llu of ~%llu seed-search waves overflowed their candidate pool: %u records per wave from now on\n", redo, waves, c->ccap);
+    }
+  }
+  if (h[C_ERR_SCAP]) {
+    // a read shares seeds with more references than the LDS table of its wave holds (384): from now on such reads build their set in a
+    // per-block table in global memory; the candidate keys need room for as many members
+    if (c->chain_ext) { set_err(c, "more than 49152 references share seeds with one read (candidate set capacity)"); return SMR_ERR_CAPACITY; }
+    c->chain_ext = true; retry = true; c->cinfo_retry[4]++;
+    if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: a read shares seeds with more references than its wave's LDS table holds: per-block global candidate tables enabled (%.1f GB)\n",
+                                       (double)c->chain_blocks * (4.0 * CH_EXT_CAP * 4 + (double)c->pairs_cap * 8 + (double)CH_EXT_CAP * 8) / 1e9);
+    if (c->keys_cap < CH_EXT_CAP) { c->d_keys.release(); c->keys_cap = 0; c->keys_need = CH_EXT_CAP; }
+  }
+  if (h[C_ERR_SLOTS]) { set_err(c, "a read produced more alignments than max_alignments_per_read (smr_reads_upload)"); return SMR_ERR_CAPACITY; }
+  return SMR_OK;
+}
+}  // namespace
+
 extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
   if (!c || slot < 0 || slot >= 64) return SMR_ERR_ARG;
   if (!c->idx[slot].used || !c->b->d_saved) { set_err(c, "index slot empty or no reads uploaded"); return SMR_ERR_STATE; }
@@ -674,165 +747,36 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
   const DevIndex& di = c->idx[slot];
   if (di.lnwin < 8 || di.lnwin > 20) { set_err(c, "unsupported seed length"); return SMR_ERR_ARG; }
   DParams P = make_dparams(c, di, p);
-  // --edges N% of a read of fewer than 100 / N letters is 0, and 0 is not "no margin" in the reference: `tail > edges - 1` is an unsigned compare
-  // (alignment.cpp:320,345), so such a read is aligned against the whole rest of its reference sequence.  Not built here (the windows of the
-  // Smith-Waterman kernels are sized read + 2 x edges): said before anything runs, not as a capacity error of some kernel.
-  if (p->is_as_percent) {
-    if (!c->b->min_ge_known) {                                // the shortest searchable read of the batch, per seed length: from the lengths on the device, once per batch
-      std::vector<uint32_t> len(c->b->n);
-      if (c->b->n) { HIPCHK(c, hipMemcpyAsync(len.data(), c->b->d_len, (size_t)c->b->n * 4, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); }
-      for (uint32_t l : len) for (int k = 0; k < 7; k++) if (l >= 8u + 2u * (uint32_t)k && l < c->b->min_ge[k]) c->b->min_ge[k] = l;
-      c->b->min_ge_known = true;
-    }
-    const uint32_t lmin = c->b->min_ge[(std::min<uint32_t>(std::max<uint32_t>(di.lnwin, 8u), 20u) - 8u) / 2u];
-    if (lmin != ~0u && (uint32_t)((p->edges / 100.0) * (double)lmin) == 0) {
-      set_err(c, "edges as a percentage: the batch has a searchable read so short that the percentage rounds to 0 letters; the reference then aligns it against the whole rest of the reference sequence (alignment.cpp:320,345), which is not supported -- use an absolute --edges");
-      return SMR_ERR_ARG;
-    }
-  }
-  uint32_t ml, rf; size_t lds; chain_lds(c, P, ml, rf, lds);
-  if (lds > 150 * 1024) { set_err(c, "reads too long for this build of the SW kernel (LDS)"); return SMR_ERR_CAPACITY; }
+  if ((rc = refuse_percent_edges(c, di, p))) return rc;
+  const AlignPlan plan = align_plan(c, P);
+  if (plan.lds > 150 * 1024) { set_err(c, "reads too long for this build of the SW kernel (LDS)"); return SMR_ERR_CAPACITY; }
   c->b->last_num_alignments = p->num_alignments;
   c->b->fetched = false;
   ev_drop(c);
   if (c->b->n == 0) return SMR_OK;
   if ((rc = ensure_pool(c))) return rc;
-  if (P.sw_mode < 0) {
-    // the striped slow path: per block of k_chain / k_begins five arrays of 16 x ceil(len / 8) uint16 (smr_sw_striped.hpp)
-    if (c->chain_blocks == 0) c->chain_blocks = (uint32_t)c->n_cu * (getenv("SMR_CHAIN_WPC") ? atoi(getenv("SMR_CHAIN_WPC")) : 12);
-    const uint32_t stride = 5u * 16u * ((c->b->max_len + 7u) / 8u + 1u);
-    const size_t need = (size_t)std::max<uint32_t>(c->chain_blocks, (uint32_t)c->n_cu * 8u) * stride;
-    if (c->sw_scr_words < need || c->sw_scr_stride < stride) { if ((rc = dev_alloc(c, &c->d_sw_scr, need))) return rc; c->sw_scr_words = need; c->sw_scr_stride = stride; }
-    P.sw_scratch = c->d_sw_scr; P.sw_scratch_stride = c->sw_scr_stride;
-    if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: scoring scheme %d/%d/%d (N %d): %s -- Smith-Waterman through the slow path that reproduces ssw.c's stripe geometry\n",
-                                       p->match, p->mismatch, p->gap_open, p->score_N, scheme_unsupported(p->mismatch, p->score_N, p->gap_open, p->gap_ext));
-  }
+  if (plan.striped && (rc = ensure_striped_scratch(c, P, p))) return rc;
   std::vector<unsigned long long> h;
   // the counters as they stand now stay on the device; an attempt that has to be redone starts from them again (one read-back per attempt, none before)
   HIPCHK(c, hipMemcpyAsync(c->d_ctr_snap, c->b->d_ctr, C_TOTAL * 8, hipMemcpyDeviceToDevice, c->stream));
-  const uint32_t tb = 256, nb = (c->b->n + tb - 1) / tb;
-  const int single = (p->is_forward != 0) ^ (p->is_reverse != 0);
-  const int num_strands = single ? 1 : 2;
   c->cinfo_attempts = 0;
   for (int q = 0; q < 5; q++) c->cinfo_retry[q] = 0;
   for (int attempt = 0; attempt < 16; attempt++) {            // (the hit-list ladder of the DFS kernel alone has seven steps: grow_hcap)
-    if ((rc = ensure_chain_scratch(c, di))) return rc;
-    c->cinfo_attempts++;
-    if (c->cinfo_on) {                                        // the route bytes start over with every attempt: they describe the one that is kept
-      if (c->croute_cap < c->b->n) { if ((rc = dev_alloc(c, &c->d_croute, (size_t)c->b->n))) return rc; c->croute_cap = c->b->n; }
-      HIPCHK(c, hipMemsetAsync(c->d_croute, 0, (size_t)c->b->n, c->stream));
-      c->croute_n = c->b->n;
-    }
     const KpSave kp0 = kp_save(c);
-    c->wstat_n = 0;
-    // restore counters (retry) and clear the per-part ones (processor.cpp:230 resets num_short per part)
-    hipLaunchKernelGGL(k_ctr_begin, dim3(1), dim3(256), 0, c->stream, c->b->d_ctr, (const unsigned long long*)c->d_ctr_snap);
-    hipLaunchKernelGGL(k_begin_part, dim3(nb), dim3(tb), 0, c->stream, dreads(c), P, c->b->d_saved, c->b->d_saved_aln, c->b->d_work, c->b->d_work_aln, c->b->d_rw, c->b->d_ctr);
-    for (int count = 0; count < num_strands; count++) {
-      hipLaunchKernelGGL(k_begin_strand, dim3(nb), dim3(tb), 0, c->stream, c->b->n, P, count, c->b->d_work, c->b->d_rw);
-      HIPCHK(c, hipMemsetAsync(&c->b->d_ctr[C_PCUR], 0, C_NSHARD * C_PCUR_STRIDE * 8, c->stream));
-      for (int pass = 0; pass < 3; pass++) {
-        if (pass > 0 && P.skip[pass] == P.skip[pass - 1]) continue;     // equal strides are skipped (paralleltraversal.cpp:269-272)
-        if ((rc = launch_seed(c, di, P, pass, !p->is_last_index_part, ((single && p->is_reverse) || count == 1) ? 1 : 0))) return rc;
-        if ((rc = launch_chain(c, di, P, pass, single || count == 1))) return rc;
-      }
-    }
-    HIPCHK(c, hipGetLastError());
+    if ((rc = run_attempt(c, di, P, p, plan))) return rc;
     if ((rc = read_ctr(c, h))) return rc;
     ev_collect(c);
-    bool retry = false;
-    if (h[C_ERR_HITCAP]) { c->cinfo_retry[0]++; if (!grow_hcap(c, P.partialwin)) return SMR_ERR_CAPACITY; retry = true; }
-    if (h[C_ERR_POOL]) { c->cinfo_retry[1]++; if ((rc = grow_pool(c))) return rc; retry = true; }
-    if (h[C_ERR_PAIRS]) {
-      c->cinfo_retry[2]++;
-      c->pairs_cap *= 4; c->hits_cap *= 4; dev_free(&c->d_pairs); dev_free(&c->d_lis); dev_free(&c->d_hits); dev_free(&c->d_tuples); dev_free(&c->d_tuples2);
-      if (c->pairs_cap > (1u << 22)) { set_err(c, "per-read candidate scratch exceeds capacity"); return SMR_ERR_CAPACITY; }
-      retry = true;
-    }
-    if (h[C_ERR_REDO]) { c->cinfo_retry[3]++; c->seed_exact = 1; retry = true; }     // too many overflowing waves for the redo list: use the DFS kernel throughout
-    {
-      // k_seed_pg's candidate pool: when more than 1/64 of this part's waves overflowed it (they were searched again by the DFS kernel:
-      // right, but slow), the next launches get twice the pool
-      if (h[C_SEED_REDO] < c->b->redo_seen || h[C_WINDOWS] < c->b->win_seen) c->b->redo_seen = c->b->win_seen = 0;       // counters were reset
-      const unsigned long long redo = h[C_SEED_REDO] - c->b->redo_seen, waves = (h[C_WINDOWS] - c->b->win_seen) / 32;   // forward + reverse search per window
-      c->b->redo_seen = h[C_SEED_REDO]; c->b->win_seen = h[C_WINDOWS];
-      if (!retry && redo * 64 > waves && c->ccap < PG_CAND_CAP_MAX) {
-        c->ccap *= 2;
-        if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: %llu of ~%llu seed-search waves overflowed their candidate pool: %u records per wave from now on\n", redo, waves, c->ccap);
-      }
-    }
-    if (h[C_ERR_SCAP]) {
-      // a read shares seeds with more references than the LDS table of its wave holds (384): from now on such reads build their set in a
-      // per-block table in global memory; the candidate keys need room for as many members
-      if (c->chain_ext) { set_err(c, "more than 49152 references share seeds with one read (candidate set capacity)"); return SMR_ERR_CAPACITY; }
-      c->chain_ext = true; retry = true; c->cinfo_retry[4]++;
-      if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: a read shares seeds with more references than its wave's LDS table holds: per-block global candidate tables enabled (%.1f GB)\n",
-                                         (double)c->chain_blocks * (4.0 * CH_EXT_CAP * 4 + (double)c->pairs_cap * 8 + (double)CH_EXT_CAP * 8) / 1e9);
-      if (c->keys_cap < CH_EXT_CAP) { dev_free(&c->d_keys); c->keys_cap = 0; c->keys_need = CH_EXT_CAP; }
-    }
-    if (h[C_ERR_SLOTS]) { set_err(c, "a read produced more alignments than max_alignments_per_read (smr_reads_upload)"); return SMR_ERR_CAPACITY; }
-    if (retry) kp_restore(c, kp0);   // timings of a discarded attempt
-    if (!retry) {
-      if ((rc = adapt_walk_rounds(c))) return rc;
-      // the begin cells of the alignments that are still stored (k_chain records the accepted ones "begin pending"): four reverse passes per wave
-      {
-        const uint64_t ntot = (uint64_t)c->b->n * c->b->slots;
-        if (c->tasks_cap < ntot) { if ((rc = dev_alloc(c, &c->d_tasks, 2 * ntot))) return rc; c->tasks_cap = ntot; }
-        uint32_t ml, rf; size_t chain_bytes;
-        chain_lds(c, P, ml, rf, chain_bytes);
-        const int x4 = (P.sw_mode >= 1 && c->b->max_len <= SW_X4_MAX_ROWS &&
-                        (long long)c->b->max_len * P.match + 255 < 32768 && rf + 128 <= 8191 && P.gap_open + P.mismatch >= 0 && P.gap_open + P.score_N >= 0 &&
-                        P.match + P.gap_open <= 255 && P.score_N + P.gap_open <= 255) ? 1 : 0;
-        const size_t lds_b = x4 ? (size_t)4 * (ml + rf) : (c->b->max_len > SW_X4_MAX_ROWS ? 0 : (size_t)ml + rf);
-        const uint32_t bg_blocks = (uint32_t)c->n_cu * 8u;
-        if ((rc = ensure_bound(c, std::max(bg_blocks, c->chain_blocks), rf))) return rc;
-        if (lds_b > 64 * 1024 && lds_b > c->begins_lds_attr) {
-          HIPCHK(c, hipFuncSetAttribute((const void*)k_begins<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
-          HIPCHK(c, hipFuncSetAttribute((const void*)k_begins<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
-          HIPCHK(c, hipFuncSetAttribute((const void*)k_begins<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
-          HIPCHK(c, hipFuncSetAttribute((const void*)k_begins<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
-          c->begins_lds_attr = lds_b;
-        }
-        HIPCHK(c, hipMemsetAsync(&c->b->d_ctr[C_BEGIN_N], 0, 16, c->stream));       // C_BEGIN_N, C_BEGIN_NEXT
-        ev_mark(c, KP_BEGINS);
-        hipLaunchKernelGGL(k_begins_collect, dim3((uint32_t)((ntot + 1023) / 1024)), dim3(1024), 0, c->stream, c->b->n, c->b->slots, (const RState*)c->b->d_work, (const RWork*)c->b->d_rw,
-                           (const AlignRec*)c->b->d_work_aln, c->d_tasks, c->b->d_ctr);
-        const size_t task_cap = (size_t)c->walk_cap * c->walk_kcap;
-        if (x4 && c->walk_split && c->d_wtask[0] && c->d_wctr && ntot <= task_cap && !getenv("SMR_BEGINS_X4")) {
-          // sixteen per wave through k_sw16 (smr_walk.hpp): stage 0 = the end cells of the alignments stored end-pending, stage 1 = the begin cells of all
-          const uint32_t wmq = std::min<uint32_t>(c->b->max_len, WK_MAX_ROWS);
-          const int swr = wmq <= 104 ? 13 : wmq <= 152 ? 19 : wmq <= 208 ? 26 : 32;
-          const uint32_t sw_blocks = (uint32_t)c->n_cu * 4u * (uint32_t)SW16_WAVES(swr);
-          for (int stage = 0; stage < 2; stage++) {
-            HIPCHK(c, hipMemsetAsync(c->d_wctr, 0, (size_t)WC_STRIDE * 8, c->stream));
-            hipLaunchKernelGGL(k_begins_prep, dim3((uint32_t)c->n_cu * 2u), dim3(1024), 0, c->stream, dindex(di), c->b->slots, (const uint32_t*)c->d_tasks, (const unsigned long long*)&c->b->d_ctr[C_BEGIN_N],
-                               (const AlignRec*)c->b->d_work_aln, stage, c->d_wtask[0], c->d_wtidx, c->d_wctr);
-#define SW16_ARGS dreads(c), dindex(di), P, (const WTask*)c->d_wtask[0], (const uint32_t*)c->d_wtidx, (const uint32_t*)(c->d_wtidx + task_cap), (const unsigned long long*)c->d_wctr, c->d_wres[0]
-            if (swr == 13) hipLaunchKernelGGL(k_sw16<13>, dim3(sw_blocks), dim3(64), 0, c->stream, SW16_ARGS);
-            else if (swr == 19) hipLaunchKernelGGL(k_sw16<19>, dim3(sw_blocks), dim3(64), 0, c->stream, SW16_ARGS);
-            else if (swr == 26) hipLaunchKernelGGL(k_sw16<26>, dim3(sw_blocks), dim3(64), 0, c->stream, SW16_ARGS);
-            else hipLaunchKernelGGL(k_sw16<32>, dim3(sw_blocks), dim3(64), 0, c->stream, SW16_ARGS);
-#undef SW16_ARGS
-            c->sw16_launches[4 + (swr == 13 ? 0 : swr == 19 ? 1 : swr == 26 ? 2 : 3)]++;
-            hipLaunchKernelGGL(k_begins_apply, dim3((uint32_t)c->n_cu * 4u), dim3(256), 0, c->stream, (const uint32_t*)c->d_tasks, (const unsigned long long*)&c->b->d_ctr[C_BEGIN_N], c->b->d_work_aln, stage,
-                               (const WTask*)c->d_wtask[0], (const uint2*)c->d_wres[0], c->b->d_ctr);
-          }
-        } else if (P.sw_mode < 0) {
-          if (c->b->max_len > SW_X4_MAX_ROWS) hipLaunchKernelGGL((k_begins<true, true>), dim3(bg_blocks), dim3(64), lds_b, c->stream, dreads(c), dindex(di), P, (const uint32_t*)c->d_tasks, c->b->d_work_aln, c->b->d_ctr, ml, rf, x4, c->d_bound, c->d_rdq);
-          else hipLaunchKernelGGL((k_begins<false, true>), dim3(bg_blocks), dim3(64), lds_b, c->stream, dreads(c), dindex(di), P, (const uint32_t*)c->d_tasks, c->b->d_work_aln, c->b->d_ctr, ml, rf, x4, (int*)nullptr, (uint8_t*)nullptr);
-        } else if (c->b->max_len > SW_X4_MAX_ROWS)
-          hipLaunchKernelGGL(k_begins<true>, dim3(bg_blocks), dim3(64), lds_b, c->stream, dreads(c), dindex(di), P, (const uint32_t*)c->d_tasks, c->b->d_work_aln, c->b->d_ctr, ml, rf, x4, c->d_bound, c->d_rdq);
-        else
-          hipLaunchKernelGGL(k_begins<false>, dim3(bg_blocks), dim3(64), lds_b, c->stream, dreads(c), dindex(di), P, (const uint32_t*)c->d_tasks, c->b->d_work_aln, c->b->d_ctr, ml, rf, x4, (int*)nullptr, (uint8_t*)nullptr);
-        ev_stop(c);
-      }
-      // only a clean attempt is committed to the persistent per-read state (kvdb.put, processor.cpp:150-155)
-      hipLaunchKernelGGL(k_commit_part, dim3(nb), dim3(tb), 0, c->stream, c->b->n, P, c->b->d_saved, c->b->d_saved_aln, c->b->d_work, c->b->d_work_aln, c->b->d_rw);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      ev_collect(c);
-      return SMR_OK;
-    }
+    bool retry;
+    if ((rc = judge_attempt(c, P, h, retry))) return rc;
+    if (retry) { kp_restore(c, kp0); continue; }              // (the timings of a discarded attempt go with it)
+    if ((rc = adapt_walk_rounds(c))) return rc;
+    if ((rc = launch_begins(c, di, P, plan))) return rc;
+    // only a clean attempt is committed to the persistent per-read state (kvdb.put, processor.cpp:150-155)
+    launch(c, k_commit_part, dim3((c->b->n + 255u) / 256u), dim3(256), 0, c->b->n, P, c->b->d_saved, c->b->d_saved_aln, c->b->d_work, c->b->d_work_aln, c->b->d_rw);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ev_collect(c);
+    return SMR_OK;
   }
   set_err(c, "capacity retries exhausted");
   return SMR_ERR_CAPACITY;
@@ -867,7 +811,7 @@ __global__ void k_ctr_accumulate(const unsigned long long* __restrict__ ctr, uns
 extern "C" int smr_counters_accumulate(smr_ctx* c, void* d_acc, uint32_t n_u64) {
   if (!c || !d_acc || n_u64 > C_PER_DB + 64 + 4 || !c->b->d_ctr) return SMR_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  hipLaunchKernelGGL(k_ctr_accumulate, dim3((n_u64 + 127) / 128), dim3(128), 0, c->stream, (const unsigned long long*)c->b->d_ctr, (unsigned long long*)d_acc, n_u64);
+  launch(c, k_ctr_accumulate, dim3((n_u64 + 127) / 128), dim3(128), 0, (const unsigned long long*)c->b->d_ctr, (unsigned long long*)d_acc, n_u64);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SMR_OK;
@@ -893,14 +837,9 @@ extern "C" int smr_results_fetch(smr_ctx* c) {
   Batch& B = *c->b;
   int rc;
   const size_t need_r = std::max<size_t>(B.n, 1), need_a = std::max<size_t>((size_t)B.n * B.slots, 1);
-  if (c->fetch_cap_r < need_r) {
-    if ((rc = dev_alloc(c, &c->d_fidx, need_r))) return rc;
-    if ((rc = dev_alloc(c, &c->d_fstate, need_r))) return rc;
-    c->fetch_cap_r = need_r;
-  }
-  if (c->fetch_cap_a < need_a) { if ((rc = dev_alloc(c, &c->d_faln, need_a))) return rc; c->fetch_cap_a = need_a; }
+  if ((rc = c->d_fidx.reserve(c, need_r)) || (rc = c->d_fstate.reserve(c, need_r)) || (rc = c->d_faln.reserve(c, need_a))) return rc;
   HIPCHK(c, hipMemsetAsync(&B.d_ctr[C_FETCH_N], 0, 8, c->stream));
-  if (B.n) hipLaunchKernelGGL(k_results_compact, dim3((B.n + 1023) / 1024), dim3(1024), 0, c->stream, B.n, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln,
+  if (B.n) launch(c, k_results_compact, dim3((B.n + 1023) / 1024), dim3(1024), 0, B.n, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln,
                               c->d_fidx, c->d_fstate, c->d_faln, B.d_ctr);
   std::vector<unsigned long long> h;
   rc = read_ctr(c, h); if (rc) return rc;
@@ -916,9 +855,9 @@ extern "C" int smr_results_fetch(smr_ctx* c) {
   if (cw) HIPCHK(c, hipMemcpyAsync(B.h_cigar.data(), B.d_cigar, cw * 4, hipMemcpyDeviceToHost, c->stream));
   B.h_idcov.clear();
   if (B.d_idcov && nhit) {
-    if (c->fetch_cap_i < need_r) { if ((rc = dev_alloc(c, &c->d_fidcov, need_r * 4))) return rc; c->fetch_cap_i = need_r; }
+    if ((rc = c->d_fidcov.reserve(c, need_r * 4))) return rc;
     B.h_idcov.resize(nhit * 4);
-    hipLaunchKernelGGL(k_idcov_gather, dim3((uint32_t)((nhit + 255) / 256)), dim3(256), 0, c->stream, (const uint32_t*)c->d_fidx, (const unsigned long long*)&B.d_ctr[C_FETCH_N],
+    launch(c, k_idcov_gather, dim3((uint32_t)((nhit + 255) / 256)), dim3(256), 0, (const uint32_t*)c->d_fidx, (const unsigned long long*)&B.d_ctr[C_FETCH_N],
                        (const uint32_t*)B.d_idcov, c->d_fidcov);
     HIPCHK(c, hipMemcpyAsync(B.h_idcov.data(), c->d_fidcov, nhit * 16, hipMemcpyDeviceToHost, c->stream));
   }
@@ -1008,10 +947,10 @@ extern "C" int smr_seed_scan(smr_ctx* c, int slot, const smr_params* p, int stra
     HIPCHK(c, hipMemsetAsync(&c->b->d_ctr[C_HIT], 0, 8, c->stream));
     HIPCHK(c, hipMemsetAsync(&c->b->d_ctr[C_SHARDS], 0, C_SHARD_W * C_NSHARD * 8, c->stream));
     // fresh per-part/strand state: forward, or reverse-complement with ambiguous letters complemented (aval 0 -> 3)
-    hipLaunchKernelGGL(k_begin_part, dim3(nb), dim3(tb), 0, c->stream, dreads(c), P, c->b->d_saved, c->b->d_saved_aln, c->b->d_work, c->b->d_work_aln, c->b->d_rw, c->b->d_ctr);
+    launch(c, k_begin_part, dim3(nb), dim3(tb), 0, dreads(c), P, c->b->d_saved, c->b->d_saved_aln, c->b->d_work, c->b->d_work_aln, c->b->d_rw, c->b->d_ctr);
     DParams Q = P; Q.is_forward = 1; Q.is_reverse = 1;
-    hipLaunchKernelGGL(k_begin_strand, dim3(nb), dim3(tb), 0, c->stream, c->b->n, Q, strand ? 1 : 0, c->b->d_work, c->b->d_rw);
-    hipLaunchKernelGGL(k_force_pass, dim3(nb), dim3(tb), 0, c->stream, c->b->n, P, pass, c->b->d_len, c->b->d_rw);
+    launch(c, k_begin_strand, dim3(nb), dim3(tb), 0, c->b->n, Q, strand ? 1 : 0, c->b->d_work, c->b->d_rw);
+    launch(c, k_force_pass, dim3(nb), dim3(tb), 0, c->b->n, P, pass, c->b->d_len, c->b->d_rw);
     if ((rc = launch_seed(c, di, P, pass))) return rc;
     if ((rc = read_ctr(c, h))) return rc;
     ev_collect(c);

@@ -17,10 +17,55 @@ void chain_lds(const smr_ctx* c, const DParams& P, uint32_t& ml, uint32_t& rf, s
 // (1 byte each) -- only batches with reads of more than one strip
 int ensure_bound(smr_ctx* c, uint32_t blocks, uint32_t rf) {
   if (c->b->max_len <= SW_X4_MAX_ROWS) return SMR_OK;
-  const size_t need = (size_t)blocks * 2 * rf, need_rd = (size_t)blocks * ((c->b->max_len + 15) & ~15u);
-  if (c->bound_cap < need) { int rc = dev_alloc(c, &c->d_bound, need); if (rc) return rc; c->bound_cap = need; }
-  if (c->rdq_cap < need_rd) { int rc = dev_alloc(c, &c->d_rdq, need_rd); if (rc) return rc; c->rdq_cap = need_rd; }
-  return SMR_OK;
+  int rc = c->d_bound.reserve(c, (size_t)blocks * 2 * rf);
+  return rc ? rc : c->d_rdq.reserve(c, (size_t)blocks * ((c->b->max_len + 15) & ~15u));
+}
+
+// What one smr_align_part settles once for all its launches.  lng: the batch has reads of more than one Smith-Waterman strip (the short-read
+// instantiations carry none of their state).  striped: the slow path that reproduces ssw.c's stripe geometry (instantiations of its own); it
+// scores in k_chain and k_begins alone, so neither the candidate walk in rounds (split) nor four problems per wave (x4) go with it -- both
+// want the packed kernels.  rows: the k_sw16 instantiation for the batch's spans.
+struct AlignPlan { uint32_t ml, rf, rq; size_t lds; bool lng, striped, split, x4; int rows; };
+int sw16_rows(uint32_t max_len) {
+  const uint32_t wmq = std::min<uint32_t>(max_len, WK_MAX_ROWS);
+  return wmq <= 104 ? 13 : wmq <= 152 ? 19 : wmq <= 208 ? 26 : 32;
+}
+AlignPlan align_plan(const smr_ctx* c, const DParams& P) {
+  AlignPlan a;
+  chain_lds(c, P, a.ml, a.rf, a.rq, a.lds);
+  const uint32_t max_len = c->b->max_len;
+  const bool packed = P.sw_mode >= 1;
+  a.lng = max_len > SW_X4_MAX_ROWS;
+  a.striped = P.sw_mode < 0;
+  // the split path takes the marked reads with a record of k_cand (the hand-over) whose Smith-Waterman problems fit the packed kernels
+  a.split = packed && c->walk_split && c->handover && sw_pk_fits((int)std::min<uint32_t>(max_len, WK_MAX_ROWS), (int)a.rq, P.match, P.mismatch, P.score_N, P.gap_open);
+  a.x4 = packed && !a.lng && (long long)max_len * P.match + 255 < 32768 && a.rf + 128 <= 8191 && P.gap_open + P.mismatch >= 0 && P.gap_open + P.score_N >= 0 &&
+         P.match + P.gap_open <= 255 && P.score_N + P.gap_open <= 255;
+  a.rows = sw16_rows(max_len);
+  return a;
+}
+
+// the instantiation of each kernel family for the flags that select it (all of them: what raise_lds_limit is given)
+typedef decltype(&k_chain<false, false, false>) chain_fn;
+chain_fn chain_kernel(bool ext, bool lng, bool striped) {
+  static const chain_fn K[8] = {k_chain<false, false, false>, k_chain<true, false, false>, k_chain<false, true, false>, k_chain<true, true, false>,
+                                k_chain<false, false, true>,  k_chain<true, false, true>,  k_chain<false, true, true>,  k_chain<true, true, true>};
+  return K[(ext ? 1 : 0) | (lng ? 2 : 0) | (striped ? 4 : 0)];
+}
+typedef decltype(&k_begins<false, false>) begins_fn;
+begins_fn begins_kernel(bool lng, bool striped) {
+  static const begins_fn K[4] = {k_begins<false, false>, k_begins<true, false>, k_begins<false, true>, k_begins<true, true>};
+  return K[(lng ? 1 : 0) | (striped ? 2 : 0)];
+}
+// k_sw16<rows> over one task list (smr_walk.hpp).  counted: 0 = a walk round, 4 = the begin-cell stage (smr_sw16_launches), < 0 = not counted (the
+// test seam); blocks 0: what fills the device
+typedef decltype(&k_sw16<13>) sw16_fn;
+void launch_sw16(smr_ctx* c, int rows, int counted, uint32_t blocks, const DReads& rd, const DIndex& ix, const DParams& P, const WTask* tasks, const uint32_t* tix, const uint32_t* tix2,
+                 const unsigned long long* wc, uint2* res) {
+  static const sw16_fn K[4] = {k_sw16<13>, k_sw16<19>, k_sw16<26>, k_sw16<32>};
+  const int v = rows == 13 ? 0 : rows == 19 ? 1 : rows == 26 ? 2 : 3;
+  launch(c, K[v], dim3(blocks ? blocks : (uint32_t)c->n_cu * 4u * (uint32_t)SW16_WAVES(rows)), dim3(64), 0, rd, ix, P, tasks, tix, tix2, wc, res);
+  if (counted >= 0) c->sw16_launches[counted + v]++;
 }
 
 __global__ void k_wstat(const unsigned long long* __restrict__ wctr, unsigned long long* __restrict__ out, uint32_t rounds) {
@@ -50,92 +95,70 @@ int adapt_walk_rounds(smr_ctx* c) {
   return SMR_OK;
 }
 
-int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, int pass, int is_last_strand) {
-  uint32_t ml, rf, rq; size_t lds;
-  chain_lds(c, P, ml, rf, rq, lds);
-  HIPCHK(c, hipMemsetAsync(&c->b->d_ctr[C_WORK_NEXT], 0, 8, c->stream));
-  if (lds > 64 * 1024 && lds > c->chain_lds_attr) {     // reads beyond ~5.6 kb: more than the default 64 KB of dynamic LDS per workgroup (gfx950 has 160 KB per CU)
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_chain<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_chain<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_chain<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_chain<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_chain<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_chain<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_chain<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_chain<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    c->chain_lds_attr = lds;
-  }
-  uint32_t blocks = std::min<uint32_t>(c->chain_blocks, std::max(c->b->n, 1u));
-  { int rc = ensure_bound(c, c->chain_blocks, rf); if (rc) return rc; }
-  int* const gb = c->b->max_len > SW_X4_MAX_ROWS ? c->d_bound : nullptr;
-  uint8_t* const grd = c->b->max_len > SW_X4_MAX_ROWS ? c->d_rdq : nullptr;
+int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, const AlignPlan& plan, int pass, int is_last_strand) {
+  Batch& B = *c->b;
+  const uint32_t ml = plan.ml, rf = plan.rf, rq = plan.rq;
+  const size_t lds = plan.lds;
+  const bool split = plan.split;
+  int rc;
+  HIPCHK(c, hipMemsetAsync(&B.d_ctr[C_WORK_NEXT], 0, 8, c->stream));
+  // reads beyond ~5.6 kb: more than the default 64 KB of dynamic LDS per workgroup (gfx950 has 160 KB per CU)
+  if ((rc = raise_lds_limit(c, c->chain_lds_attr, lds, 64 * 1024, chain_kernel(0, 0, 0), chain_kernel(1, 0, 0), chain_kernel(0, 1, 0), chain_kernel(1, 1, 0),
+                            chain_kernel(0, 0, 1), chain_kernel(1, 0, 1), chain_kernel(0, 1, 1), chain_kernel(1, 1, 1)))) return rc;
+  const uint32_t blocks = std::min<uint32_t>(c->chain_blocks, std::max(B.n, 1u));
+  if ((rc = ensure_bound(c, c->chain_blocks, rf))) return rc;
+  int* const gb = plan.lng ? c->d_bound.get() : nullptr;
+  uint8_t* const grd = plan.lng ? c->d_rdq.get() : nullptr;
   if (c->handover) {
-    // CAND_REC_WORDS words per read of the batch, one slice per block of k_cand
-    const size_t want_w = (size_t)((c->b->n + CAND_BLOCK - 1u) / CAND_BLOCK) * CAND_BLOCK * CAND_REC_WORDS;
-    if (c->mrec_cap < c->b->n) { int rc = dev_alloc(c, &c->d_mrec, (size_t)c->b->n); if (rc) return rc; c->mrec_cap = c->b->n; }
-    if (c->mpool_words < want_w) { int rc = dev_alloc(c, &c->d_mpool, want_w); if (rc) return rc; c->mpool_words = want_w; }
+    // {offset, npos} per read; CAND_REC_WORDS words per read of the batch, one slice per block of k_cand
+    if ((rc = c->d_mrec.reserve(c, B.n)) || (rc = c->d_mpool.reserve(c, (size_t)((B.n + CAND_BLOCK - 1u) / CAND_BLOCK) * CAND_BLOCK * CAND_REC_WORDS))) return rc;
   }
-  uint2* const mrec = c->handover ? c->d_mrec : nullptr;
-  // the split path takes the marked reads with a record of k_cand whose Smith-Waterman problems fit the packed kernels
-  const uint32_t wmq = std::min<uint32_t>(c->b->max_len, WK_MAX_ROWS), wml = (wmq + 15) & ~15u;
-  const bool split = c->walk_split && mrec && P.sw_mode >= 1 && sw_pk_fits((int)wmq, (int)rq, P.match, P.mismatch, P.score_N, P.gap_open);
+  const uint2* const mrec = c->handover ? c->d_mrec.get() : nullptr;
+  const uint32_t wml = (std::min<uint32_t>(B.max_len, WK_MAX_ROWS) + 15) & ~15u;
   const uint32_t RMX = c->walk_rounds, WK = c->walk_k;         // RMX: what d_wctr is laid out for; RM: the rounds of this launch
   const uint32_t RM = (!c->walk_rounds_fixed && c->walk_need[pass]) ? std::min(RMX, c->walk_need[pass]) : RMX;
   if (split) {
-    const size_t n = c->b->n;
+    const size_t n = B.n;
     if (c->walk_cap < n || c->walk_kcap < WK) {
-      for (int q = 0; q < 2; q++) {
-        int rc;
-        if ((rc = dev_alloc(c, &c->d_wlist[q], n)) || (rc = dev_alloc(c, &c->d_wstate[q], n)) || (rc = dev_alloc(c, &c->d_wtask[q], n * WK)) || (rc = dev_alloc(c, &c->d_wres[q], n * WK))) return rc;
-      }
-      int rc;
-      if ((rc = dev_alloc(c, &c->d_wtidx, 2 * n * WK)) || (rc = dev_alloc(c, &c->d_wslow, n))) return rc;
+      for (int q = 0; q < 2; q++)
+        if ((rc = c->d_wlist[q].alloc(c, n)) || (rc = c->d_wstate[q].alloc(c, n)) || (rc = c->d_wtask[q].alloc(c, n * WK)) || (rc = c->d_wres[q].alloc(c, n * WK))) return rc;
+      if ((rc = c->d_wtidx.alloc(c, 2 * n * WK)) || (rc = c->d_wslow.alloc(c, n))) return rc;
       c->walk_cap = n; c->walk_kcap = WK;
     }
-    if (c->walk_rcap < RMX) { int rc = dev_alloc(c, &c->d_wctr, (size_t)(RMX + 2) * WC_STRIDE); if (rc) return rc; if ((rc = dev_alloc(c, &c->d_wstat, (size_t)8 * 32))) return rc; c->walk_rcap = RMX; }
+    if ((rc = c->d_wctr.reserve(c, (size_t)(RMX + 2) * WC_STRIDE)) || (rc = c->d_wstat.reserve(c, (size_t)8 * 32))) return rc;      // (RMX is the context's: made once)
     HIPCHK(c, hipMemsetAsync(c->d_wctr, 0, (size_t)(RMX + 2) * WC_STRIDE * 8, c->stream));
-    const size_t lds_w = (size_t)wml + rq;
-    if (lds_w > 64 * 1024 && lds_w > c->walk_lds_attr) { HIPCHK(c, hipFuncSetAttribute((const void*)k_walk<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w)); c->walk_lds_attr = lds_w; }
+    if ((rc = raise_lds_limit(c, c->walk_lds_attr, (size_t)wml + rq, 64 * 1024, k_walk<true>))) return rc;
   }
   const size_t n_tix = (size_t)c->walk_cap * c->walk_kcap;     // the second half of d_wtidx: the score-only tasks
   unsigned long long* const n_slow = split ? c->d_wctr + (size_t)(RMX + 1) * WC_STRIDE : nullptr;
+  const dim3 per_read((B.n + 255u) / 256u);
   ev_mark(c, KP_CAND);
   // the reads without any candidate reference end their pass in k_cand; k_chain walks the ones it marks
-  hipLaunchKernelGGL(k_cand, dim3((c->b->n + CAND_BLOCK - 1u) / CAND_BLOCK), dim3(256), CAND_LDS_BYTES(c->cand_bloom, c->handover), c->stream, dreads(c), dindex(di), P, pass, is_last_strand, c->b->d_work, c->b->d_rw, (const uint32_t*)c->d_pool, c->b->d_marks, c->cand_bloom,
-                     mrec, c->d_mpool, c->mpool_words);
+  launch(c, k_cand, dim3((B.n + CAND_BLOCK - 1u) / CAND_BLOCK), dim3(256), CAND_LDS_BYTES(c->cand_bloom, c->handover), dreads(c), dindex(di), P, pass, is_last_strand, B.d_work, B.d_rw, c->d_pool, B.d_marks, c->cand_bloom,
+         c->handover ? c->d_mrec.get() : nullptr, c->d_mpool, c->d_mpool.cap());
   if (split) {
     // rounds of walk -> Smith-Waterman -> next list (smr_walk.hpp); the last round scores in the walk kernel, so every listed read ends its pass here
     ev_mark(c, KP_WNEXT);
-    hipLaunchKernelGGL(k_wlist, dim3((c->b->n + 1023u) / 1024u), dim3(1024), 0, c->stream, dreads(c), c->b->d_marks, (const uint2*)mrec, (uint32_t)WK_MAX_ROWS, c->d_wlist[0], c->d_wslow, c->d_wctr, n_slow, getenv("SMR_WALK_DEBUG") ? n_slow + 8 : (unsigned long long*)nullptr, (P.num_seeds >= 2 && c->walk_gather) ? 1 : 0);
-    if (c->cinfo_on) hipLaunchKernelGGL(k_cand_route, dim3((c->b->n + 255u) / 256u), dim3(256), 0, c->stream, c->b->n, (const uint8_t*)c->b->d_marks, (const uint2*)mrec, (const uint2*)c->d_wlist[0], (const unsigned long long*)c->d_wctr, 0, c->d_croute);
-    const int swr = wmq <= 104 ? 13 : wmq <= 152 ? 19 : wmq <= 208 ? 26 : 32;
-    const uint32_t walk_blocks = (uint32_t)c->n_cu * 4u * SMR_WALK_WAVES_PER_SIMD, sw_blocks = (uint32_t)c->n_cu * 4u * (uint32_t)SW16_WAVES(swr);
+    launch(c, k_wlist, dim3((B.n + 1023u) / 1024u), dim3(1024), 0, dreads(c), B.d_marks, mrec, (uint32_t)WK_MAX_ROWS, c->d_wlist[0], c->d_wslow, c->d_wctr, n_slow, getenv("SMR_WALK_DEBUG") ? n_slow + 8 : nullptr, (P.num_seeds >= 2 && c->walk_gather) ? 1 : 0);
+    if (c->cinfo_on) launch(c, k_cand_route, per_read, dim3(256), 0, B.n, B.d_marks, mrec, c->d_wlist[0], c->d_wctr, 0, c->d_croute);
+    const uint32_t walk_blocks = (uint32_t)c->n_cu * 4u * SMR_WALK_WAVES_PER_SIMD;
     for (uint32_t rnd = 0; rnd < RM; rnd++) {
       const int cur = (int)(rnd & 1u), prv = cur ^ 1;
       unsigned long long* const wc = c->d_wctr + (size_t)rnd * WC_STRIDE;
       const bool fin = rnd + 1 == RM;
       ev_mark(c, KP_WALK);
-#define WALK_ARGS dreads(c), dindex(di), P, pass, is_last_strand, c->b->d_work, c->b->d_work_aln, c->b->d_rw, c->b->d_ctr, (const uint2*)mrec, (const uint32_t*)c->d_mpool, (const uint32_t*)c->d_pool, (const uint2*)c->d_wlist[cur], \
-                  (const WState*)c->d_wstate[prv], (const WTask*)c->d_wtask[prv], (const uint2*)c->d_wres[prv], c->d_wstate[cur], c->d_wtask[cur], c->d_wtidx, c->d_wtidx + n_tix, wc, WK, (unsigned long long)n_tix, (int)rnd, wml, rq, c->walk_assume
-      if (fin) hipLaunchKernelGGL(k_walk<true>, dim3(walk_blocks * 3u / SMR_WALK_WAVES_PER_SIMD), dim3(64), (size_t)wml + rq, c->stream, WALK_ARGS);
-      else {
-        hipLaunchKernelGGL(k_walk<false>, dim3(walk_blocks), dim3(64), 0, c->stream, WALK_ARGS);
-        ev_mark(c, KP_SW16);
-#define SW16_ARGS dreads(c), dindex(di), P, (const WTask*)c->d_wtask[cur], (const uint32_t*)c->d_wtidx, (const uint32_t*)(c->d_wtidx + n_tix), (const unsigned long long*)wc, c->d_wres[cur]
-        if (swr == 13) hipLaunchKernelGGL(k_sw16<13>, dim3(sw_blocks), dim3(64), 0, c->stream, SW16_ARGS);
-        else if (swr == 19) hipLaunchKernelGGL(k_sw16<19>, dim3(sw_blocks), dim3(64), 0, c->stream, SW16_ARGS);
-        else if (swr == 26) hipLaunchKernelGGL(k_sw16<26>, dim3(sw_blocks), dim3(64), 0, c->stream, SW16_ARGS);
-        else hipLaunchKernelGGL(k_sw16<32>, dim3(sw_blocks), dim3(64), 0, c->stream, SW16_ARGS);
-#undef SW16_ARGS
-        c->sw16_launches[swr == 13 ? 0 : swr == 19 ? 1 : swr == 26 ? 2 : 3]++;
-        ev_mark(c, KP_WNEXT);
-        hipLaunchKernelGGL(k_wnext, dim3((uint32_t)c->n_cu * 2u), dim3(1024), 0, c->stream, P, is_last_strand, c->b->d_work, c->b->d_rw, c->b->d_ctr, (const uint2*)c->d_wlist[cur], (const WState*)c->d_wstate[cur],
-                           (const uint2*)c->d_wres[cur], c->d_wlist[prv], (const unsigned long long*)wc, wc + WC_STRIDE, WK, (unsigned long long)n_tix, (int)rnd);
-      }
-#undef WALK_ARGS
+      launch(c, fin ? k_walk<true> : k_walk<false>, dim3(fin ? walk_blocks * 3u / SMR_WALK_WAVES_PER_SIMD : walk_blocks), dim3(64), fin ? (size_t)wml + rq : 0,
+             dreads(c), dindex(di), P, pass, is_last_strand, B.d_work, B.d_work_aln, B.d_rw, B.d_ctr, mrec, c->d_mpool, c->d_pool, c->d_wlist[cur],
+             c->d_wstate[prv], c->d_wtask[prv], c->d_wres[prv], c->d_wstate[cur], c->d_wtask[cur], c->d_wtidx, c->d_wtidx + n_tix, wc, WK, n_tix, (int)rnd, wml, rq, c->walk_assume);
+      if (fin) continue;
+      ev_mark(c, KP_SW16);
+      launch_sw16(c, plan.rows, 0, 0, dreads(c), dindex(di), P, c->d_wtask[cur], c->d_wtidx, c->d_wtidx + n_tix, wc, c->d_wres[cur]);
+      ev_mark(c, KP_WNEXT);
+      launch(c, k_wnext, dim3((uint32_t)c->n_cu * 2u), dim3(1024), 0, P, is_last_strand, B.d_work, B.d_rw, B.d_ctr, c->d_wlist[cur], c->d_wstate[cur],
+             c->d_wres[cur], c->d_wlist[prv], wc, wc + WC_STRIDE, WK, n_tix, (int)rnd);
     }
     if (!c->walk_rounds_fixed && c->wstat_n < 8) {         // the reads listed per round, kept for adapt_walk_rounds
-      hipLaunchKernelGGL(k_wstat, dim3(1), dim3(32), 0, c->stream, (const unsigned long long*)c->d_wctr, c->d_wstat + (size_t)c->wstat_n * 32, RM);
+      launch(c, k_wstat, dim3(1), dim3(32), 0, c->d_wctr, c->d_wstat + (size_t)c->wstat_n * 32, RM);
       c->wstat_pass[c->wstat_n] = pass; c->wstat_rm[c->wstat_n] = RM; c->wstat_n++;
     }
     if (getenv("SMR_WALK_DEBUG")) {                         // measurement aid: reads listed and tasks left per round, reads left to k_chain
@@ -149,32 +172,47 @@ int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, int pass, int
     }
   }
   ev_mark(c, KP_CHAIN);
-#define CHAIN_ARGS(stab, t2) dreads(c), dindex(di), P, pass, is_last_strand, c->b->d_work, c->b->d_work_aln, c->b->d_rw, c->d_pool, c->b->d_ctr, c->d_tuples, c->d_keys, c->d_pairs, \
-                             c->d_lis, c->d_hits, c->keys_cap, c->pairs_cap, c->hits_cap, ml, rf, c->chain_scap, stab, t2, rq, gb, grd, c->b->d_marks, (const uint2*)mrec, (const uint32_t*)c->d_mpool, \
-                             (const uint32_t*)(split ? c->d_wslow : nullptr), (const unsigned long long*)n_slow
-  if (c->cinfo_on) hipLaunchKernelGGL(k_cand_route, dim3((c->b->n + 255u) / 256u), dim3(256), 0, c->stream, c->b->n, (const uint8_t*)c->b->d_marks, (const uint2*)nullptr, (const uint2*)nullptr, (const unsigned long long*)nullptr, 1, c->d_croute);
-  // (LONG: the batch has reads of more than one Smith-Waterman strip; the short-read instantiation carries none of their state)
-  const bool striped = P.sw_mode < 0;                        // (the slow path that reproduces ssw.c's stripe geometry: instantiations of its own)
-  if (striped) {
-    if (gb) hipLaunchKernelGGL((k_chain<false, true, true>), dim3(blocks), dim3(64), lds, c->stream, CHAIN_ARGS(c->chain_ext ? c->d_stab : nullptr, c->chain_ext ? c->d_tuples2 : nullptr));
-    else hipLaunchKernelGGL((k_chain<false, false, true>), dim3(blocks), dim3(64), lds, c->stream, CHAIN_ARGS(c->chain_ext ? c->d_stab : nullptr, c->chain_ext ? c->d_tuples2 : nullptr));
-  } else
-  if (gb) hipLaunchKernelGGL((k_chain<false, true>), dim3(blocks), dim3(64), lds, c->stream, CHAIN_ARGS(c->chain_ext ? c->d_stab : nullptr, c->chain_ext ? c->d_tuples2 : nullptr));
-  else hipLaunchKernelGGL((k_chain<false, false>), dim3(blocks), dim3(64), lds, c->stream, CHAIN_ARGS(c->chain_ext ? c->d_stab : nullptr, c->chain_ext ? c->d_tuples2 : nullptr));
-  if (c->chain_ext) {
-    // the reads whose candidate set outgrew the LDS table of the first launch: same walk, set in the block's global table
-    HIPCHK(c, hipMemsetAsync(&c->b->d_ctr[C_WORK_NEXT], 0, 8, c->stream));
-    if (c->cinfo_on) hipLaunchKernelGGL(k_cand_route, dim3((c->b->n + 255u) / 256u), dim3(256), 0, c->stream, c->b->n, (const uint8_t*)c->b->d_marks, (const uint2*)nullptr, (const uint2*)nullptr, (const unsigned long long*)nullptr, 2, c->d_croute);
-    if (striped) {
-      if (gb) hipLaunchKernelGGL((k_chain<true, true, true>), dim3(blocks), dim3(64), lds, c->stream, CHAIN_ARGS(c->d_stab, c->d_tuples2));
-      else hipLaunchKernelGGL((k_chain<true, false, true>), dim3(blocks), dim3(64), lds, c->stream, CHAIN_ARGS(c->d_stab, c->d_tuples2));
-    } else
-    if (gb) hipLaunchKernelGGL((k_chain<true, true>), dim3(blocks), dim3(64), lds, c->stream, CHAIN_ARGS(c->d_stab, c->d_tuples2));
-    else hipLaunchKernelGGL((k_chain<true, false>), dim3(blocks), dim3(64), lds, c->stream, CHAIN_ARGS(c->d_stab, c->d_tuples2));
+  // k_chain<EXT = false> over the marked reads; with the global tables on, k_chain<EXT = true> over the reads whose candidate set outgrew the LDS
+  // table of the first launch: same walk, set in the block's global table
+  for (int ext = 0; ext <= (c->chain_ext ? 1 : 0); ext++) {
+    if (ext) HIPCHK(c, hipMemsetAsync(&B.d_ctr[C_WORK_NEXT], 0, 8, c->stream));
+    if (c->cinfo_on) launch(c, k_cand_route, per_read, dim3(256), 0, B.n, B.d_marks, nullptr, nullptr, nullptr, 1 + ext, c->d_croute);
+    launch(c, chain_kernel(ext, plan.lng, plan.striped), dim3(blocks), dim3(64), lds, dreads(c), dindex(di), P, pass, is_last_strand, B.d_work, B.d_work_aln, B.d_rw, c->d_pool, B.d_ctr,
+           c->d_tuples, c->d_keys, c->d_pairs, c->d_lis, c->d_hits, c->keys_cap, c->pairs_cap, c->hits_cap, ml, rf, c->chain_scap, c->chain_ext ? c->d_stab.get() : nullptr,
+           c->chain_ext ? c->d_tuples2.get() : nullptr, rq, gb, grd, B.d_marks, mrec, c->d_mpool, split ? c->d_wslow.get() : nullptr, n_slow);
   }
-#undef CHAIN_ARGS
   ev_stop(c);
   HIPCHK(c, hipGetLastError());
+  return SMR_OK;
+}
+
+// The begin cells of the alignments that are still stored (k_chain records the accepted ones "begin pending"): four reverse passes per wave, or --
+// sixteen per wave through k_sw16 -- the end cells of the alignments stored end-pending (stage 0), then the begin cells of all (stage 1).
+int launch_begins(smr_ctx* c, const DevIndex& di, const DParams& P, const AlignPlan& plan) {
+  Batch& B = *c->b;
+  int rc;
+  const uint64_t ntot = (uint64_t)B.n * B.slots;
+  if ((rc = c->d_tasks.reserve(c, 2 * ntot))) return rc;
+  const int x4 = plan.x4 ? 1 : 0;
+  const size_t lds_b = x4 ? (size_t)4 * (plan.ml + plan.rf) : (plan.lng ? 0 : (size_t)plan.ml + plan.rf);
+  const uint32_t bg_blocks = (uint32_t)c->n_cu * 8u;
+  if ((rc = ensure_bound(c, std::max(bg_blocks, c->chain_blocks), plan.rf))) return rc;
+  if ((rc = raise_lds_limit(c, c->begins_lds_attr, lds_b, 64 * 1024, begins_kernel(0, 0), begins_kernel(1, 0), begins_kernel(0, 1), begins_kernel(1, 1)))) return rc;
+  HIPCHK(c, hipMemsetAsync(&B.d_ctr[C_BEGIN_N], 0, 16, c->stream));       // C_BEGIN_N, C_BEGIN_NEXT
+  ev_mark(c, KP_BEGINS);
+  launch(c, k_begins_collect, dim3((uint32_t)((ntot + 1023) / 1024)), dim3(1024), 0, B.n, B.slots, B.d_work, B.d_rw, B.d_work_aln, c->d_tasks, B.d_ctr);
+  const size_t task_cap = (size_t)c->walk_cap * c->walk_kcap;
+  if (x4 && c->walk_split && c->d_wtask[0] && c->d_wctr && ntot <= task_cap && !getenv("SMR_BEGINS_X4")) {
+    for (int stage = 0; stage < 2; stage++) {
+      HIPCHK(c, hipMemsetAsync(c->d_wctr, 0, (size_t)WC_STRIDE * 8, c->stream));
+      launch(c, k_begins_prep, dim3((uint32_t)c->n_cu * 2u), dim3(1024), 0, dindex(di), B.slots, c->d_tasks, &B.d_ctr[C_BEGIN_N], B.d_work_aln, stage, c->d_wtask[0], c->d_wtidx, c->d_wctr);
+      launch_sw16(c, plan.rows, 4, 0, dreads(c), dindex(di), P, c->d_wtask[0], c->d_wtidx, c->d_wtidx + task_cap, c->d_wctr, c->d_wres[0]);
+      launch(c, k_begins_apply, dim3((uint32_t)c->n_cu * 4u), dim3(256), 0, c->d_tasks, &B.d_ctr[C_BEGIN_N], B.d_work_aln, stage, c->d_wtask[0], c->d_wres[0], B.d_ctr);
+    }
+  } else
+    launch(c, begins_kernel(plan.lng, plan.striped), dim3(bg_blocks), dim3(64), lds_b, dreads(c), dindex(di), P, c->d_tasks, B.d_work_aln, B.d_ctr, plan.ml, plan.rf, x4,
+           plan.lng ? c->d_bound.get() : nullptr, plan.lng ? c->d_rdq.get() : nullptr);
+  ev_stop(c);
   return SMR_OK;
 }
 

@@ -12,16 +12,13 @@ extern "C" int smr_state_export(smr_ctx* c, uint8_t* bytes, uint64_t cap, uint64
   if (n == 0) { if (off) off[0] = 0; return SMR_OK; }
   int rc;
   const uint32_t np = (n + EXP_SIZE_BLOCK - 1u) / EXP_SIZE_BLOCK;
-  if (c->xoff_cap < (size_t)n + 1) {
-    c->xoff_cap = 0;
-    if ((rc = dev_alloc(c, &c->d_xoff, (size_t)n + 1))) return rc;
-    if ((rc = dev_alloc(c, &c->d_xpart, (size_t)np))) return rc;
-    c->xoff_cap = (size_t)n + 1;
+  if (c->d_xoff.cap() < (size_t)n + 1) {                     // (both or neither: d_xoff's capacity stands for the pair)
+    if ((rc = c->d_xoff.alloc(c, (size_t)n + 1)) || (rc = c->d_xpart.alloc(c, (size_t)np))) { c->d_xoff.release(); return rc; }
   }
-  hipLaunchKernelGGL(k_export_size, dim3(np), dim3(EXP_SIZE_BLOCK), 0, c->stream, n, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, c->d_xoff, c->d_xpart);
+  launch(c, k_export_size, dim3(np), dim3(EXP_SIZE_BLOCK), 0, n, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, c->d_xoff, c->d_xpart);
   if (np > 1) {
-    hipLaunchKernelGGL(k_export_scan, dim3(1), dim3(EXP_SIZE_BLOCK), 0, c->stream, c->d_xpart, np);
-    hipLaunchKernelGGL(k_export_offsets, dim3(np), dim3(EXP_SIZE_BLOCK), 0, c->stream, n, c->d_xoff, (const unsigned long long*)c->d_xpart);
+    launch(c, k_export_scan, dim3(1), dim3(EXP_SIZE_BLOCK), 0, c->d_xpart, np);
+    launch(c, k_export_offsets, dim3(np), dim3(EXP_SIZE_BLOCK), 0, n, c->d_xoff, (const unsigned long long*)c->d_xpart);
   }
   HIPCHK(c, hipGetLastError());
   unsigned long long total = 0;
@@ -32,14 +29,9 @@ extern "C" int smr_state_export(smr_ctx* c, uint8_t* bytes, uint64_t cap, uint64
   if (!bytes) return SMR_OK;
   if (cap < total) { set_err(c, "smr_state_export: the records take " + std::to_string(total) + " bytes, the buffer has " + std::to_string(cap)); return SMR_ERR_CAPACITY; }
   if (total == 0) return SMR_OK;
-  if (c->xbytes_cap < total) {
-    c->xbytes_cap = 0;
-    const uint64_t want = (total + (total >> 3) + 4095u) & ~4095ull;           // (the next, slightly larger batch fits as well)
-    if ((rc = dev_alloc(c, &c->d_xbytes, (size_t)want))) return rc;
-    c->xbytes_cap = want;
-  }
+  if (c->d_xbytes.cap() < total && (rc = c->d_xbytes.alloc(c, (size_t)((total + (total >> 3) + 4095u) & ~4095ull)))) return rc;      // (the next, slightly larger batch fits as well)
   const uint32_t chunks = (n + 63u) / 64u, blocks = std::min<uint32_t>((chunks + 3u) / 4u, (uint32_t)c->n_cu * 8u);
-  hipLaunchKernelGGL(k_export_state, dim3(blocks), dim3(256), 0, c->stream, n, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar,
+  launch(c, k_export_state, dim3(blocks), dim3(256), 0, n, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar,
                      (unsigned long long)(B.d_cigar ? B.cigar_words : 0), (const uint32_t*)B.d_idcov, B.last_num_alignments, (const unsigned long long*)c->d_xoff, c->d_xbytes);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(bytes, c->d_xbytes, (size_t)total, hipMemcpyDeviceToHost, c->stream));

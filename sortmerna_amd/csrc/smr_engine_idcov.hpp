@@ -9,16 +9,14 @@ static int idcov_core(smr_ctx* c, const DevIndex& di, uint32_t index_num, uint32
   ev_drop(c);
   const uint64_t ntot = (uint64_t)B.n * B.slots;
   if (ntot >= 0xFFFFFC00ull) { set_err(c, "smr_idcov_part: reads x alignment slots of the batch must stay below 2^32 (the work lists index them with 32 bits)"); return SMR_ERR_CAPACITY; }
-  if (c->tasks_cap < ntot) { if ((rc = dev_alloc(c, &c->d_tasks, 2 * ntot))) return rc; c->tasks_cap = ntot; }     // two lists: few / many operations
-  if (!d_out && B.cap_idcov < (size_t)B.n) {
-    if ((rc = dev_alloc(c, &B.d_idcov, (size_t)B.n * 4))) return rc;
-    B.cap_idcov = B.n;
+  if ((rc = c->d_tasks.reserve(c, 2 * ntot))) return rc;     // two lists: few / many operations
+  if (!d_out && B.d_idcov.cap() < (size_t)B.n * 4) {
+    if ((rc = B.d_idcov.alloc(c, (size_t)B.n * 4))) return rc;
     HIPCHK(c, hipMemsetAsync(B.d_idcov, 0, (size_t)B.n * 16, c->stream));
   }
   HIPCHK(c, hipMemsetAsync(&B.d_ctr[C_IDCOV_FEW], 0, 24, c->stream));              // C_IDCOV_FEW, C_IDCOV_MANY, C_IDCOV_NOCIG
   uint32_t* few = c->d_tasks; uint32_t* many = c->d_tasks + ntot;
-  hipLaunchKernelGGL(k_idcov_collect, dim3((uint32_t)((ntot + 1023) / 1024)), dim3(1024), 0, c->stream, B.n, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln,
-                     index_num, part, few, many, B.d_ctr, (int)C_IDCOV_FEW);
+  launch(c, k_idcov_collect, dim3((uint32_t)((ntot + 1023) / 1024)), dim3(1024), 0, B.n, B.slots, B.d_saved, B.d_saved_aln, index_num, part, few, many, B.d_ctr, (int)C_IDCOV_FEW);
   HIPCHK(c, hipGetLastError());
   std::vector<unsigned long long> h;
   if ((rc = read_ctr(c, h))) return rc;
@@ -30,12 +28,12 @@ static int idcov_core(smr_ctx* c, const DevIndex& di, uint32_t index_num, uint32
   if (n_few + n_many == 0) return SMR_OK;
   B.fetched = false;
   if (!d_out) B.idcov_ran = true;
-  uint32_t* per_read = d_out ? nullptr : B.d_idcov;
+  uint32_t* per_read = d_out ? nullptr : B.d_idcov.get();
   ev_mark(c, KP_IDCOV);
-  if (n_few) hipLaunchKernelGGL(k_idcov_few, dim3(std::min<uint32_t>((n_few + 3u) / 4u, (uint32_t)c->n_cu * 16u)), dim3(64), 0, c->stream, dreads(c), dindex(di), (const uint32_t*)few, n_few,
-                                B.d_saved_aln, (const uint32_t*)B.d_cigar, B.slots, min_id, min_cov, per_read, d_out, B.d_ctr, (int)C_IDCOV);
-  if (n_many) hipLaunchKernelGGL(k_idcov_many, dim3(std::min<uint32_t>(n_many, (uint32_t)c->n_cu * 16u)), dim3(64), 0, c->stream, dreads(c), dindex(di), (const uint32_t*)many, n_many,
-                                 B.d_saved_aln, (const uint32_t*)B.d_cigar, B.slots, min_id, min_cov, per_read, d_out, B.d_ctr, (int)C_IDCOV);
+  if (n_few) launch(c, k_idcov_few, dim3(std::min<uint32_t>((n_few + 3u) / 4u, (uint32_t)c->n_cu * 16u)), dim3(64), 0, dreads(c), dindex(di), few, n_few,
+                    B.d_saved_aln, B.d_cigar, B.slots, min_id, min_cov, per_read, d_out, B.d_ctr, (int)C_IDCOV);
+  if (n_many) launch(c, k_idcov_many, dim3(std::min<uint32_t>(n_many, (uint32_t)c->n_cu * 16u)), dim3(64), 0, dreads(c), dindex(di), many, n_many,
+                     B.d_saved_aln, B.d_cigar, B.slots, min_id, min_cov, per_read, d_out, B.d_ctr, (int)C_IDCOV);
   ev_stop(c);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -85,15 +83,8 @@ extern "C" int smr_idcov_batch(smr_ctx* c, uint32_t n, const uint8_t* reads, con
   HIPCHK(c, hipSetDevice(c->device));
   if (n == 0) return SMR_OK;
   if (!reads || !refs || !cigars) return SMR_ERR_ARG;
-  Batch* keep = c->b;
-  Batch tmp;
-  DevIndex di;
-  std::vector<uint32_t> words, lens(n);
-  std::vector<uint64_t> rec_off((size_t)n + 1, 0);
-  std::vector<RState> st(n);
-  std::vector<AlignRec> al(n);
-  uint32_t max_len = 1;
   if (cigar_off[n] >= 0xFFFFFFF0ull) { set_err(c, "smr_idcov_batch: too many CIGAR operations"); return SMR_ERR_ARG; }
+  std::vector<uint64_t> ref_span(n);                       // reference letters each CIGAR covers
   for (uint32_t i = 0; i < n; i++) {
     const uint64_t m = read_off[i + 1] - read_off[i], nr = ref_off[i + 1] - ref_off[i], nc = cigar_off[i + 1] - cigar_off[i];
     if (m == 0 || m > 0xFFFFu || nc == 0 || readlen[i] == 0 || read_begin[i] < 0 || (uint64_t)read_begin[i] >= m) { set_err(c, "smr_idcov_batch: empty or oversized triple"); return SMR_ERR_ARG; }
@@ -106,57 +97,21 @@ extern "C" int smr_idcov_batch(smr_ctx* c, uint32_t n, const uint8_t* reads, con
       if (op != 1) qb += len;
     }
     if (pb > m || qb > nr) { set_err(c, "smr_idcov_batch: a CIGAR runs past its read or its reference window"); return SMR_ERR_ARG; }
-    const uint32_t cw = (uint32_t)((m + 15) >> 4), mw = (uint32_t)((m + 31) >> 5);
-    rec_off[i] = words.size();
-    words.resize(words.size() + cw + mw, 0u);
-    uint32_t* rec = words.data() + rec_off[i];
-    for (uint64_t q = 0; q < m; q++) {
-      const uint8_t ch = reads[read_off[i] + q];
-      if (ch > 3) rec[cw + (q >> 5)] |= 1u << (q & 31); else rec[q >> 4] |= (uint32_t)ch << ((q & 15) * 2);
-    }
-    lens[i] = (uint32_t)m; max_len = std::max(max_len, (uint32_t)m);
-    memset(&st[i], 0, sizeof(RState)); st[i].n_align = 1; st[i].is_hit = 1;
-    memset(&al[i], 0, sizeof(AlignRec));
-    al[i].ref_num = i; al[i].ref_begin1 = 0; al[i].ref_end1 = (int32_t)qb - 1; al[i].read_begin1 = read_begin[i]; al[i].read_end1 = read_end[i];
-    al[i].readlen = readlen[i]; al[i].strand = 1; al[i].has_cigar = 1; al[i].cigar_off = (uint32_t)cigar_off[i]; al[i].cigar_len = (uint32_t)nc;
+    ref_span[i] = qb;
   }
-  rec_off[n] = words.size();
-  tmp.n = n; tmp.max_len = max_len; tmp.slots = 1; tmp.used = true;
-  uint32_t* d_out = nullptr;
-  auto run = [&]() -> int {
-    int r2;
-    c->b = &tmp;
-    if ((r2 = dev_alloc(c, &tmp.d_words, words.size() + 4))) return r2;
-    if ((r2 = dev_alloc(c, &tmp.d_rec_off, rec_off.size()))) return r2;
-    if ((r2 = dev_alloc(c, &tmp.d_len, lens.size()))) return r2;
-    if ((r2 = dev_alloc(c, &tmp.d_saved, (size_t)n))) return r2;
-    if ((r2 = dev_alloc(c, &tmp.d_saved_aln, (size_t)n))) return r2;
-    if ((r2 = dev_alloc(c, &tmp.d_ctr, (size_t)C_TOTAL))) return r2;
-    if ((r2 = dev_alloc(c, &tmp.d_cigar, (size_t)cigar_off[n] + 1))) return r2;
-    if ((r2 = dev_alloc(c, &di.ref_seq, (size_t)ref_off[n] + 64))) return r2;
-    if ((r2 = dev_alloc(c, &di.ref_off, (size_t)n + 1))) return r2;
-    if ((r2 = dev_alloc(c, &d_out, (size_t)n * 4))) return r2;
-    HIPCHK(c, hipMemsetAsync(tmp.d_words + words.size(), 0, 16, c->stream));
-    HIPCHK(c, hipMemcpyAsync(tmp.d_words, words.data(), words.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(tmp.d_rec_off, rec_off.data(), rec_off.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(tmp.d_len, lens.data(), lens.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(tmp.d_saved, st.data(), st.size() * sizeof(RState), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(tmp.d_saved_aln, al.data(), al.size() * sizeof(AlignRec), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(tmp.d_ctr, 0, C_TOTAL * 8, c->stream));
-    HIPCHK(c, hipMemcpyAsync(tmp.d_cigar, cigars, (size_t)cigar_off[n] * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(di.ref_seq + ref_off[n], 0, 64, c->stream));
-    if (ref_off[n]) HIPCHK(c, hipMemcpyAsync(di.ref_seq, refs, (size_t)ref_off[n], hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(di.ref_off, ref_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    di.n_refs = n; di.lnwin = 18; di.used = true;
-    if ((r2 = idcov_core(c, di, 0, 0, min_id, min_cov, d_out))) return r2;
-    HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SMR_OK;
-  };
-  const int rc = run();
-  (void)hipStreamSynchronize(c->stream);
-  c->b = keep;
-  dev_free(&tmp.d_words); dev_free(&tmp.d_rec_off); dev_free(&tmp.d_len); dev_free(&tmp.d_saved); dev_free(&tmp.d_saved_aln); dev_free(&tmp.d_ctr); dev_free(&tmp.d_cigar);
-  dev_free(&di.ref_seq); dev_free(&di.ref_off); dev_free(&d_out);
-  return rc;
+  TempBatch t(c);
+  t.pack(n, reads, read_off);
+  for (uint32_t i = 0; i < n; i++) {                        // one stored alignment per triple, with the caller's CIGAR
+    AlignRec& a = t.al[i];
+    a.ref_begin1 = 0; a.ref_end1 = (int32_t)ref_span[i] - 1; a.read_begin1 = read_begin[i]; a.read_end1 = read_end[i];
+    a.readlen = readlen[i]; a.has_cigar = 1; a.cigar_off = (uint32_t)cigar_off[i]; a.cigar_len = (uint32_t)(cigar_off[i + 1] - cigar_off[i]);
+  }
+  DevBuf<uint32_t> d_out;
+  int rc;
+  if ((rc = t.upload(refs, ref_off)) || (rc = t.b.d_cigar.alloc(c, (size_t)cigar_off[n] + 1)) || (rc = d_out.alloc(c, (size_t)n * 4))) return rc;
+  HIPCHK(c, hipMemcpyAsync(t.b.d_cigar, cigars, (size_t)cigar_off[n] * 4, hipMemcpyHostToDevice, c->stream));
+  if ((rc = idcov_core(c, t.di, 0, 0, min_id, min_cov, d_out))) return rc;
+  HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SMR_OK;
 }

@@ -15,7 +15,7 @@ int import_fresh(smr_ctx* c, Batch& B, bool clear_saved) {
   HIPCHK(c, hipMemsetAsync(B.d_ctr + C_ERR_HITCAP, 0, (size_t)(C_SW_SPEC - C_ERR_HITCAP) * 8, c->stream));      // error flags and cursors, C_CIGAR_CURSOR among them
   HIPCHK(c, hipMemsetAsync(B.d_ctr + C_PCUR, 0, (size_t)C_NSHARD * C_PCUR_STRIDE * 8, c->stream));
   HIPCHK(c, hipMemsetAsync(B.d_ctr + C_IDCOV, 0, 4 * 8, c->stream));
-  if (B.d_idcov) HIPCHK(c, hipMemsetAsync(B.d_idcov, 0, std::min(B.cap_idcov, (size_t)B.n) * 16, c->stream));
+  if (B.d_idcov) HIPCHK(c, hipMemsetAsync(B.d_idcov, 0, std::min(B.d_idcov.cap() / 4, (size_t)B.n) * 16, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   B.fetched = false;
   return SMR_OK;
@@ -47,23 +47,21 @@ extern "C" int smr_state_import(smr_ctx* c, const uint8_t* bytes, const uint64_t
   const uint64_t need = total / 4;
   if (need > B.cigar_words) {
     const uint64_t w = std::max<uint64_t>(need, 1u << 20);
-    if ((rc = dev_alloc(c, &B.d_cigar, (size_t)w))) { B.cigar_words = 0; return rc; }
+    if ((rc = B.d_cigar.alloc(c, (size_t)w))) { B.cigar_words = 0; return rc; }
     B.cigar_words = w;
   }
-  uint32_t* d_bytes = nullptr; unsigned long long* d_off = nullptr; uint32_t* d_flag = nullptr;
+  DevBuf<uint32_t> d_bytes, d_flag; DevBuf<unsigned long long> d_off;      // (of this call)
   uint32_t h_flag[4] = {0, 0, 0, 0};
   auto run = [&]() -> int {
     int r2;
     const size_t nw = (size_t)((total + 3) / 4);
-    if ((r2 = dev_alloc(c, &d_bytes, nw + 2))) return r2;
-    if ((r2 = dev_alloc(c, &d_off, (size_t)n + 1))) return r2;
-    if ((r2 = dev_alloc(c, &d_flag, 4))) return r2;
+    if ((r2 = d_bytes.alloc(c, nw + 2)) || (r2 = d_off.alloc(c, (size_t)n + 1)) || (r2 = d_flag.alloc(c, 4))) return r2;
     HIPCHK(c, hipMemsetAsync(d_bytes + (nw ? nw - 1 : 0), 0, 8, c->stream));          // the last word ends on bytes that are not the caller's
     if (total) HIPCHK(c, hipMemcpyAsync(d_bytes, bytes + o_base, (size_t)total, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_off, off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_flag, 0, 16, c->stream));
     const uint32_t chunks = (n + 63u) / 64u, blocks = std::min<uint32_t>((chunks + 3u) / 4u, (uint32_t)c->n_cu * 8u);
-    hipLaunchKernelGGL(k_import_state, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t*)d_bytes, (unsigned long long)o_base, (unsigned long long)total, (const unsigned long long*)d_off, n, B.slots,
+    launch(c, k_import_state, dim3(blocks), dim3(256), 0, (const uint32_t*)d_bytes, (unsigned long long)o_base, (unsigned long long)total, (const unsigned long long*)d_off, n, B.slots,
                        (const uint32_t*)B.d_len, B.d_saved, B.d_saved_aln, B.d_cigar, (unsigned long long)B.cigar_words, B.d_ctr, d_flag);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_flag, d_flag, 16, hipMemcpyDeviceToHost, c->stream));
@@ -72,7 +70,7 @@ extern "C" int smr_state_import(smr_ctx* c, const uint8_t* bytes, const uint64_t
   };
   rc = run();
   (void)hipStreamSynchronize(c->stream);
-  dev_free(&d_bytes); dev_free(&d_off); dev_free(&d_flag);
+  d_bytes.release(); d_off.release(); d_flag.release();
   if (rc == SMR_OK && h_flag[0]) {
     const uint32_t f = h_flag[0];
     if (f & (IMP_ERR_FORMAT | IMP_ERR_POOL)) return refuse(SMR_ERR_ARG, "smr_state_import: a record's lengths (alignment_size, an alignment's length or its CIGAR length) do not add up to the bytes given for it");

@@ -9,39 +9,35 @@ int ensure_seed_bufs(smr_ctx* c, const DParams& P) {
   const uint32_t nk = 2u << P.lnwin;                      // 2 x 4^(L/2) bins: forward and reverse keys
   if (2 * slots >= 0xFFFFFF00ull) { set_err(c, "batch too large for the seed stage (reads x windows >= 2^31): use smaller batches"); return SMR_ERR_CAPACITY; }
   int rc;
-  if (c->sb_nk < nk) {
-    if ((rc = dev_alloc(c, &c->sb.chist, (size_t)4096 + 1))) return rc;
-    if ((rc = dev_alloc(c, &c->sb.cbase, (size_t)4096 + 2))) return rc;
-    if ((rc = dev_alloc(c, &c->sb.hpre, (size_t)4096 + 2))) return rc;
-    if ((rc = dev_alloc(c, &c->sb.hlist, (size_t)4096 + 2))) return rc;
-    if (!c->sb.rows && (rc = dev_alloc(c, &c->sb.rows, (size_t)SEED_KEY_BLOCKS * 4096))) return rc;
-    if (!c->sb.bcnt && (rc = dev_alloc(c, &c->sb.bcnt, (size_t)SEED_KEY_BLOCKS))) return rc;
-    if (!c->sb.redo && (rc = dev_alloc(c, &c->sb.redo, SEED_REDO_CAP))) return rc;
-    if (!c->sb.sn && (rc = dev_alloc(c, &c->sb.sn, SN_COUNT))) return rc;
-    if ((rc = dev_alloc(c, &c->sb.emap, (size_t)(nk / 2) / 16 + 1))) return rc;
+  SeedScratch& S = c->seed;
+  if (c->sb_nk < nk) {                                     // (sb_nk: the one capacity of the arrays sized by the bins)
+    if ((rc = S.chist.alloc(c, (size_t)4096 + 1)) || (rc = S.cbase.alloc(c, (size_t)4096 + 2)) || (rc = S.hpre.alloc(c, (size_t)4096 + 2)) || (rc = S.hlist.alloc(c, (size_t)4096 + 2))) return rc;
+    if (!S.rows && (rc = S.rows.alloc(c, (size_t)SEED_KEY_BLOCKS * 4096))) return rc;
+    if (!S.bcnt && (rc = S.bcnt.alloc(c, (size_t)SEED_KEY_BLOCKS))) return rc;
+    if (!S.redo && (rc = S.redo.alloc(c, SEED_REDO_CAP))) return rc;
+    if (!S.sn && (rc = S.sn.alloc(c, SN_COUNT))) return rc;
+    if ((rc = S.emap.alloc(c, (size_t)(nk / 2) / 16 + 1))) return rc;
     c->sb_nk = nk;
   }
-  if (c->sb_slots < slots) {
+  if (c->sb_slots < slots) {                               // (sb_slots: the one capacity of the arrays sized by the windows)
     // a forward and a reverse tuple per window; tmp is cut into one region per block of k_seed_keys (the slots of its reads)
-    if ((rc = dev_alloc(c, &c->sb.tmp, 2 * slots))) return rc;
-    if ((rc = dev_alloc(c, &c->sb.mid, 2 * slots))) return rc;
-    if ((rc = dev_alloc(c, &c->sb.srt, 2 * slots))) return rc;
-    for (int d = 0; d < 2; d++) {
-      if ((rc = dev_alloc(c, &c->sb.wseg[d], slots))) return rc;
-      if ((rc = dev_alloc(c, &c->sb.fbits[d], slots / 32 + 2))) return rc;
-    }
-    if ((rc = dev_alloc(c, &c->sb.wbin, 2 * slots / 64 + 2))) return rc;
-    if ((rc = dev_alloc(c, &c->sb.zbits, slots / 32 + 2))) return rc;
-    if ((rc = dev_alloc(c, &c->sb.gflag, slots / 2048 + 2))) return rc;
+    if ((rc = S.tmp.alloc(c, 2 * slots)) || (rc = S.mid.alloc(c, 2 * slots)) || (rc = S.srt.alloc(c, 2 * slots))) return rc;
+    for (int d = 0; d < 2; d++)
+      if ((rc = S.wseg[d].alloc(c, slots)) || (rc = S.fbits[d].alloc(c, slots / 32 + 2))) return rc;
+    if ((rc = S.wbin.alloc(c, 2 * slots / 64 + 2)) || (rc = S.zbits.alloc(c, slots / 32 + 2)) || (rc = S.gflag.alloc(c, slots / 2048 + 2))) return rc;
     // skewed batches: a coarse bin of at least SEED_HOT_BIN_MIN tuples in sub-ranges of SEED_HOT_SUB (their fine histograms); the pieces of hot keys (>= 1024 tuples each)
     c->sb.hbin_min = getenv("SMR_SEED_HOT_BIN") ? (uint32_t)std::max(1, atoi(getenv("SMR_SEED_HOT_BIN"))) : SEED_HOT_BIN_MIN;
     c->sb.hsub = getenv("SMR_SEED_HOT_SUB") ? (uint32_t)std::max(1, atoi(getenv("SMR_SEED_HOT_SUB"))) : SEED_HOT_SUB;
     c->sb.cap_hent = (uint32_t)(2 * slots / c->sb.hsub + 2 * slots / c->sb.hbin_min + 2);
-    if ((rc = dev_alloc(c, &c->sb.hh, (size_t)c->sb.cap_hent * 512))) return rc;
+    if ((rc = S.hh.alloc(c, (size_t)c->sb.cap_hent * 512))) return rc;
     c->sb.cap_pieces = (uint32_t)std::min<uint64_t>(2 * slots / std::max(c->hot_min, 64u) + 2 * slots / SEED_DD_PIECE + 16, 1u << 26);
-    if ((rc = dev_alloc(c, &c->sb.pieces, (size_t)c->sb.cap_pieces))) return rc;
+    if ((rc = S.pieces.alloc(c, (size_t)c->sb.cap_pieces))) return rc;
     c->sb_slots = slots;
   }
+  SeedBufs& v = c->sb;                                     // the kernels' view of the arrays
+  v.chist = S.chist; v.cbase = S.cbase; v.rows = S.rows; v.bcnt = S.bcnt; v.tmp = S.tmp; v.mid = S.mid; v.srt = S.srt; v.zbits = S.zbits; v.gflag = S.gflag; v.wbin = S.wbin;
+  v.emap = S.emap; v.sn = S.sn; v.redo = S.redo; v.hpre = S.hpre; v.hlist = S.hlist; v.hh = S.hh; v.pieces = S.pieces;
+  for (int d = 0; d < 2; d++) { v.wseg[d] = S.wseg[d]; v.fbits[d] = S.fbits[d]; }
   c->sb.hot_min = c->hot_min;
   c->sb.nk = nk; c->sb.nkh = nk / 2;
   c->sb.fb = std::min<uint32_t>(9, P.lnwin); c->sb.nc = nk >> c->sb.fb;       // L <= 20: at most 4096 coarse bins
@@ -104,33 +100,36 @@ int seed_sort(smr_ctx* c, const DevIndex& di, const DParams& P, int pass, SeedBu
   const uint32_t gw = std::max<uint32_t>(1u, (uint32_t)((2 * slots + 63) / 64));     // wave chunks of 64 tuples the batch can have at most (every kernel checks its range)
   const bool many_bins = sb.nc > 2048u;                    // (their three tables take 48 KB of the 160)
   const size_t lds_split = (size_t)3 * ((sb.nc + 1u) & ~1u) * 4 + (size_t)(many_bins ? SEED_SPLIT_PIECE_MANY_BINS : SEED_SPLIT_PIECE) * sizeof(SeedTup), lds_bins = (size_t)SEED_PIECE * sizeof(SeedTup);
-  if (lds_bins > 60 * 1024 && lds_bins > c->bins_lds_attr) { HIPCHK(c, hipFuncSetAttribute((const void*)k_seed_bins, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bins)); HIPCHK(c, hipFuncSetAttribute((const void*)k_seed_hbins_move, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bins)); c->bins_lds_attr = lds_bins; }      // (per context = per device, like split_lds_attr)
-  if (lds_split > 64 * 1024 && lds_split > c->split_lds_attr) {
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_seed_split<SEED_SPLIT_PIECE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_split));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_seed_split<SEED_SPLIT_PIECE_MANY_BINS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_split));
-    c->split_lds_attr = lds_split;
-  }
+  int rc;                                                  // (the high-water marks are per context = per device)
+  if ((rc = raise_lds_limit(c, c->bins_lds_attr, lds_bins, 60 * 1024, k_seed_bins, k_seed_hbins_move))) return rc;
+  if ((rc = raise_lds_limit(c, c->split_lds_attr, lds_split, 64 * 1024, k_seed_split<SEED_SPLIT_PIECE>, k_seed_split<SEED_SPLIT_PIECE_MANY_BINS>))) return rc;
   size_t lds_keys;
   const seed_keys_fn kf = seed_keys_setup(c, sb, lds_keys);
   ev_mark(c, KP_KEYS);
   HIPCHK(c, hipMemsetAsync(sb.sn, 0, SN_COUNT * 4, c->stream));
-  if ((mode & 15) != SEED_KEYS_SHARED) hipLaunchKernelGGL(k_seed_emap, dim3((sb.nkh / 16 + 255) / 256), dim3(256), 0, c->stream, (const uint32_t*)di.lkc, sb.nkh, P.minoccur, sb.emap);
-  hipLaunchKernelGGL(kf, dim3(sb.kb), dim3(64 * SEED_WAVES), lds_keys, c->stream, dreads(c), P, pass, sb, (const RWork*)c->b->d_rw, c->b->d_ctr, mode);
+  if ((mode & 15) != SEED_KEYS_SHARED) launch(c, k_seed_emap, dim3((sb.nkh / 16 + 255) / 256), dim3(256), 0, (const uint32_t*)di.lkc, sb.nkh, P.minoccur, sb.emap);
+  launch(c, kf, dim3(sb.kb), dim3(64 * SEED_WAVES), lds_keys, dreads(c), P, pass, sb, (const RWork*)c->b->d_rw, c->b->d_ctr, mode);
   // the two-level sort of the stage's forward and reverse tuples (smr_seed.hpp)
   ev_mark(c, KP_SPLIT);                                    // (with the scans of the block histograms in front of it)
-  hipLaunchKernelGGL(k_seed_colscan, dim3((sb.nc + 63) / 64), dim3(1024), 0, c->stream, sb);
-  hipLaunchKernelGGL(k_seed_cscan, dim3(1), dim3(1024), 0, c->stream, sb, c->b->d_ctr);
-  hipLaunchKernelGGL(k_seed_wbin, dim3((gw + 255) / 256), dim3(256), 0, c->stream, sb);
-  if (many_bins) hipLaunchKernelGGL(k_seed_split<SEED_SPLIT_PIECE_MANY_BINS>, dim3(sb.kb), dim3(1024), lds_split, c->stream, sb);
-  else hipLaunchKernelGGL(k_seed_split<SEED_SPLIT_PIECE>, dim3(sb.kb), dim3(1024), lds_split, c->stream, sb);
+  launch(c, k_seed_colscan, dim3((sb.nc + 63) / 64), dim3(1024), 0, sb);
+  launch(c, k_seed_cscan, dim3(1), dim3(1024), 0, sb, c->b->d_ctr);
+  launch(c, k_seed_wbin, dim3((gw + 255) / 256), dim3(256), 0, sb);
+  launch(c, many_bins ? k_seed_split<SEED_SPLIT_PIECE_MANY_BINS> : k_seed_split<SEED_SPLIT_PIECE>, dim3(sb.kb), dim3(1024), lds_split, sb);
   ev_mark(c, KP_BINS);
-  hipLaunchKernelGGL(k_seed_bins, dim3(sb.nc), dim3(1024), lds_bins, c->stream, sb);
+  launch(c, k_seed_bins, dim3(sb.nc), dim3(1024), lds_bins, sb);
   // the coarse bins that are far larger than the others, several blocks each (none on evenly spread keys: three empty launches)
   const uint32_t gh = std::min<uint32_t>(sb.cap_hent, (uint32_t)c->n_cu * 2u);       // (grids that loop: an empty launch should cost a launch, not 2 000 blocks)
-  hipLaunchKernelGGL(k_seed_hbins_hist, dim3(gh), dim3(1024), 0, c->stream, sb);
-  hipLaunchKernelGGL(k_seed_hbins_scan, dim3(std::min<uint32_t>(sb.nc, 128u)), dim3(1024), 0, c->stream, sb);
-  hipLaunchKernelGGL(k_seed_hbins_move, dim3(gh), dim3(1024), lds_bins, c->stream, sb);
+  launch(c, k_seed_hbins_hist, dim3(gh), dim3(1024), 0, sb);
+  launch(c, k_seed_hbins_scan, dim3(std::min<uint32_t>(sb.nc, 128u)), dim3(1024), 0, sb);
+  launch(c, k_seed_hbins_move, dim3(gh), dim3(1024), lds_bins, sb);
   return SMR_OK;
+}
+
+// the forward (dir 0) / reverse instantiations of the three search kernels
+struct SeedDirKernels { decltype(&k_seed_pg<0>) pg; decltype(&k_seed_search<0>) search; decltype(&k_seed_prop<0>) prop; };
+SeedDirKernels seed_dir_kernels(int dir) {
+  if (dir == 0) return {k_seed_pg<0>, k_seed_search<0>, k_seed_prop<0>};
+  return {k_seed_pg<1>, k_seed_search<1>, k_seed_prop<1>};
 }
 
 // the searches of one sorted array: forward (dir 0) or reverse launch, the overflow redo, the repeated seeds' windows
@@ -141,21 +140,16 @@ int seed_search(smr_ctx* c, const DevIndex& di, const DParams& P, int pass, cons
   const uint32_t gp = c->pg_grid ? std::min<uint32_t>((gw + 7u) & ~7u, c->pg_grid) : ((gw + 7u) & ~7u);
   const uint32_t gd = std::min<uint32_t>(sb.cap_pieces, (uint32_t)c->n_cu * 8u);
   HIPCHK(c, hipMemsetAsync(&sb.sn[SN_REDO], 0, 4, c->stream));
-  if (dir == 0) {
-    hipLaunchKernelGGL(k_seed_pg<0>, dim3(gp), dim3(64), lds_pg, c->stream, dindex(di), P, pass, sb, c->ccap, c->d_pool, pool_words, c->b->d_ctr, c->pg_swz);
-    hipLaunchKernelGGL(k_seed_search<0>, dim3(gr), dim3(64), lds, c->stream, dindex(di), P, pass, sb, c->hcap, c->d_pool, pool_words, c->b->d_ctr, (const uint32_t*)sb.redo);
-    if (sb.hot_min) hipLaunchKernelGGL(k_seed_prop<0>, dim3(gd), dim3(256), 0, c->stream, sb, c->b->d_ctr);
-  } else {
-    hipLaunchKernelGGL(k_seed_pg<1>, dim3(gp), dim3(64), lds_pg, c->stream, dindex(di), P, pass, sb, c->ccap, c->d_pool, pool_words, c->b->d_ctr, c->pg_swz);
-    hipLaunchKernelGGL(k_seed_search<1>, dim3(gr), dim3(64), lds, c->stream, dindex(di), P, pass, sb, c->hcap, c->d_pool, pool_words, c->b->d_ctr, (const uint32_t*)sb.redo);
-    if (sb.hot_min) hipLaunchKernelGGL(k_seed_prop<1>, dim3(gd), dim3(256), 0, c->stream, sb, c->b->d_ctr);
-  }
+  const SeedDirKernels K = seed_dir_kernels(dir);
+  launch(c, K.pg, dim3(gp), dim3(64), lds_pg, dindex(di), P, pass, sb, c->ccap, c->d_pool, pool_words, c->b->d_ctr, c->pg_swz);
+  launch(c, K.search, dim3(gr), dim3(64), lds, dindex(di), P, pass, sb, c->hcap, c->d_pool, pool_words, c->b->d_ctr, sb.redo);
+  if (sb.hot_min) launch(c, K.prop, dim3(gd), dim3(256), 0, sb, c->b->d_ctr);
   return SMR_OK;
 }
 
 // the six shared arrays of the selected batch (see SharedSort); usable = false when a condition above does not hold
 int ensure_shared_sort(smr_ctx* c, const DevIndex& di, const DParams& P) {
-  SharedSort& S = *c->shared;
+  SharedSort& S = c->shared;
   const bool same = S.batch == c->b && S.gen == c->b->gen && S.lnwin == P.lnwin && S.skip[0] == P.skip[0] && S.skip[1] == P.skip[1] && S.skip[2] == P.skip[2] && S.n == c->b->n;
   if (same) return SMR_OK;
   S.batch = c->b; S.gen = c->b->gen; S.lnwin = P.lnwin; S.n = c->b->n; S.max_len = c->b->max_len;
@@ -163,7 +157,7 @@ int ensure_shared_sort(smr_ctx* c, const DevIndex& di, const DParams& P) {
   S.usable = false;
   for (int s = 0; s < 2; s++) for (int p = 0; p < 3; p++) S.set[s][p].built = false;
   const size_t aw = ((size_t)c->b->n + 255) / 256 * 8 + 4;
-  if (S.abits_words < aw) { int rc = dev_alloc(c, &S.abits, aw); if (rc) return rc; S.abits_words = aw; }
+  { int rc = S.abits.reserve(c, aw); if (rc) return rc; }
   DParams Q = P; Q.minoccur = 0;
   for (int p = 0; p < 3; p++) {
     if (p > 0 && P.skip[p] == P.skip[p - 1]) continue;
@@ -173,11 +167,11 @@ int ensure_shared_sort(smr_ctx* c, const DevIndex& di, const DParams& P) {
       SharedSet& T = S.set[s][p];
       int rc;
       if (S.cap[p] < cap || !T.srt) {
-        if ((rc = dev_alloc(c, &T.srt, (size_t)cap)) || (rc = dev_alloc(c, &T.wbin, (size_t)(cap / 64 + 2))) ||
-            (!T.cbase && ((rc = dev_alloc(c, &T.cbase, (size_t)4096 + 2)) || (rc = dev_alloc(c, &T.sn, (size_t)SN_COUNT))))) {
+        if ((rc = T.srt.alloc(c, (size_t)cap)) || (rc = T.wbin.alloc(c, (size_t)(cap / 64 + 2))) ||
+            (!T.cbase && ((rc = T.cbase.alloc(c, (size_t)4096 + 2)) || (rc = T.sn.alloc(c, (size_t)SN_COUNT))))) {
           // no room for the six arrays (17 GB at 8 M reads; several contexts on one device): every part sorts for itself, as without the option
           (void)hipGetLastError();
-          for (int s2 = 0; s2 < 2; s2++) for (int p2 = 0; p2 < 3; p2++) { SharedSet& U = S.set[s2][p2]; dev_free(&U.srt); dev_free(&U.wbin); U.built = false; }
+          for (int s2 = 0; s2 < 2; s2++) for (int p2 = 0; p2 < 3; p2++) { SharedSet& U = S.set[s2][p2]; U.srt.release(); U.wbin.release(); U.built = false; }
           for (int p2 = 0; p2 < 3; p2++) S.cap[p2] = 0;
           c->seed_shared = 0;
           if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: no device memory for the shared seed sort: every index part sorts for itself\n");
@@ -225,23 +219,15 @@ int launch_seed(smr_ctx* c, const DevIndex& di, const DParams& P, int pass, bool
   const size_t lds = (size_t)SEED_LDS_WORDS(c->hcap) * 4, lds_pg1 = (size_t)PG_LDS_WORDS(c->ccap) * 4;
   const size_t lds_pg = lds_pg1 + (getenv("SMR_PG_LDS_PAD") ? (size_t)atoi(getenv("SMR_PG_LDS_PAD")) : 0);      // (the variable: occupancy experiments)
   // lists of more than 128 hits per search (a crafted neighbourhood: SEED_HCAP_MAX) take more than the default 64 KB of dynamic LDS
-  if (lds_pg > 64 * 1024 && lds_pg > c->pg_lds_attr) {
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_seed_pg<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pg));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_seed_pg<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pg));
-    c->pg_lds_attr = lds_pg;
-  }
-  if (lds > 64 * 1024 && lds > c->search_lds_attr) {
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_seed_search<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_seed_search<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    c->search_lds_attr = lds;
-  }
+  if ((rc = raise_lds_limit(c, c->pg_lds_attr, lds_pg, 64 * 1024, seed_dir_kernels(0).pg, seed_dir_kernels(1).pg))) return rc;
+  if ((rc = raise_lds_limit(c, c->search_lds_attr, lds, 64 * 1024, seed_dir_kernels(0).search, seed_dir_kernels(1).search))) return rc;
   const uint32_t pool_words = (uint32_t)std::min<uint64_t>(c->pool_words, 0x7FFFFFF0ull);
   const uint32_t gw = std::max<uint32_t>(1u, (uint32_t)((2 * slots + 63) / 64));     // wave chunks of 64 tuples the batch can have at most (every kernel checks its range)
   // one sort for several parts?  (strand < 0: smr_seed_scan, the test seam of one (strand, pass) -- always the part's own sort)
   bool shared = false;
-  if (strand >= 0 && c->seed_shared && !c->seed_exact && P.minoccur == 0 && (more_parts || c->seed_shared >= 2 || (c->shared->usable && c->shared->batch == c->b && c->shared->gen == c->b->gen))) {
+  if (strand >= 0 && c->seed_shared && !c->seed_exact && P.minoccur == 0 && (more_parts || c->seed_shared >= 2 || (c->shared.usable && c->shared.batch == c->b && c->shared.gen == c->b->gen))) {
     if ((rc = ensure_shared_sort(c, di, P))) return rc;
-    shared = c->shared->usable && c->shared->set[strand][pass].built;
+    shared = c->shared.usable && c->shared.set[strand][pass].built;
   }
   for (int d = 0; d < 2; d++) HIPCHK(c, hipMemsetAsync(sb.fbits[d], 0, (size_t)(slots / 32 + 2) * 4, c->stream));         // no window has a hit segment yet
   HIPCHK(c, hipMemsetAsync(sb.zbits, 0, (size_t)(slots / 32 + 2) * 4, c->stream));
@@ -251,29 +237,25 @@ int launch_seed(smr_ctx* c, const DevIndex& di, const DParams& P, int pass, bool
   if (own) {
     if ((rc = seed_sort(c, di, P, pass, sb, shared ? SEED_KEYS_AMB : SEED_KEYS_ALL))) return rc;
     const uint32_t gd = std::min<uint32_t>(sb.cap_pieces, (uint32_t)c->n_cu * 8u);
-    if (sb.hot_min) hipLaunchKernelGGL(k_seed_dedup, dim3(gd), dim3(256), 0, c->stream, sb);
+    if (sb.hot_min) launch(c, k_seed_dedup, dim3(gd), dim3(256), 0, sb);
   }
   SeedBufs sh = sb;                                          // the shared array of this (strand, pass), filtered by the reads that are in the launch
   if (shared) {
-    const SharedSet& T = c->shared->set[strand][pass];
-    sh.srt = T.srt; sh.wbin = T.wbin; sh.cbase = T.cbase; sh.sn = T.sn; sh.cap_tuples = (uint32_t)std::min<uint64_t>(c->shared->cap[pass], 0xFFFFFFFFull);
-    sh.abits = c->shared->abits; sh.hot_min = 0;
+    const SharedSet& T = c->shared.set[strand][pass];
+    sh.srt = T.srt; sh.wbin = T.wbin; sh.cbase = T.cbase; sh.sn = T.sn; sh.cap_tuples = (uint32_t)std::min<uint64_t>(c->shared.cap[pass], 0xFFFFFFFFull);
+    sh.abits = c->shared.abits; sh.hot_min = 0;
     c->n_seed_shared++;
-    hipLaunchKernelGGL(k_seed_active, dim3((c->b->n + 255u) / 256u), dim3(256), 0, c->stream, c->b->n, pass, strand == 0 ? 1 : 0, (const RWork*)c->b->d_rw, c->shared->abits);
+    launch(c, k_seed_active, dim3((c->b->n + 255u) / 256u), dim3(256), 0, c->b->n, pass, strand == 0 ? 1 : 0, (const RWork*)c->b->d_rw, c->shared.abits);
   }
-  const uint32_t* no_redo = nullptr;
-  if (c->seed_exact) {
-    ev_mark(c, KP_PG0);
-    hipLaunchKernelGGL(k_seed_search<0>, dim3(gw), dim3(64), lds, c->stream, dindex(di), P, pass, sb, c->hcap, c->d_pool, pool_words, c->b->d_ctr, no_redo);
-    ev_mark(c, KP_PG1);
-    hipLaunchKernelGGL(k_seed_search<1>, dim3(gw), dim3(64), lds, c->stream, dindex(di), P, pass, sb, c->hcap, c->d_pool, pool_words, c->b->d_ctr, no_redo);
-  } else {
-    // pigeonhole search; the (rare) waves whose candidate pool overflowed are searched again by the DFS kernel
-    for (int dir = 0; dir < 2; dir++) {
-      ev_mark(c, dir ? KP_PG1 : KP_PG0);
-      if (shared && (rc = seed_search(c, di, P, pass, sh, dir, pool_words, lds, lds_pg))) return rc;
-      if (own && (rc = seed_search(c, di, P, pass, sb, dir, pool_words, lds, lds_pg))) return rc;
+  for (int dir = 0; dir < 2; dir++) {
+    ev_mark(c, dir ? KP_PG1 : KP_PG0);
+    if (c->seed_exact) {                                     // the DFS kernel for every wave (no redo list)
+      launch(c, seed_dir_kernels(dir).search, dim3(gw), dim3(64), lds, dindex(di), P, pass, sb, c->hcap, c->d_pool, pool_words, c->b->d_ctr, nullptr);
+      continue;
     }
+    // pigeonhole search; the (rare) waves whose candidate pool overflowed are searched again by the DFS kernel
+    if (shared && (rc = seed_search(c, di, P, pass, sh, dir, pool_words, lds, lds_pg))) return rc;
+    if (own && (rc = seed_search(c, di, P, pass, sb, dir, pool_words, lds, lds_pg))) return rc;
   }
   if (getenv("SMR_SEED_DEBUG")) {                            // (debug aid: synchronises)
     uint32_t sn[SN_COUNT], hent = 0, sn2[SN_COUNT] = {0};
@@ -285,7 +267,7 @@ int launch_seed(smr_ctx* c, const DevIndex& di, const DParams& P, int pass, bool
             pass, sn[SN_TUPLES], sn[SN_FWD], hent, sn[SN_PIECES], sb.hot_min, sn[SN_REDO], shared ? "in use" : "no", sn2[SN_TUPLES]);
   }
   ev_mark(c, KP_FINISH);
-  hipLaunchKernelGGL(k_seed_finish, dim3((c->b->n + 255) / 256), dim3(256), 0, c->stream, dreads(c), P, pass, sb, c->b->d_work, c->b->d_rw, c->d_pool, pool_words, c->b->d_ctr);
+  launch(c, k_seed_finish, dim3((c->b->n + 255) / 256), dim3(256), 0, dreads(c), P, pass, sb, c->b->d_work, c->b->d_rw, c->d_pool, pool_words, c->b->d_ctr);
   ev_stop(c);
   HIPCHK(c, hipGetLastError());
   return SMR_OK;

@@ -236,21 +236,6 @@ extern "C" int smr_sw_long_rows(int m) { return smr::sw_long_rows(m); }
 // k_sw16 at the same seam: the kernel as the candidate walk launches it (smr_walk.hpp) -- packed records of the selected batch, WTasks, the two
 // index lists and the counters as k_walk leaves them -- and, for the tasks scored with end cells, the begin-cell tasks as k_begins_prep makes them.
 // =================================================================================================
-namespace {
-int sw16_launch(smr_ctx* c, int rows, uint32_t blocks, const DReads& rd, const DIndex& ix, const DParams& P, const WTask* tk, const uint32_t* t1, const uint32_t* t2,
-                const unsigned long long* wc, uint2* res) {
-  const uint32_t gb = blocks ? blocks : (uint32_t)c->n_cu * 4u * (uint32_t)SW16_WAVES(rows);
-#define SW16_ARGS rd, ix, P, tk, t1, t2, wc, res
-  if (rows == 13) hipLaunchKernelGGL(k_sw16<13>, dim3(gb), dim3(64), 0, c->stream, SW16_ARGS);
-  else if (rows == 19) hipLaunchKernelGGL(k_sw16<19>, dim3(gb), dim3(64), 0, c->stream, SW16_ARGS);
-  else if (rows == 26) hipLaunchKernelGGL(k_sw16<26>, dim3(gb), dim3(64), 0, c->stream, SW16_ARGS);
-  else hipLaunchKernelGGL(k_sw16<32>, dim3(gb), dim3(64), 0, c->stream, SW16_ARGS);
-#undef SW16_ARGS
-  HIPCHK(c, hipGetLastError());
-  return SMR_OK;
-}
-}  // namespace
-
 extern "C" int smr_sw16_batch(smr_ctx* c, uint32_t n_tasks, const smr_sw16_task* tasks, const uint8_t* ref, uint64_t ref_len, int force_any_n,
                               int match, int mismatch, int score_N, int gap_open, int gap_ext, uint32_t filters, int rows, uint32_t blocks, int32_t* out) {
   if (!c || (n_tasks && (!tasks || !out)) || (ref_len && !ref)) return SMR_ERR_ARG;
@@ -305,7 +290,8 @@ extern "C" int smr_sw16_batch(smr_ctx* c, uint32_t n_tasks, const smr_sw16_task*
   if (!ib.empty()) HIPCHK(c, hipMemcpyAsync(d_ib, ib.data(), ib.size() * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_wc, wc, sizeof wc, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(d_res, 0xEE, (size_t)n_tasks * sizeof(uint2), c->stream));
-  { int rc = sw16_launch(c, rows, blocks, dreads(c), ix, P, d_tk, d_ia, d_ib, d_wc, d_res); if (rc) return rc; }
+  launch_sw16(c, rows, -1, blocks, dreads(c), ix, P, d_tk, d_ia, d_ib, d_wc, d_res);
+  HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(res.data(), d_res, (size_t)n_tasks * sizeof(uint2), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   // begin cells (k_begins_prep, stage 1): rows back from the end row, columns back from the end column, all in the list with end cells
@@ -340,7 +326,8 @@ extern "C" int smr_sw16_batch(smr_ctx* c, uint32_t n_tasks, const smr_sw16_task*
   HIPCHK(c, hipMemcpyAsync(d_ia, beg.data(), beg.size() * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_wc, wc, sizeof wc, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(d_res, 0xEE, (size_t)n_tasks * sizeof(uint2), c->stream));
-  { int rc = sw16_launch(c, rows, blocks, dreads(c), ix, P, d_tk, d_ia, d_ib, d_wc, d_res); if (rc) return rc; }
+  launch_sw16(c, rows, -1, blocks, dreads(c), ix, P, d_tk, d_ia, d_ib, d_wc, d_res);
+  HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(res.data(), d_res, (size_t)n_tasks * sizeof(uint2), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (uint32_t i : beg) {

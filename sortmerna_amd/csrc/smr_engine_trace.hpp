@@ -15,6 +15,62 @@ __global__ void k_trace_collect(uint32_t n, uint32_t slots, const RState* __rest
   if (take) tasks[o] = i;
 }
 
+namespace {
+// A throw-away batch / reference set for the seams below: n reads (one letter per byte) packed like an upload packs them, each with ONE stored
+// alignment against its own reference window (reference i = window i).  The caller fills st / al (and whatever else its pass reads: b.d_cigar)
+// between pack() and upload(); upload() puts everything on the device and selects the batch; leaving the scope waits for the stream, selects the
+// batch that was selected before and frees.
+struct TempBatch {
+  smr_ctx* c; Batch* keep; Batch b; DevIndex di;
+  std::vector<uint32_t> words, lens; std::vector<uint64_t> rec_off;
+  std::vector<RState> st; std::vector<AlignRec> al;
+  explicit TempBatch(smr_ctx* c_) : c(c_), keep(c_->b) {}
+  TempBatch(const TempBatch&) = delete;
+  TempBatch& operator=(const TempBatch&) = delete;
+  ~TempBatch() { (void)hipStreamSynchronize(c->stream); c->b = keep; }
+  // the reads (each of 1 .. 65535 letters: the caller has looked); the stored alignments start out as "one hit, strand 1, reference i, readlen = the read's length"
+  void pack(uint32_t n, const uint8_t* reads, const uint64_t* read_off) {
+    lens.resize(n); rec_off.assign((size_t)n + 1, 0); st.resize(n); al.resize(n);
+    uint32_t max_len = 1;
+    for (uint32_t i = 0; i < n; i++) {
+      const uint64_t m = read_off[i + 1] - read_off[i];
+      const uint32_t cw = (uint32_t)((m + 15) >> 4), mw = (uint32_t)((m + 31) >> 5);
+      rec_off[i] = words.size();
+      words.resize(words.size() + cw + mw, 0u);
+      uint32_t* rec = words.data() + rec_off[i];
+      for (uint64_t q = 0; q < m; q++) {
+        const uint8_t ch = reads[read_off[i] + q];
+        if (ch > 3) rec[cw + (q >> 5)] |= 1u << (q & 31); else rec[q >> 4] |= (uint32_t)ch << ((q & 15) * 2);
+      }
+      lens[i] = (uint32_t)m; max_len = std::max(max_len, (uint32_t)m);
+      memset(&st[i], 0, sizeof(RState)); st[i].n_align = 1; st[i].is_hit = 1;
+      memset(&al[i], 0, sizeof(AlignRec)); al[i].ref_num = i; al[i].readlen = (uint32_t)m; al[i].strand = 1;
+    }
+    rec_off[n] = words.size();
+    b.n = n; b.max_len = max_len; b.slots = 1; b.used = true;
+  }
+  int upload(const uint8_t* refs, const uint64_t* ref_off) {
+    const size_t n = b.n, nref = (size_t)ref_off[n];
+    int rc;
+    c->b = &b;
+    if ((rc = b.d_words.alloc(c, words.size() + 4)) || (rc = b.d_rec_off.alloc(c, rec_off.size())) || (rc = b.d_len.alloc(c, n)) || (rc = b.d_saved.alloc(c, n)) ||
+        (rc = b.d_saved_aln.alloc(c, n)) || (rc = b.d_ctr.alloc(c, C_TOTAL)) || (rc = di.ref_seq.alloc(c, nref + 64)) || (rc = di.ref_off.alloc(c, n + 1))) return rc;
+    HIPCHK(c, hipMemsetAsync(b.d_words + words.size(), 0, 16, c->stream));             // (the slack the kernels may read ahead into)
+    HIPCHK(c, hipMemcpyAsync(b.d_words, words.data(), words.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.d_rec_off, rec_off.data(), rec_off.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.d_len, lens.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.d_saved, st.data(), n * sizeof(RState), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.d_saved_aln, al.data(), n * sizeof(AlignRec), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.d_ctr, 0, C_TOTAL * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(di.ref_seq + nref, 0, 64, c->stream));
+    if (nref) HIPCHK(c, hipMemcpyAsync(di.ref_seq, refs, nref, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(di.ref_off, ref_off, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    di.n_refs = b.n; di.lnwin = 18; di.used = true;
+    return SMR_OK;
+  }
+};
+}  // namespace
+
 // CIGARs for every stored alignment of the selected batch that lacks one and belongs to (p->index_num, p->part), whose reference sequences are di's
 static int traceback_core(smr_ctx* c, const DevIndex& di, const smr_params* p) {
   int rc;
@@ -22,11 +78,11 @@ static int traceback_core(smr_ctx* c, const DevIndex& di, const smr_params* p) {
   DParams P = make_dparams(c, di, p);
   c->b->fetched = false;
   const uint64_t ntot = (uint64_t)c->b->n * c->b->slots;
-  if (c->tasks_cap < ntot) { if ((rc = dev_alloc(c, &c->d_tasks, 2 * ntot))) return rc; c->tasks_cap = ntot; }     // two lists: in / handed on
+  if ((rc = c->d_tasks.reserve(c, 2 * ntot))) return rc;     // two lists: in / handed on
   if (c->b->cigar_words == 0) {
     c->b->cigar_words = std::max<uint64_t>(ntot * 16, 1u << 20);
     if (const char* e = getenv("SMR_CIGAR_POOL_WORDS")) c->b->cigar_words = std::max<uint64_t>(strtoull(e, nullptr, 10), 16);   // debugging aid: start small, exercise the regrow
-    if ((rc = dev_alloc(c, &c->b->d_cigar, c->b->cigar_words))) return rc;
+    if ((rc = c->b->d_cigar.alloc(c, c->b->cigar_words))) return rc;
   }
   uint32_t ml, rf; size_t chain_bytes;
   chain_lds(c, P, ml, rf, chain_bytes);                    // ml / rf: the longest read / reference window an alignment can span (edges as k_chain takes them)
@@ -48,11 +104,11 @@ static int traceback_core(smr_ctx* c, const DevIndex& di, const smr_params* p) {
     if (h[C_ERR_TRACE]) { set_err(c, "banded traceback left the band for some alignments (internal error)"); return SMR_ERR_CAPACITY; }
     if (h[C_ERR_CIGAR]) {
       // grow the CIGAR pool, keeping what is already there; the failed claims moved the cursor past the end: back to the old capacity
-      const uint64_t w = c->b->cigar_words * 2; uint32_t* nw = nullptr;
+      const uint64_t w = c->b->cigar_words * 2; DevBuf<uint32_t> nw;
       if (w > 0xFFFFFFF0ull) { set_err(c, "CIGAR pool exceeds 2^32 words"); return SMR_ERR_CAPACITY; }
-      HIPCHK(c, hipMalloc((void**)&nw, w * 4));
+      if ((r2 = nw.alloc(c, w))) return r2;
       HIPCHK(c, hipMemcpy(nw, c->b->d_cigar, c->b->cigar_words * 4, hipMemcpyDeviceToDevice));
-      (void)hipFree(c->b->d_cigar); c->b->d_cigar = nw;
+      c->b->d_cigar = std::move(nw);
       const unsigned long long cur = std::min<unsigned long long>(h[C_CIGAR_CURSOR], c->b->cigar_words);
       c->b->cigar_words = w;
       HIPCHK(c, hipMemcpy(&c->b->d_ctr[C_CIGAR_CURSOR], &cur, 8, hipMemcpyHostToDevice));
@@ -65,7 +121,7 @@ static int traceback_core(smr_ctx* c, const DevIndex& di, const smr_params* p) {
   for (int attempt = 0; attempt < 40; attempt++) {
     t_in = c->d_tasks; t_out = c->d_tasks + ntot;
     HIPCHK(c, hipMemsetAsync(&c->b->d_ctr[C_TRACE_NEXT], 0, 8, c->stream));
-    hipLaunchKernelGGL(k_trace_collect, dim3((uint32_t)((ntot + 1023) / 1024)), dim3(1024), 0, c->stream, c->b->n, c->b->slots, c->b->d_saved, c->b->d_saved_aln, P.index_num, P.part, t_in, c->b->d_ctr);
+    launch(c, k_trace_collect, dim3((uint32_t)((ntot + 1023) / 1024)), dim3(1024), 0, c->b->n, c->b->slots, c->b->d_saved, c->b->d_saved_aln, P.index_num, P.part, t_in, c->b->d_ctr);
     if ((rc = read_ctr(c, h))) return rc;
     uint32_t n_tasks = (uint32_t)h[C_TRACE_NEXT];
     if (n_tasks == 0) return SMR_OK;
@@ -78,10 +134,8 @@ static int traceback_core(smr_ctx* c, const DevIndex& di, const smr_params* p) {
       if (lds > 64 * 1024) break;
       const uint32_t blocks = std::min<uint32_t>((n_tasks + ng - 1) / ng, (uint32_t)c->n_cu * 16u);
       if ((rc = before())) return rc;
-      if (G == 8) hipLaunchKernelGGL(k_trace_band<8>, dim3(blocks), dim3(64), lds, c->stream, dreads(c), dindex(di), P, (const uint32_t*)t_in, n_tasks, c->b->d_saved_aln,
-                                     c->b->d_cigar, pool_words, c->b->d_ctr, t_out, ml, rf, row_pairs);
-      else hipLaunchKernelGGL(k_trace_band<16>, dim3(blocks), dim3(64), lds, c->stream, dreads(c), dindex(di), P, (const uint32_t*)t_in, n_tasks, c->b->d_saved_aln,
-                              c->b->d_cigar, pool_words, c->b->d_ctr, t_out, ml, rf, row_pairs);
+      launch(c, G == 8 ? k_trace_band<8> : k_trace_band<16>, dim3(blocks), dim3(64), lds, dreads(c), dindex(di), P, t_in, n_tasks, c->b->d_saved_aln,
+             c->b->d_cigar, pool_words, c->b->d_ctr, t_out, ml, rf, row_pairs);
       st = after(n_tasks);
     }
     // wide kernel: one wave per alignment, band caps growing level by level up to a band that covers the whole window
@@ -100,17 +154,15 @@ static int traceback_core(smr_ctx* c, const DevIndex& di, const smr_params* p) {
       // smaller device, fewer blocks run instead of the allocation failing)
       size_t mem_free = 0, mem_total = 0;
       if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) mem_free = (size_t)16 << 30;
-      const uint64_t budget = std::min<uint64_t>(16ull << 30, std::max<uint64_t>(c->trflags_bytes, (uint64_t)mem_free / 4));
+      const uint64_t budget = std::min<uint64_t>(16ull << 30, std::max<uint64_t>(c->d_trflags.cap(), (uint64_t)mem_free / 4));
       uint32_t blocks = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(budget / per_block, 1), (uint64_t)c->n_cu * tw_bpc);
       blocks = std::min(blocks, n_tasks);
       const size_t lds_tw = (size_t)TR_CIG_STAGE * 4 + (rows_lds ? (size_t)wcap * 8 : 0);
-      if (c->trflags_bytes < (uint64_t)blocks * flags_cap) { if ((rc = dev_alloc(c, &c->d_trflags, (size_t)blocks * flags_cap))) return rc; c->trflags_bytes = (uint64_t)blocks * flags_cap; }
-      if (!rows_lds && c->trrows_ints < (uint64_t)blocks * 2 * wcap) { if ((rc = dev_alloc(c, &c->d_trrows, (size_t)blocks * 2 * wcap))) return rc; c->trrows_ints = (uint64_t)blocks * 2 * wcap; }
+      if ((rc = c->d_trflags.reserve(c, (size_t)blocks * flags_cap))) return rc;
+      if (!rows_lds && (rc = c->d_trrows.reserve(c, (size_t)blocks * 2 * wcap))) return rc;
       if ((rc = before())) return rc;
-      if (rows_lds) hipLaunchKernelGGL(k_trace_wide<true>, dim3(blocks), dim3(64), lds_tw, c->stream, dreads(c), dindex(di), P, (const uint32_t*)t_in, n_tasks,
-                                       c->b->d_saved_aln, c->b->d_cigar, pool_words, c->b->d_ctr, t_out, (int)band, c->d_trflags, (unsigned long long)flags_cap, c->d_trrows, wcap);
-      else hipLaunchKernelGGL(k_trace_wide<false>, dim3(blocks), dim3(64), lds_tw, c->stream, dreads(c), dindex(di), P, (const uint32_t*)t_in, n_tasks,
-                              c->b->d_saved_aln, c->b->d_cigar, pool_words, c->b->d_ctr, t_out, (int)band, c->d_trflags, (unsigned long long)flags_cap, c->d_trrows, wcap);
+      launch(c, rows_lds ? k_trace_wide<true> : k_trace_wide<false>, dim3(blocks), dim3(64), lds_tw, dreads(c), dindex(di), P, t_in, n_tasks,
+             c->b->d_saved_aln, c->b->d_cigar, pool_words, c->b->d_ctr, t_out, (int)band, c->d_trflags, flags_cap, c->d_trrows, wcap);
       st = after(n_tasks);
     }
     if (st < 0) return st;
@@ -142,76 +194,35 @@ extern "C" int smr_cigar_batch(smr_ctx* c, uint32_t n_pairs, const uint8_t* read
   if (n_pairs == 0) return SMR_OK;
   smr_params p; smr_params_default(&p);
   p.match = match; p.mismatch = mismatch; p.score_N = score_N; p.gap_open = gap_open; p.gap_ext = gap_ext; p.edges = 0;
-  Batch* keep = c->b;
-  Batch tmp;
-  DevIndex di;
-  std::vector<uint32_t> words, lens(n_pairs);
-  std::vector<uint64_t> rec_off((size_t)n_pairs + 1, 0);
-  std::vector<RState> st(n_pairs);
-  std::vector<AlignRec> al(n_pairs);
-  uint32_t max_len = 1; uint64_t max_ref = 1;
+  uint64_t max_ref = 1;
   for (uint32_t i = 0; i < n_pairs; i++) {
     const uint64_t m = read_off[i + 1] - read_off[i], n = ref_off[i + 1] - ref_off[i];
     if (m == 0 || n == 0 || m > 0xFFFFu) { set_err(c, "smr_cigar_batch: empty or oversized pair"); return SMR_ERR_ARG; }
-    const uint32_t cw = (uint32_t)((m + 15) >> 4), mw = (uint32_t)((m + 31) >> 5);
-    rec_off[i] = words.size();
-    words.resize(words.size() + cw + mw, 0u);
-    uint32_t* rec = words.data() + rec_off[i];
-    for (uint64_t q = 0; q < m; q++) {
-      const uint8_t ch = reads[read_off[i] + q];
-      if (ch > 3) rec[cw + (q >> 5)] |= 1u << (q & 31); else rec[q >> 4] |= (uint32_t)ch << ((q & 15) * 2);
-    }
-    lens[i] = (uint32_t)m; max_len = std::max(max_len, (uint32_t)m); max_ref = std::max(max_ref, n);
-    memset(&st[i], 0, sizeof(RState)); st[i].n_align = 1; st[i].is_hit = 1;
-    memset(&al[i], 0, sizeof(AlignRec));
-    al[i].ref_num = i; al[i].ref_begin1 = 0; al[i].ref_end1 = (int32_t)n - 1; al[i].read_begin1 = 0; al[i].read_end1 = (int32_t)m - 1;
-    al[i].readlen = (uint32_t)m; al[i].score1 = scores[i]; al[i].strand = 1;
+    max_ref = std::max(max_ref, n);
   }
-  rec_off[n_pairs] = words.size();
+  TempBatch t(c);
+  t.pack(n_pairs, reads, read_off);
+  for (uint32_t i = 0; i < n_pairs; i++) {                 // one stored alignment per pair, spanning both windows
+    AlignRec& a = t.al[i];
+    a.ref_begin1 = 0; a.ref_end1 = (int32_t)(ref_off[i + 1] - ref_off[i]) - 1; a.read_begin1 = 0; a.read_end1 = (int32_t)t.lens[i] - 1; a.score1 = scores[i];
+  }
+  const uint32_t max_len = t.b.max_len;
   p.edges = (int32_t)std::min<uint64_t>(max_ref > max_len ? (max_ref - max_len + 1) / 2 : 0, 0x3FFFFFFF);   // so that the LDS window bound covers the longest reference window
-  tmp.n = n_pairs; tmp.max_len = max_len; tmp.slots = 1; tmp.used = true;
-  int rc = SMR_OK;
-  auto run = [&]() -> int {
-    int r2;
-    c->b = &tmp;
-    if ((r2 = dev_alloc(c, &tmp.d_words, words.size() + 4))) return r2;
-    if ((r2 = dev_alloc(c, &tmp.d_rec_off, rec_off.size()))) return r2;
-    if ((r2 = dev_alloc(c, &tmp.d_len, lens.size()))) return r2;
-    if ((r2 = dev_alloc(c, &tmp.d_saved, (size_t)n_pairs))) return r2;
-    if ((r2 = dev_alloc(c, &tmp.d_saved_aln, (size_t)n_pairs))) return r2;
-    if ((r2 = dev_alloc(c, &tmp.d_ctr, (size_t)C_TOTAL))) return r2;
-    if ((r2 = dev_alloc(c, &di.ref_seq, (size_t)ref_off[n_pairs] + 64))) return r2;
-    if ((r2 = dev_alloc(c, &di.ref_off, (size_t)n_pairs + 1))) return r2;
-    HIPCHK(c, hipMemcpyAsync(tmp.d_words, words.data(), words.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(tmp.d_rec_off, rec_off.data(), rec_off.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(tmp.d_len, lens.data(), lens.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(tmp.d_saved, st.data(), st.size() * sizeof(RState), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(tmp.d_saved_aln, al.data(), al.size() * sizeof(AlignRec), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(tmp.d_ctr, 0, C_TOTAL * 8, c->stream));
-    HIPCHK(c, hipMemcpyAsync(di.ref_seq, refs, (size_t)ref_off[n_pairs], hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(di.ref_off, ref_off, ((size_t)n_pairs + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    di.n_refs = n_pairs; di.lnwin = 18; di.used = true;
-    if ((r2 = check_params(c, &p, false))) return r2;
-    if ((r2 = traceback_core(c, di, &p))) return r2;
-    std::vector<unsigned long long> h;
-    if ((r2 = read_ctr(c, h))) return r2;
-    std::vector<uint32_t> pool((size_t)std::min<uint64_t>(h[C_CIGAR_CURSOR], tmp.cigar_words));
-    HIPCHK(c, hipMemcpyAsync(al.data(), tmp.d_saved_aln, al.size() * sizeof(AlignRec), hipMemcpyDeviceToHost, c->stream));
-    if (!pool.empty()) HIPCHK(c, hipMemcpyAsync(pool.data(), tmp.d_cigar, pool.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    uint64_t o = 0;
-    for (uint32_t i = 0; i < n_pairs; i++) {
-      if (!al[i].has_cigar) { set_err(c, "smr_cigar_batch: an alignment was left without a CIGAR"); return SMR_ERR_STATE; }
-      for (uint32_t q = 0; q < al[i].cigar_len; q++, o++) if (cigar_out && o < cigar_cap) cigar_out[o] = pool[(size_t)al[i].cigar_off + q];
-      cigar_off_out[i + 1] = o;
-    }
-    return SMR_OK;
-  };
-  rc = run();
-  (void)hipStreamSynchronize(c->stream);
-  c->b = keep;
-  dev_free(&tmp.d_words); dev_free(&tmp.d_rec_off); dev_free(&tmp.d_len); dev_free(&tmp.d_saved); dev_free(&tmp.d_saved_aln); dev_free(&tmp.d_ctr); dev_free(&tmp.d_cigar);
-  dev_free(&di.ref_seq); dev_free(&di.ref_off);
-  return rc;
+  int rc;
+  if ((rc = t.upload(refs, ref_off)) || (rc = check_params(c, &p, false)) || (rc = traceback_core(c, t.di, &p))) return rc;
+  std::vector<unsigned long long> h;
+  if ((rc = read_ctr(c, h))) return rc;
+  std::vector<uint32_t> pool((size_t)std::min<uint64_t>(h[C_CIGAR_CURSOR], t.b.cigar_words));
+  HIPCHK(c, hipMemcpyAsync(t.al.data(), t.b.d_saved_aln, t.al.size() * sizeof(AlignRec), hipMemcpyDeviceToHost, c->stream));
+  if (!pool.empty()) HIPCHK(c, hipMemcpyAsync(pool.data(), t.b.d_cigar, pool.size() * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  uint64_t o = 0;
+  for (uint32_t i = 0; i < n_pairs; i++) {
+    const AlignRec& a = t.al[i];
+    if (!a.has_cigar) { set_err(c, "smr_cigar_batch: an alignment was left without a CIGAR"); return SMR_ERR_STATE; }
+    for (uint32_t q = 0; q < a.cigar_len; q++, o++) if (cigar_out && o < cigar_cap) cigar_out[o] = pool[(size_t)a.cigar_off + q];
+    cigar_off_out[i + 1] = o;
+  }
+  return SMR_OK;
 }
 

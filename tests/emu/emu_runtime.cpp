@@ -321,6 +321,8 @@ hipError_t hipFree(void* p) {
   fprintf(stderr, "emu: hipFree of an unknown pointer %p\n", p);
   abort();
 }
+// device allocations that have not been freed (the guard table: 0 throughout with SMR_EMU_GUARD=0): what a test of the engine's ownership counts
+extern "C" size_t emu_live_allocations() { std::lock_guard<std::mutex> g(g_guard_mu); return g_guard.size(); }
 hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memmove(d, s, n); return hipSuccess; }
