@@ -5,6 +5,8 @@
 //   <out>/summary.txt   total reads, reads passing the E-value threshold, per-DB counts, too-short reads
 // and, on request, the reference's reports through smr_report_* (aligned/other FASTX, BLAST tabular, SAM):
 //   --fastx --other --blast "1 cigar qcov qstrand" --sam
+// --pack device: the reads files are parsed and 2-bit packed by kernels (smr_reads_upload_fastx_file) instead of by the host's cores; the
+// default, --pack host, is smr_reads_load_fastx_text + smr_reads_upload.  Everything after that is the same, and so is every output file.
 // Build:  g++ -std=c++17 -O2 examples/smr_align.cpp -Iinclude -Lsortmerna_amd/lib -lsmr_hip -Wl,-rpath,$PWD/sortmerna_amd/lib -o smr_align
 // There is no CPU fallback: without a HIP device smr_create fails and the program exits like the reference does (ERR + exit 1).
 #include <cstdint>
@@ -29,6 +31,7 @@ int main(int argc, char** argv) {
   smr_params base; smr_params_default(&base);
   double evalue = 1.0;
   int device = 0;
+  bool pack_device = false;
   smr_report_opts ro; memset(&ro, 0, sizeof ro);
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -52,6 +55,7 @@ int main(int argc, char** argv) {
     else if (a == "-gap_open") base.gap_open = atoi(val().c_str());
     else if (a == "-gap_ext") base.gap_ext = atoi(val().c_str());
     else if (a == "-device") device = atoi(val().c_str());
+    else if (a == "-pack" || a == "--pack") { const std::string v = val(); if (v != "host" && v != "device") die("--pack: host or device"); pack_device = v == "device"; }
     else if (a == "-fastx" || a == "--fastx") ro.fastx = 1;
     else if (a == "-other" || a == "--other") ro.other = 1;
     else if (a == "-sam" || a == "--sam") ro.sam = 1;
@@ -74,7 +78,7 @@ int main(int argc, char** argv) {
       printf("usage: smr_align --ref DB.fasta --gumbel LAMBDA K [--idx PREFIX] [--ref ...] --reads READS.fa|fq[.gz] [--reads MATES] [--out DIR]\n"
              "       [-e EVALUE] [-num_alignments N] [-no-best] [-min_lis N] [-num_seeds N] [-edges N] [-full_search] [-F|-R]\n"
              "       [-match N -mismatch N -gap_open N -gap_ext N] [-device K] [--fastx] [--other] [--blast '0' | '1 cigar qcov qstrand'] [--sam [-SQ]]\n"
-             "       [-zip-out 0|1] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
+             "       [-zip-out 0|1] [--pack host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
       return 0;
     } else die("unknown option " + a);
   }
@@ -89,10 +93,17 @@ int main(int argc, char** argv) {
   // reads (Readfeed::next -> Read::init, readfeed.hpp:124 / read.cpp:264-347)
   // (all cores parse and 2-bit pack the FASTA / FASTQ / .gz file; the text stays mapped for the report writers)
   // one batch per reads file (the second file holds the mates of the first: options.cpp:1591 is_paired)
+  // (--pack device: the kernels of the engine do that, straight into batch b; what comes back has the text, the record offsets and the lengths)
   std::vector<smr_reads*> rf(reads_paths.size(), nullptr);
   uint64_t n = 0, total_len = 0; uint32_t min_len = 0xFFFFFFFFu, max_len = 0;
+  smr_ctx* gpu = nullptr;
+  const uint32_t slots = base.num_alignments > 0 ? base.num_alignments : 256;
+  if (pack_device && smr_create(device, &gpu, err, sizeof err) != SMR_OK) die(err);
   for (size_t b = 0; b < rf.size(); b++) {
-    if (smr_reads_load_fastx_text(reads_paths[b].c_str(), 0, &rf[b], err, sizeof err) != SMR_OK) die(err);
+    if (pack_device) {
+      if (smr_batch_select(gpu, (int)b) != SMR_OK) die(smr_last_error(gpu));
+      if (smr_reads_upload_fastx_file(gpu, reads_paths[b].c_str(), slots, SMR_FASTX_VIEW, &rf[b], err, sizeof err) != SMR_OK) die(err);
+    } else if (smr_reads_load_fastx_text(reads_paths[b].c_str(), 0, &rf[b], err, sizeof err) != SMR_OK) die(err);
     n += smr_reads_count(rf[b]); total_len += smr_reads_total_len(rf[b]);
     if (smr_reads_count(rf[b])) { min_len = std::min(min_len, smr_reads_min_len(rf[b])); max_len = std::max(max_len, smr_reads_max_len(rf[b])); }
   }
@@ -127,11 +138,9 @@ int main(int argc, char** argv) {
     }
   }
 
-  smr_ctx* gpu = nullptr;
-  if (smr_create(device, &gpu, err, sizeof err) != SMR_OK) die(err);
+  if (!gpu && smr_create(device, &gpu, err, sizeof err) != SMR_OK) die(err);
   if (smr_sw_mode(gpu, -1) == 0) fprintf(stderr, "smr_align: the 32-bit Smith-Waterman kernel is in use (packed kernel off or failed its self-check): expect about half the alignment rate\n");
-  const uint32_t slots = base.num_alignments > 0 ? base.num_alignments : 256;
-  for (size_t b = 0; b < rf.size(); b++)
+  for (size_t b = 0; !pack_device && b < rf.size(); b++)
     if (smr_batch_select(gpu, (int)b) != SMR_OK || smr_reads_upload(gpu, rf[b], slots) != SMR_OK) die(smr_last_error(gpu));
 
   // the (index, part) loop of processor.cpp:219-277

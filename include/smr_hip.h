@@ -248,6 +248,32 @@ int smr_reads_upload(smr_ctx*, const smr_reads*, uint32_t max_alignments_per_rea
  * alignment of batch k (the reference's Readfeed/Processor overlap file reading with alignment the same way, readfeed.cpp, processor.cpp:248-256).
  * Fails with SMR_ERR_STATE when `batch` is the selected batch. */
 int smr_reads_upload_batch(smr_ctx*, int batch, const smr_reads*, uint32_t max_alignments_per_read);
+/* FASTA/FASTQ TEXT to a resident batch: records are found, measured, laid out and 2-bit packed by kernels (csrc/smr_fastx.hpp), straight into the
+ * batch's device arrays.  For any bytes the batch -- and *out -- are exactly what smr_reads_load_fastx_text + smr_reads_upload of a file holding
+ * those bytes give, including the error code and message of malformed text (smr_last_error; no file name in front for the two buffer calls).
+ * Regular text is handled on the device: any FASTA, and FASTQ in which, counting lines from the first byte that is not '\n' / '\r', every line 4k
+ * begins with '@' up to the last record, the record count is whole and only lines that are empty or one '\r' follow.  Anything else (blank lines
+ * between FASTQ records, a cut last record, stray bytes, empty text) is walked by the host parser inside the same call ("Parsing
+ * and packing on the device").  n_bytes >= 2^32 - 64 is SMR_ERR_CAPACITY, decided before the text is touched: hand the text over in pieces that
+ * end at record boundaries.  After a refusal the batch is as it was before the call.
+ *   smr_reads_upload_fastx        into the selected batch, on the engine's stream
+ *   smr_reads_upload_fastx_batch  into batch `batch` on the upload stream, like smr_reads_upload_batch (SMR_ERR_STATE for the selected batch)
+ *   smr_reads_upload_fastx_file   maps the file (inflates a gzip file) first; the message also goes to err
+ * out == NULL: only the totals come back from the device.  Otherwise *out is a complete smr_reads (smr_reads_free it): lengths, offsets and packed
+ * words are copied back from the device, so smr_reads_digest, _slice, _record_text, ... work on it unchanged.  With the two buffer calls its
+ * text borrows the caller's bytes, which must outlive it; the file call's object owns the text.
+ * flags & SMR_FASTX_VIEW: the packed words are not copied back.  The object has the text, the record offsets, lengths and statistics:
+ * smr_reads_record_text, _count, _total_len, _min_len, _max_len and _is_fastq work; smr_reads_slice and smr_reads_upload* answer SMR_ERR_STATE and
+ * smr_reads_digest answers 0. */
+#define SMR_FASTX_VIEW 1u
+int smr_reads_upload_fastx(smr_ctx*, const char* text, uint64_t n_bytes, uint32_t max_alignments_per_read, uint32_t flags, smr_reads** out);
+int smr_reads_upload_fastx_batch(smr_ctx*, int batch, const char* text, uint64_t n_bytes, uint32_t max_alignments_per_read, uint32_t flags, smr_reads** out);
+int smr_reads_upload_fastx_file(smr_ctx*, const char* path, uint32_t max_alignments_per_read, uint32_t flags, smr_reads** out, char* err, size_t errcap);
+/* Test seam (tests/test_gpu_fastx_device.py): of the last smr_reads_upload_fastx* call on the context {path taken: 0 the kernels, 1 the host parser;
+ * lines the kernels found; records; text bytes copied to the device}.  smr_fastx_times: HIP-event milliseconds of that call's stages on the
+ * device path {text H2D, lines, records, pack, results D2H} (0 for the host parser's path). */
+int smr_fastx_info(const smr_ctx*, uint64_t info[4]);
+int smr_fastx_times(const smr_ctx*, double ms[5]);
 /* Forget all per-read results/counters of the resident batch (reads stay resident). */
 int smr_state_reset(smr_ctx*);
 

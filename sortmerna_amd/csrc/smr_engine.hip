@@ -15,6 +15,7 @@
 #include "smr_idcov.hpp"
 #include "smr_import.hpp"
 #include "smr_export.hpp"
+#include "smr_fastx.hpp"
 #include "smr_ibuild.hpp"
 #include "smr_pgbuild.hpp"
 #include "smr_hostmem.hpp"
@@ -92,6 +93,18 @@ struct SharedSort {
 struct SeedScratch {
   DevBuf<uint32_t> chist, cbase, rows, bcnt, wseg[2], fbits[2], zbits, gflag, emap, sn, redo, hpre, hlist, hh;
   DevBuf<SeedTup> tmp, mid, srt; DevBuf<uint16_t> wbin; DevBuf<uint2> pieces;
+};
+
+// scratch of smr_reads_upload_fastx* (smr_fastx.hpp), grow-only; one set per stream the call can run on
+struct FxScratch {
+  DevBuf<uint8_t> text;
+  DevBuf<uint32_t> tot, part_t, part_l, line_start, lrec, lcum, hdr_line, rcum, rlen, rwi;      // part_l: three arrays of one entry per block of lines
+  DevBuf<unsigned long long> hoff, soff;
+  hipEvent_t ev[6] = {};
+  FxScratch() = default;
+  FxScratch(const FxScratch&) = delete;
+  FxScratch& operator=(const FxScratch&) = delete;
+  ~FxScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 struct smr_ctx {
@@ -172,6 +185,9 @@ struct smr_ctx {
   // read that says which way it went through the candidate stage in the launches of the final attempt (k_cand_route; no other kernel knows of it)
   bool cinfo_on = false; DevBuf<uint8_t> d_croute; uint32_t croute_n = 0;
   uint32_t cinfo_attempts = 0, cinfo_retry[5] = {0, 0, 0, 0, 0};       // attempts; redone because of HITCAP, POOL, PAIRS, REDO, SCAP
+  // smr_reads_upload_fastx*: [0] on `stream`, [1] on `upload_stream`; smr_fastx_info / smr_fastx_times of the last call (written under err_m)
+  FxScratch fx[2];
+  uint64_t fx_info[4] = {0, 0, 0, 0}; double fx_ms[5] = {0, 0, 0, 0, 0};
 };
 struct KpSave { double ms[KP_COUNT]; uint64_t l[KP_COUNT]; };
 
@@ -199,6 +215,10 @@ void set_err(smr_ctx* c, const std::string& msg) { std::lock_guard<std::mutex> l
 template <class T> struct arg_of { typedef T type; };
 template <class... P> void launch(smr_ctx* c, void (*k)(P...), dim3 grid, dim3 block, size_t lds, typename arg_of<P>::type... a) {
   hipLaunchKernelGGL(k, grid, block, lds, c->stream, a...);
+}
+// the same on a stream of the caller's choice (smr_reads_upload_fastx_batch works on the upload stream)
+template <class... P> void launch_on(hipStream_t st, void (*k)(P...), dim3 grid, dim3 block, size_t lds, typename arg_of<P>::type... a) {
+  hipLaunchKernelGGL(k, grid, block, lds, st, a...);
 }
 // "the dynamic-LDS limit of these kernels is at least `bytes`": set once per high-water mark, and only above what every kernel may use anyway
 template <class... F> int raise_lds_limit(smr_ctx* c, size_t& high_water, size_t bytes, size_t free_bytes, F... kernels) {
@@ -556,29 +576,40 @@ int reset_batch(smr_ctx* c, Batch& B, hipStream_t st) {
   B.fetched = false;
   return SMR_OK;
 }
-// the packed reads of r into batch B (+ its per-read state, reset), all work on stream st; touches nothing but B
-int upload_into(smr_ctx* c, Batch& B, const smr_reads* r, uint32_t max_aln, hipStream_t st) {
-  if (max_aln == 0) max_aln = 1;
+// room in batch B for n reads of `words` packed words and max_aln alignments each, and the batch's fields; the arrays' contents are the caller's
+int batch_reserve(smr_ctx* c, Batch& B, size_t words, uint32_t n, uint32_t min_len, uint32_t max_len, uint32_t max_aln, hipStream_t st) {
   int rc;
   if (!B.d_ctr) { if ((rc = B.d_ctr.alloc(c, C_TOTAL))) return rc; HIPCHK(c, hipMemsetAsync(B.d_ctr, 0, C_TOTAL * 8, st)); }
-  const size_t nw = r->words.size() + 4, nr = (size_t)r->n + 1, na = std::max<size_t>((size_t)r->n * max_aln, 1);     // + slack: window extraction reads 2 words ahead
+  const size_t nw = words + 4, nr = (size_t)n + 1, na = std::max<size_t>((size_t)n * max_aln, 1);     // + slack: window extraction reads 2 words ahead
   if ((rc = B.d_words.reserve(c, nw))) return rc;
   // (the six per-read arrays are reserved for the same number in the same calls: they grow together)
   if ((rc = B.d_rec_off.reserve(c, nr)) || (rc = B.d_len.reserve(c, nr)) || (rc = B.d_saved.reserve(c, nr)) || (rc = B.d_work.reserve(c, nr)) || (rc = B.d_rw.reserve(c, nr)) ||
       (rc = B.d_marks.reserve(c, nr))) return rc;
   if ((rc = B.d_saved_aln.reserve(c, na)) || (rc = B.d_work_aln.reserve(c, na))) return rc;
-  B.n = r->n; B.max_len = r->max_len; B.slots = max_aln; B.used = true;
+  B.n = n; B.max_len = max_len; B.slots = max_aln; B.used = true;
   for (int k = 0; k < 7; k++) B.min_ge[k] = ~0u;
   B.min_ge_known = false;
-  if (r->n && r->min_len >= 100) { for (int k = 0; k < 7; k++) B.min_ge[k] = r->min_len; B.min_ge_known = true; }      // (1 % of 100 letters is a margin already: nothing to look for)
-  HIPCHK(c, hipMemcpyAsync(B.d_words, r->words.data(), r->words.size() * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(B.d_rec_off, r->rec_off.data(), r->rec_off.size() * 8, hipMemcpyHostToDevice, st));
-  if (r->n) HIPCHK(c, hipMemcpyAsync(B.d_len, r->len.data(), r->len.size() * 4, hipMemcpyHostToDevice, st));
+  if (n && min_len >= 100) { for (int k = 0; k < 7; k++) B.min_ge[k] = min_len; B.min_ge_known = true; }      // (1 % of 100 letters is a margin already: nothing to look for)
+  return SMR_OK;
+}
+// the per-read state of a batch whose reads have just been put in place
+int batch_fresh_state(smr_ctx* c, Batch& B, hipStream_t st) {
   HIPCHK(c, hipMemsetAsync(B.d_rw, 0, (size_t)B.n * sizeof(RWork), st));
   HIPCHK(c, hipMemsetAsync(B.d_work, 0, (size_t)B.n * sizeof(RState), st));
   B.cigar_words = 0; B.d_cigar.release();
   if (B.d_idcov.cap() < (size_t)B.n * 4) B.d_idcov.release();                     // (the next smr_idcov_part allocates it for this batch size)
   return reset_batch(c, B, st);
+}
+// the packed reads of r into batch B (+ its per-read state, reset), all work on stream st; touches nothing but B
+int upload_into(smr_ctx* c, Batch& B, const smr_reads* r, uint32_t max_aln, hipStream_t st) {
+  if (r->view) { set_err(c, "the batch was made with SMR_FASTX_VIEW: its packed words are on the device only"); return SMR_ERR_STATE; }
+  if (max_aln == 0) max_aln = 1;
+  int rc;
+  if ((rc = batch_reserve(c, B, r->words.size(), r->n, r->min_len, r->max_len, max_aln, st))) return rc;
+  HIPCHK(c, hipMemcpyAsync(B.d_words, r->words.data(), r->words.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(B.d_rec_off, r->rec_off.data(), r->rec_off.size() * 8, hipMemcpyHostToDevice, st));
+  if (r->n) HIPCHK(c, hipMemcpyAsync(B.d_len, r->len.data(), r->len.size() * 4, hipMemcpyHostToDevice, st));
+  return batch_fresh_state(c, B, st);
 }
 }  // namespace
 
@@ -786,6 +817,7 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
 #include "smr_engine_idcov.hpp"
 #include "smr_engine_import.hpp"
 #include "smr_engine_export.hpp"
+#include "smr_engine_fastx.hpp"
 extern "C" int smr_counters(smr_ctx* c, uint64_t* out, uint32_t n_db) {
   if (!c || !out) return SMR_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));

@@ -139,4 +139,12 @@ struct smr_reads {
   std::shared_ptr<void> text_owner;
   const char* text = nullptr; size_t text_n = 0; bool fastq = false;
   std::vector<uint64_t> hdr_off, seq_off;      // offset of the header line / of the first sequence line
+  bool view = false;                           // smr_reads_upload_fastx* with SMR_FASTX_VIEW: words and rec_off stayed on the device
 };
+
+namespace smr {
+// smr_reads.cpp, for smr_reads_upload_fastx* of smr_engine.hip: the file as bytes (mapped, or inflated when it is gzip; owner keeps them alive),
+// and the host parser on bytes -- what smr_reads_load_fastx_mt / _text run after mapping the file
+bool fastx_slurp(const char* path, std::shared_ptr<void>& owner, const char*& p, size_t& n, std::string& why);
+int load_fastx_bytes(const char* name, const char* p, size_t n, std::shared_ptr<void> owner, uint32_t threads, bool keep_text, smr_reads** out, std::string& why);
+}

@@ -210,19 +210,16 @@ inline void pack_piece(uint32_t* cp, uint32_t* mp, size_t k0, const char* s, siz
 }
 }  // namespace
 
-namespace {
-int load_fastx_impl(const char* path, uint32_t threads, bool keep_text, smr_reads** out, char* err, size_t errcap) {
-  if (!path || !out) return SMR_ERR_ARG;
-  auto fail = [&](const std::string& w) { if (err && errcap) snprintf(err, errcap, "%s", w.c_str()); return SMR_ERR_IO; };
-  auto bp = std::make_shared<Bytes>();
-  Bytes& b = *bp; std::string w0;
-  if (!slurp(path, b, w0)) return fail(w0);
-  const char* p = b.p; const size_t n = b.n;
+// The parser proper, on bytes that are in memory already (load_fastx_impl below maps a file first; smr_reads_upload_fastx* of smr_engine.hip
+// hands irregular text here).  name: what a message calls the text ("<name>: ..."; empty: no prefix); owner: what keeps p alive, may be empty.
+int smr::load_fastx_bytes(const char* name, const char* p, size_t n, std::shared_ptr<void> owner, uint32_t threads, bool keep_text, smr_reads** out, std::string& why) {
+  const std::string pre = name && *name ? std::string(name) + ": " : std::string();
+  auto fail = [&](const std::string& w) { why = w; return SMR_ERR_IO; };
   if (threads == 0) threads = smr::host_threads();
   size_t first = 0;
   while (first < n && (p[first] == '\n' || p[first] == '\r')) first++;
   const bool fastq = first < n && p[first] == '@';
-  if (first < n && p[first] != '@' && p[first] != '>') return fail(std::string(path) + ": neither FASTA nor FASTQ");
+  if (first < n && p[first] != '@' && p[first] != '>') return fail(pre + "neither FASTA nor FASTQ");
   threads = (uint32_t)std::min<size_t>(threads, std::max<size_t>(1, n / (1u << 16)));
   std::vector<size_t> cut(threads + 1, n);
   cut[0] = first;
@@ -234,26 +231,26 @@ int load_fastx_impl(const char* path, uint32_t threads, bool keep_text, smr_read
   }
   auto run = [&](auto&& fn) { std::vector<std::thread> th; for (uint32_t t = 1; t < threads; t++) th.emplace_back(fn, t); fn(0u); for (auto& x : th) x.join(); };
   std::vector<std::vector<Rec>> recs(threads);
-  std::vector<std::string> why(threads);
+  std::vector<std::string> why_t(threads);
   std::vector<uint64_t> nrec(threads + 1, 0), nword(threads + 1, 0);
   std::vector<uint64_t> tlen(threads, 0);
   std::vector<uint32_t> tmin(threads, 0xffffffffu), tmax(threads, 0);
   run([&](uint32_t t) {
     if (cut[t] >= cut[t + 1]) return;
     recs[t].reserve((cut[t + 1] - cut[t]) / (fastq ? 256 : 128) + 16);
-    list_range(p, n, cut[t], cut[t + 1], recs[t], why[t]);
+    list_range(p, n, cut[t], cut[t + 1], recs[t], why_t[t]);
     uint64_t wsum = 0;
     for (const Rec& r : recs[t]) { wsum += (r.len + 15) / 16 + (r.len + 31) / 32; tlen[t] += r.len; tmin[t] = std::min(tmin[t], r.len); tmax[t] = std::max(tmax[t], r.len); }
     nrec[t + 1] = recs[t].size(); nword[t + 1] = wsum;
   });
-  for (uint32_t t = 0; t < threads; t++) if (!why[t].empty()) return fail(std::string(path) + ": " + why[t]);
+  for (uint32_t t = 0; t < threads; t++) if (!why_t[t].empty()) return fail(pre + why_t[t]);
   for (uint32_t t = 0; t < threads; t++) { nrec[t + 1] += nrec[t]; nword[t + 1] += nword[t]; }
-  if (nrec[threads] > 0xfffffff0ull) return fail(std::string(path) + ": more than 2^32 records in one batch");
+  if (nrec[threads] > 0xfffffff0ull) return fail(pre + "more than 2^32 records in one batch");
   auto r = new smr_reads();
   r->n = (uint32_t)nrec[threads];
   r->fastq = fastq;
   // (the arrays are value-initialised by the one thread that sizes them: 2 MB pages make that first touch cheap -- smr_hostmem.hpp)
-  if (keep_text) { r->text_owner = bp; r->text = p; r->text_n = n; smr::reserve_huge(r->hdr_off, r->n); smr::reserve_huge(r->seq_off, r->n); r->hdr_off.resize(r->n); r->seq_off.resize(r->n); }
+  if (keep_text) { r->text_owner = owner; r->text = p; r->text_n = n; smr::reserve_huge(r->hdr_off, r->n); smr::reserve_huge(r->seq_off, r->n); r->hdr_off.resize(r->n); r->seq_off.resize(r->n); }
   smr::reserve_huge(r->len, r->n); smr::reserve_huge(r->rec_off, (size_t)r->n + 1); smr::reserve_huge(r->words, nword[threads]);
   r->len.resize(r->n); r->rec_off.resize((size_t)r->n + 1); r->words.resize(nword[threads]);
   r->rec_off[0] = 0;
@@ -273,6 +270,22 @@ int load_fastx_impl(const char* path, uint32_t threads, bool keep_text, smr_read
   });
   *out = r;
   return SMR_OK;
+}
+
+bool smr::fastx_slurp(const char* path, std::shared_ptr<void>& owner, const char*& p, size_t& n, std::string& why) {
+  auto bp = std::make_shared<Bytes>();
+  if (!slurp(path, *bp, why)) return false;
+  p = bp->p; n = bp->n; owner = bp;
+  return true;
+}
+
+namespace {
+int load_fastx_impl(const char* path, uint32_t threads, bool keep_text, smr_reads** out, char* err, size_t errcap) {
+  if (!path || !out) return SMR_ERR_ARG;
+  std::shared_ptr<void> owner; const char* p = nullptr; size_t n = 0; std::string why;
+  int rc = smr::fastx_slurp(path, owner, p, n, why) ? smr::load_fastx_bytes(path, p, n, owner, threads, keep_text, out, why) : SMR_ERR_IO;
+  if (rc != SMR_OK && err && errcap) snprintf(err, errcap, "%s", why.c_str());
+  return rc;
 }
 }  // namespace
 
@@ -323,6 +336,7 @@ extern "C" void smr_reads_free(smr_reads* r) { delete r; }
 // records [first, first + count) of a packed batch as a batch of their own: the host-side read shard of one rank / one pipeline chunk
 extern "C" int smr_reads_slice(const smr_reads* r, uint64_t first, uint64_t count, smr_reads** out) {
   if (!r || !out || first > r->n || count > r->n - first) return SMR_ERR_ARG;
+  if (r->view) return SMR_ERR_STATE;                              // (SMR_FASTX_VIEW: the packed words stayed on the device)
   auto s = new smr_reads();
   s->n = (uint32_t)count;
   s->len.assign(r->len.begin() + (size_t)first, r->len.begin() + (size_t)(first + count));
@@ -338,7 +352,7 @@ extern "C" int smr_reads_slice(const smr_reads* r, uint64_t first, uint64_t coun
 }
 // FNV-1a over lengths, record offsets and packed words: two batches with the same digest hold the same reads in the same order
 extern "C" uint64_t smr_reads_digest(const smr_reads* r) {
-  if (!r) return 0;
+  if (!r || r->view) return 0;
   uint64_t h = 1469598103934665603ull;
   auto mix = [&](const void* p, size_t n) { const uint8_t* b = (const uint8_t*)p; for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; } };
   mix(&r->n, 4);

@@ -117,8 +117,9 @@ class Index:
 
 
 class Reads:
-    def __init__(self, handle):
+    def __init__(self, handle, keep=None):
         self.h = handle
+        self._keep = keep          # the bytes a batch of Engine.upload_fastx(bytes) borrows its text from
 
     @staticmethod
     def from_seqs(seqs):
@@ -232,6 +233,7 @@ def pigeonhole_layout(index):
 
 
 ROUTE_RECORD, ROUTE_GATHER, ROUTE_CHAIN, ROUTE_EXT = 1, 2, 4, 8      # SMR_ROUTE_* of smr_hip.h (Engine.cand_routes)
+FASTX_VIEW = 1                                                       # SMR_FASTX_VIEW (Engine.upload_fastx)
 
 
 class Engine:
@@ -353,6 +355,44 @@ class Engine:
         while the selected batch is being aligned)"""
         self._chk(self.L.smr_reads_upload_batch(self.h, batch, reads.h, max_alignments_per_read), "smr_reads_upload_batch")
         self._batch_n[batch] = reads.count
+
+    def upload_fastx(self, data_or_path, max_alignments_per_read=1, batch=None, view=False):
+        """smr_reads_upload_fastx*: FASTA/FASTQ text (bytes), or the file at a path (str; gzip is inflated), parsed and 2-bit packed on the device
+        into the selected batch -- or, with batch=k, into batch k on the upload stream.  Returns the Reads the host parser would have made of
+        the same bytes, copied back from the device; view=True leaves the packed words there (SMR_FASTX_VIEW: record_text and the statistics
+        work, digest is 0, slice and upload raise)."""
+        h = C.c_void_p()
+        flags = FASTX_VIEW if view else 0
+        keep = None
+        if isinstance(data_or_path, str):
+            if batch is not None:
+                raise SmrError("upload_fastx: batch= takes bytes (read the file first)")
+            err = C.create_string_buffer(512)
+            rc, what = self.L.smr_reads_upload_fastx_file(self.h, data_or_path.encode(), max_alignments_per_read, flags, C.byref(h), err, 512), "smr_reads_upload_fastx_file"
+        else:
+            keep = C.create_string_buffer(bytes(data_or_path), len(data_or_path) + 1)          # (the Reads borrows these bytes)
+            if batch is None:
+                rc, what = self.L.smr_reads_upload_fastx(self.h, keep, len(data_or_path), max_alignments_per_read, flags, C.byref(h)), "smr_reads_upload_fastx"
+            else:
+                rc, what = self.L.smr_reads_upload_fastx_batch(self.h, batch, keep, len(data_or_path), max_alignments_per_read, flags, C.byref(h)), "smr_reads_upload_fastx_batch"
+        self._chk(rc, what)
+        reads = Reads(h, keep)
+        if batch is None:
+            self.n_reads = reads.count
+        self._batch_n[self._cur if batch is None else batch] = reads.count
+        return reads
+
+    def fastx_info(self):
+        """(path taken: 0 the kernels, 1 the host parser; lines found; records; text bytes uploaded) of the last upload_fastx (smr_fastx_info: a test seam)"""
+        info = (C.c_uint64 * 4)()
+        self._chk(self.L.smr_fastx_info(self.h, info), "smr_fastx_info")
+        return tuple(int(x) for x in info)
+
+    def fastx_times(self):
+        """HIP-event ms of the last upload_fastx on the device path: dict(h2d, lines, records, pack, d2h)"""
+        ms = (C.c_double * 5)()
+        self._chk(self.L.smr_fastx_times(self.h, ms), "smr_fastx_times")
+        return dict(zip(("h2d", "lines", "records", "pack", "d2h"), (float(x) for x in ms)))
 
     def reset_state(self):
         self._chk(self.L.smr_state_reset(self.h), "smr_state_reset")
@@ -560,7 +600,8 @@ def align(engine, reads, index_parts, params_per_index, with_cigar=True, max_ali
         raise SmrError("align: id_cov with resume is not supported here (the pass needs the references of the earlier --ref as well)")
     p0 = params_per_index[0]
     slots = max_alignments_per_read or (p0.num_alignments if p0.num_alignments > 0 else 32)
-    engine.upload_reads(reads, slots)
+    if reads is not None:                       # (None: the selected batch is in place already, e.g. by engine.upload_fastx with as many slots)
+        engine.upload_reads(reads, slots)
     if resume is not None:
         records, counters = resume
         engine.import_state(records)
