@@ -7,6 +7,9 @@
 //   --fastx --other --blast "1 cigar qcov qstrand" --sam
 // --pack device: the reads files are parsed and 2-bit packed by kernels (smr_reads_upload_fastx_file) instead of by the host's cores; the
 // default, --pack host, is smr_reads_load_fastx_text + smr_reads_upload.  Everything after that is the same, and so is every output file.
+// --split device (needs --pack device): the text stays with the batches (SMR_FASTX_KEEP) and aligned.* / other.* are written from the streams
+// of one smr_fastx_split call (smr_report_add_fastx) instead of read by read; the default, --split host, is smr_reads_record_text +
+// smr_report_add / smr_report_add_pair.  Every output file is the same.
 // Build:  g++ -std=c++17 -O2 examples/smr_align.cpp -Iinclude -Lsortmerna_amd/lib -lsmr_hip -Wl,-rpath,$PWD/sortmerna_amd/lib -o smr_align
 // There is no CPU fallback: without a HIP device smr_create fails and the program exits like the reference does (ERR + exit 1).
 #include <cstdint>
@@ -31,7 +34,7 @@ int main(int argc, char** argv) {
   smr_params base; smr_params_default(&base);
   double evalue = 1.0;
   int device = 0;
-  bool pack_device = false;
+  bool pack_device = false, split_device = false;
   smr_report_opts ro; memset(&ro, 0, sizeof ro);
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -56,6 +59,7 @@ int main(int argc, char** argv) {
     else if (a == "-gap_ext") base.gap_ext = atoi(val().c_str());
     else if (a == "-device") device = atoi(val().c_str());
     else if (a == "-pack" || a == "--pack") { const std::string v = val(); if (v != "host" && v != "device") die("--pack: host or device"); pack_device = v == "device"; }
+    else if (a == "-split" || a == "--split") { const std::string v = val(); if (v != "host" && v != "device") die("--split: host or device"); split_device = v == "device"; }
     else if (a == "-fastx" || a == "--fastx") ro.fastx = 1;
     else if (a == "-other" || a == "--other") ro.other = 1;
     else if (a == "-sam" || a == "--sam") ro.sam = 1;
@@ -78,10 +82,11 @@ int main(int argc, char** argv) {
       printf("usage: smr_align --ref DB.fasta --gumbel LAMBDA K [--idx PREFIX] [--ref ...] --reads READS.fa|fq[.gz] [--reads MATES] [--out DIR]\n"
              "       [-e EVALUE] [-num_alignments N] [-no-best] [-min_lis N] [-num_seeds N] [-edges N] [-full_search] [-F|-R]\n"
              "       [-match N -mismatch N -gap_open N -gap_ext N] [-device K] [--fastx] [--other] [--blast '0' | '1 cigar qcov qstrand'] [--sam [-SQ]]\n"
-             "       [-zip-out 0|1] [--pack host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
+             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
       return 0;
     } else die("unknown option " + a);
   }
+  if (split_device && !pack_device) die("--split device writes aligned.* / other.* from the text the device parsed: it needs --pack device");
   if (dbs.empty() || reads_paths.empty()) die("--ref and --reads are required (see --help)");
   if (const char* why = smr_params_refused(&base)) die(std::string("these options are outside what libsmr_hip aligns (the reference accepts them): ") + why);
   // minimal_score (which reads count as aligned) and the e-values / bit scores of the BLAST report depend on the Gumbel parameters of the
@@ -102,7 +107,7 @@ int main(int argc, char** argv) {
   for (size_t b = 0; b < rf.size(); b++) {
     if (pack_device) {
       if (smr_batch_select(gpu, (int)b) != SMR_OK) die(smr_last_error(gpu));
-      if (smr_reads_upload_fastx_file(gpu, reads_paths[b].c_str(), slots, SMR_FASTX_VIEW, &rf[b], err, sizeof err) != SMR_OK) die(err);
+      if (smr_reads_upload_fastx_file(gpu, reads_paths[b].c_str(), slots, SMR_FASTX_VIEW | (split_device ? SMR_FASTX_KEEP : 0u), &rf[b], err, sizeof err) != SMR_OK) die(err);
     } else if (smr_reads_load_fastx_text(reads_paths[b].c_str(), 0, &rf[b], err, sizeof err) != SMR_OK) die(err);
     n += smr_reads_count(rf[b]); total_len += smr_reads_total_len(rf[b]);
     if (smr_reads_count(rf[b])) { min_len = std::min(min_len, smr_reads_min_len(rf[b])); max_len = std::max(max_len, smr_reads_max_len(rf[b])); }
@@ -176,6 +181,22 @@ int main(int argc, char** argv) {
       for (size_t part = 0; part < dbs[k].parts.size(); part++) smr_report_set_part(rep, (uint32_t)k, (uint32_t)part, dbs[k].parts[part]);
     }
   }
+  // --split device: aligned.* / other.* of the whole input in one call (layout 0: single reads, 1: mates interleaved, 2: mates in batch 1); the
+  // loop below then leaves those files alone, and needs the text of a read only for the BLAST and SAM rows
+  const bool split_fx = split_device && rep && (ro.fastx || ro.other);
+  const bool rows = ro.blast_tabular || ro.blast_pairwise || ro.sam;
+  if (split_fx) {
+    smr_fxsplit_opts so; memset(&so, 0, sizeof so);
+    so.layout = rf.size() == 2 ? 2 : paired ? 1 : 0;
+    so.paired_in = ro.paired_in; so.paired_out = ro.paired_out; so.out2 = ro.out2; so.sout = ro.sout; so.want_aligned = ro.fastx; so.want_other = ro.other;
+    uint64_t off[9], need = 0;
+    if (smr_batch_select(gpu, 0) != SMR_OK || smr_fastx_split(gpu, so.layout == 2 ? 1 : -1, &so, nullptr, nullptr, 0, off, &need) != SMR_OK) die(smr_last_error(gpu));
+    std::vector<uint8_t> fx((size_t)need + 1);
+    if (smr_fastx_split(gpu, so.layout == 2 ? 1 : -1, &so, nullptr, fx.data(), need, off, &need) != SMR_OK) die(smr_last_error(gpu));
+    if (smr_report_add_fastx(rep, fx.data(), off) != SMR_OK) die(smr_report_last_error(rep));
+    smr_report_skip_fastx(rep, 1);
+  }
+  const bool feed = rep && (!split_fx || rows);                     // does the report take the reads one by one at all
   // kvdb.put(read.id, read.toBinString()) (processor.cpp:150-155) -> records.bin ; Readstats -> summary.txt
   const std::string rp = out_dir + "/records.bin", sp = out_dir + "/summary.txt";
   FILE* f = fopen(rp.c_str(), "wb");
@@ -188,7 +209,7 @@ int main(int argc, char** argv) {
     const size_t len = smr_result_record(gpu, i, nullptr, 0);
     m.rec.resize(len);
     if (len) smr_result_record(gpu, i, m.rec.data(), len);
-    if (rep) {
+    if (feed) {
       size_t tl[3];
       smr_reads_record_text(rf[b], i, nullptr, 0, nullptr, 0, nullptr, 0, tl);
       m.h.resize(tl[0] + 1); m.s.resize(tl[1] + 1); m.q.resize(tl[2] + 1);
@@ -206,13 +227,13 @@ int main(int argc, char** argv) {
     const uint32_t np = rf.size() == 2 ? smr_reads_count(rf[0]) : smr_reads_count(rf[0]) / 2;
     for (uint32_t i = 0; i < np; i++) {
       if (rf.size() == 2) { load(0, i, m1); load(1, i, m2); } else { load(0, 2 * i, m1); load(0, 2 * i + 1, m2); }
-      if (rep && smr_report_add_pair(rep, m1.h.data(), m1.s.data(), is_fastq ? m1.q.data() : nullptr, m1.rec.data(), m1.rec.size(),
-                                     m2.h.data(), m2.s.data(), is_fastq ? m2.q.data() : nullptr, m2.rec.data(), m2.rec.size()) != SMR_OK) die(smr_report_last_error(rep));
+      if (feed && smr_report_add_pair(rep, m1.h.data(), m1.s.data(), is_fastq ? m1.q.data() : nullptr, m1.rec.data(), m1.rec.size(),
+                                      m2.h.data(), m2.s.data(), is_fastq ? m2.q.data() : nullptr, m2.rec.data(), m2.rec.size()) != SMR_OK) die(smr_report_last_error(rep));
     }
   } else {
     for (uint32_t i = 0; i < smr_reads_count(rf[0]); i++) {
       load(0, i, m1);
-      if (rep && smr_report_add(rep, m1.h.data(), m1.s.data(), is_fastq ? m1.q.data() : nullptr, m1.rec.data(), m1.rec.size()) != SMR_OK) die(smr_report_last_error(rep));
+      if (feed && smr_report_add(rep, m1.h.data(), m1.s.data(), is_fastq ? m1.q.data() : nullptr, m1.rec.data(), m1.rec.size()) != SMR_OK) die(smr_report_last_error(rep));
     }
   }
   std::vector<uint64_t> ctr(2 + dbs.size(), 0), cb(2 + dbs.size());

@@ -264,8 +264,14 @@ int smr_reads_upload_batch(smr_ctx*, int batch, const smr_reads*, uint32_t max_a
  * text borrows the caller's bytes, which must outlive it; the file call's object owns the text.
  * flags & SMR_FASTX_VIEW: the packed words are not copied back.  The object has the text, the record offsets, lengths and statistics:
  * smr_reads_record_text, _count, _total_len, _min_len, _max_len and _is_fastq work; smr_reads_slice and smr_reads_upload* answer SMR_ERR_STATE and
- * smr_reads_digest answers 0. */
+ * smr_reads_digest answers 0.
+ * flags & SMR_FASTX_KEEP (combines with SMR_FASTX_VIEW): the text stays with the batch on the device -- the padded text, the offsets of every
+ * record's header line and first sequence line, the format: what smr_reads_record_text reads -- for smr_fastx_split.  The buffers the parser
+ * kernels worked on are handed over, not copied (the upload's scratch allocates again on its next use); text the host parser walked is
+ * uploaded with the parser's offsets.  Cost: the text plus 16 bytes per record of device memory until the batch is uploaded into again by any
+ * upload call (which drops it) or the context is destroyed; smr_state_reset keeps it.  Without the flag nothing is kept and nothing changes. */
 #define SMR_FASTX_VIEW 1u
+#define SMR_FASTX_KEEP 2u
 int smr_reads_upload_fastx(smr_ctx*, const char* text, uint64_t n_bytes, uint32_t max_alignments_per_read, uint32_t flags, smr_reads** out);
 int smr_reads_upload_fastx_batch(smr_ctx*, int batch, const char* text, uint64_t n_bytes, uint32_t max_alignments_per_read, uint32_t flags, smr_reads** out);
 int smr_reads_upload_fastx_file(smr_ctx*, const char* path, uint32_t max_alignments_per_read, uint32_t flags, smr_reads** out, char* err, size_t errcap);
@@ -274,6 +280,31 @@ int smr_reads_upload_fastx_file(smr_ctx*, const char* path, uint32_t max_alignme
  * device path {text H2D, lines, records, pack, results D2H} (0 for the host parser's path). */
 int smr_fastx_info(const smr_ctx*, uint64_t info[4]);
 int smr_fastx_times(const smr_ctx*, double ms[5]);
+/* The aligned.* / other.* FASTX outputs of the selected batch, written on the device (csrc/smr_fxsplit.hpp) from the text that SMR_FASTX_KEEP
+ * left there and the batch's per-read is_hit: what smr_results_fetch + smr_reads_record_text + smr_report_add / smr_report_add_pair write one
+ * read at a time ("Writing aligned.* / other.* from the device").  Eight streams, aligned[0..3] then other[0..3]; index j is the
+ * file smr_report_open gives that index (the only file; _fwd / _rev; _paired / _singleton; _paired_fwd, _paired_rev, _singleton_fwd,
+ * _singleton_rev).  Stream k is bytes[off[k], off[k + 1]), off[0] = 0, off[8] = *need; a stream that does not exist under the options, or is
+ * not wanted, is empty.  Each stream holds exactly the bytes the host writer puts into that file when it is given the reads in order: per record
+ * the header line, the letters of all sequence lines joined, and for FASTQ "+" and the quality line, each trimmed of trailing '\r', blank and tab
+ * and ended by '\n'.  Routing: layout 0 smr_report_add, layouts 1 and 2 the table of smr_report_add_pair.
+ *   hit    NULL: the batches' own is_hit (before any alignment every read is `other`).  Else one byte per read, non-zero = aligned: the reads of
+ *          the selected batch, then -- layout 2 -- those of batch `mates`; used instead of the device's.
+ *   bytes  NULL: sizes only.  cap < *need: SMR_ERR_CAPACITY, off and *need valid, bytes untouched.  Otherwise exactly *need bytes are written.
+ *          May be pinned memory.
+ * SMR_ERR_STATE (the message names SMR_FASTX_KEEP) for a batch without kept text.  SMR_ERR_ARG under layouts 1 and 2 for an odd read count
+ * (layout 1), `mates` equal to the selected batch, unequal read counts or FASTA against FASTQ (layout 2), and the option combinations
+ * smr_report_open refuses.  Runs on the engine's stream; needs no smr_results_fetch and leaves the host copy of the results alone; may be
+ * repeated.  Device memory: 24 bytes per record of scratch and the output, both kept for the next call. */
+typedef struct {
+  int32_t layout;      /* 0: single reads; 1: mates interleaved in the selected batch (2i, 2i+1); 2: mates of read i of the selected batch are read i of batch `mates` */
+  int32_t paired_in, paired_out, out2, sout;   /* as in smr_report_opts */
+  int32_t want_aligned, want_other;            /* -fastx / -other: a stream that is not wanted has length 0 */
+} smr_fxsplit_opts;
+int smr_fastx_split(smr_ctx*, int mates /* batch number, layout 2 only; else -1 */, const smr_fxsplit_opts*,
+                    const uint8_t* hit /* NULL: the batches' own is_hit */, uint8_t* bytes, uint64_t cap, uint64_t off[9], uint64_t* need);
+/* HIP-event milliseconds of the last smr_fastx_split: {measure and route, scans, copy, bytes D2H} (the last two 0 for a sizes-only call) */
+int smr_fastx_split_times(const smr_ctx*, double ms[4]);
 /* Forget all per-read results/counters of the resident batch (reads stay resident). */
 int smr_state_reset(smr_ctx*);
 
@@ -496,6 +527,12 @@ int smr_report_add(smr_report*, const char* header, const char* seq, const char*
 /* a pair of mates (read i of the first and of the second file / two consecutive records of an interleaved file) */
 int smr_report_add_pair(smr_report*, const char* header1, const char* seq1, const char* qual1, const uint8_t* record1, size_t record1_len,
                         const char* header2, const char* seq2, const char* qual2, const uint8_t* record2, size_t record2_len);
+/* The streams of smr_fastx_split: stream k is appended to the open aligned.* (k < 4) / other.* (k - 4) file of that index, through gzip under
+ * zip_out.  SMR_ERR_ARG, and nothing is written, when a stream that is not empty has no open file. */
+int smr_report_add_fastx(smr_report*, const uint8_t* bytes, const uint64_t off[9]);
+/* on != 0: smr_report_add / smr_report_add_pair leave aligned.* / other.* alone (smr_report_add_fastx writes them); BLAST, SAM, the OTU map and
+ * aligned_denovo.* are unaffected */
+int smr_report_skip_fastx(smr_report*, int on);
 /* *total_otu = lines of otu_map.txt (Readstats::total_otu, for smr_summary), stored when smr_report_close runs: the pointer must live until then */
 int smr_report_otu_count(smr_report*, uint64_t* total_otu);
 /* One otu_map.txt for a run whose reads went through several report objects (one per device, each fed a contiguous shard of the reads in input

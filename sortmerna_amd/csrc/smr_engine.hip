@@ -16,6 +16,7 @@
 #include "smr_import.hpp"
 #include "smr_export.hpp"
 #include "smr_fastx.hpp"
+#include "smr_fxsplit.hpp"
 #include "smr_ibuild.hpp"
 #include "smr_pgbuild.hpp"
 #include "smr_hostmem.hpp"
@@ -76,6 +77,10 @@ struct Batch {
   std::vector<RState> h_state; std::vector<AlignRec> h_aln; std::vector<uint32_t> h_cigar;       // of the reads with alignments, packed
   std::vector<uint32_t> h_idx, h_map;                                                            // packed position -> read, read -> packed position (or ~0)
   uint32_t last_num_alignments = 1;
+  // SMR_FASTX_KEEP: the FASTA/FASTQ text the batch was parsed from ('\n' behind its fx_n bytes up to a multiple of 16 plus 64) and where every
+  // record's header line and first sequence line start in it -- what smr_reads_record_text reads, for smr_fastx_split.  Taken over from the
+  // upload's scratch, dropped by any other upload into the batch
+  DevBuf<uint8_t> fx_text; DevBuf<unsigned long long> fx_hoff, fx_soff; uint32_t fx_n = 0; bool fx_fastq = false, fx_kept = false;
   unsigned long long redo_seen = 0, win_seen = 0;        // C_SEED_REDO / C_WINDOWS at the end of the previous part (smr_align_part sizes k_seed_pg's candidate pool from the increments)
   bool fetched = false;
 };
@@ -105,6 +110,17 @@ struct FxScratch {
   FxScratch(const FxScratch&) = delete;
   FxScratch& operator=(const FxScratch&) = delete;
   ~FxScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
+// scratch and staging of smr_fastx_split (smr_fxsplit.hpp), grow-only
+struct FxSplitScratch {
+  DevBuf<uint4> rec; DevBuf<unsigned long long> woff, part, tot; DevBuf<uint8_t> hit, out;
+  hipEvent_t ev[6] = {};
+  double ms[4] = {0, 0, 0, 0};            // of the last call: measure, scans, copy, D2H
+  FxSplitScratch() = default;
+  FxSplitScratch(const FxSplitScratch&) = delete;
+  FxSplitScratch& operator=(const FxSplitScratch&) = delete;
+  ~FxSplitScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 struct smr_ctx {
@@ -188,6 +204,7 @@ struct smr_ctx {
   // smr_reads_upload_fastx*: [0] on `stream`, [1] on `upload_stream`; smr_fastx_info / smr_fastx_times of the last call (written under err_m)
   FxScratch fx[2];
   uint64_t fx_info[4] = {0, 0, 0, 0}; double fx_ms[5] = {0, 0, 0, 0, 0};
+  FxSplitScratch fxs;
 };
 struct KpSave { double ms[KP_COUNT]; uint64_t l[KP_COUNT]; };
 
@@ -579,6 +596,7 @@ int reset_batch(smr_ctx* c, Batch& B, hipStream_t st) {
 // room in batch B for n reads of `words` packed words and max_aln alignments each, and the batch's fields; the arrays' contents are the caller's
 int batch_reserve(smr_ctx* c, Batch& B, size_t words, uint32_t n, uint32_t min_len, uint32_t max_len, uint32_t max_aln, hipStream_t st) {
   int rc;
+  if (B.fx_kept) { B.fx_text.release(); B.fx_hoff.release(); B.fx_soff.release(); B.fx_n = 0; B.fx_kept = false; }      // (the text of the reads that are being replaced)
   if (!B.d_ctr) { if ((rc = B.d_ctr.alloc(c, C_TOTAL))) return rc; HIPCHK(c, hipMemsetAsync(B.d_ctr, 0, C_TOTAL * 8, st)); }
   const size_t nw = words + 4, nr = (size_t)n + 1, na = std::max<size_t>((size_t)n * max_aln, 1);     // + slack: window extraction reads 2 words ahead
   if ((rc = B.d_words.reserve(c, nw))) return rc;
@@ -818,6 +836,7 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
 #include "smr_engine_import.hpp"
 #include "smr_engine_export.hpp"
 #include "smr_engine_fastx.hpp"
+#include "smr_engine_fxsplit.hpp"
 extern "C" int smr_counters(smr_ctx* c, uint64_t* out, uint32_t n_db) {
   if (!c || !out) return SMR_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));

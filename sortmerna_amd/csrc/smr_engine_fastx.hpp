@@ -14,12 +14,28 @@ void fx_make_view(smr_reads* r) {
   std::vector<uint32_t>().swap(r->words); std::vector<uint64_t>().swap(r->rec_off);
   r->view = true;
 }
+// SMR_FASTX_KEEP on the host parser's path: the text, padded like fastx_upload pads it, and the parser's record offsets go to the batch
+int fx_keep_host(smr_ctx* c, Batch& B, hipStream_t st, const char* text, size_t n, const smr_reads* r) {
+  const size_t cap = ((n + 15u) & ~(size_t)15u) + 64u;
+  int rc;
+  if ((rc = B.fx_text.alloc(c, cap)) || (rc = B.fx_hoff.alloc(c, r->n)) || (rc = B.fx_soff.alloc(c, r->n))) return rc;
+  if (n) HIPCHK(c, hipMemcpyAsync(B.fx_text, text, n, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(B.fx_text + n, '\n', cap - n, st));
+  if (r->n) {
+    HIPCHK(c, hipMemcpyAsync(B.fx_hoff, r->hdr_off.data(), (size_t)r->n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(B.fx_soff, r->seq_off.data(), (size_t)r->n * 8, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  B.fx_n = (uint32_t)n; B.fx_fastq = r->fastq; B.fx_kept = true;
+  return SMR_OK;
+}
 int fx_host_path(smr_ctx* c, Batch& B, hipStream_t st, const char* name, const char* text, size_t n, const std::shared_ptr<void>& owner, uint32_t max_aln, uint32_t flags,
                  smr_reads** out, uint64_t lines, uint64_t bytes) {
   smr_reads* r = nullptr; std::string why;
   int rc = smr::load_fastx_bytes(name, text, n, owner, 0, true, &r, why);
   if (rc != SMR_OK) { set_err(c, why); return rc; }
   rc = upload_into(c, B, r, max_aln, st);
+  if (rc == SMR_OK && (flags & SMR_FASTX_KEEP)) rc = fx_keep_host(c, B, st, text, n, r);
   if (rc != SMR_OK) { delete r; return rc; }
   fx_report(c, 1, lines, r->n, bytes, nullptr);
   if (out) { if (flags & SMR_FASTX_VIEW) fx_make_view(r); *out = r; } else delete r;
@@ -121,6 +137,10 @@ int fastx_upload(smr_ctx* c, Batch& B, FxScratch& S, hipStream_t st, const char*
   double ms[5] = {0, 0, 0, 0, 0};
   for (int k = 0; k < 5; k++) { float f = 0; if (hipEventElapsedTime(&f, S.ev[k], S.ev[k + 1]) == hipSuccess) ms[k] = f; }
   fx_report(c, 0, nl, R, n, ms);
+  if (flags & SMR_FASTX_KEEP) {                                 // (handed over, not copied: the stream's scratch allocates again on its next use)
+    B.fx_text = std::move(S.text); B.fx_hoff = std::move(S.hoff); B.fx_soff = std::move(S.soff);
+    B.fx_n = n; B.fx_fastq = fastq != 0; B.fx_kept = true;
+  }
   if (out) *out = r;
   return SMR_OK;
 }

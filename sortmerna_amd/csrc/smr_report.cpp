@@ -96,6 +96,7 @@ struct smr_report {
   std::map<std::pair<uint32_t, uint32_t>, const smr_index*> parts;
   std::map<std::pair<uint32_t, uint32_t>, std::string> blast, sam;     // rows per (index, part)
   std::string err, cmdline = "libsmr_hip";
+  bool skip_fx = false;                                                // smr_report_skip_fastx: aligned.* / other.* come from smr_report_add_fastx
 };
 
 extern "C" int smr_report_open(const char* out_dir, const smr_report_opts* opts, int is_fastq, smr_report** out, char* err, size_t errcap) {
@@ -161,7 +162,7 @@ extern "C" int smr_report_add(smr_report* r, const char* header, const char* seq
   std::vector<Aln> alns;
   uint32_t ic[4];
   if (!parse_record(record, record_len, is_hit, alns, ic)) { r->err = "malformed record"; return SMR_ERR_ARG; }
-  write_fx(r, is_hit ? r->f_aligned[0] : r->f_other[0], header, seq, qual);
+  if (!r->skip_fx) write_fx(r, is_hit ? r->f_aligned[0] : r->f_other[0], header, seq, qual);
   if (r->o.denovo && is_dn(ic)) write_fx(r, r->f_denovo[0], header, seq, qual);
   if (r->o.otu_map) { const int rc = add_otu(r, header, seq, alns, ic); if (rc != SMR_OK) return rc; }
   return add_rows(r, header, seq, qual, alns);
@@ -178,7 +179,7 @@ extern "C" int smr_report_add_pair(smr_report* r, const char* header1, const cha
   const bool both = hit[0] && hit[1], any = hit[0] || hit[1];
   const smr_report_opts& o = r->o;
   // aligned.* (ReportFastx::append): nothing when neither mate aligned
-  if (any) {
+  if (any && !r->skip_fx) {
     for (int i = 0; i < 2; i++) {
       int idx = -1;
       if (r->num_out == 1) { if (o.paired_out ? both : (o.paired_in || hit[i])) idx = 0; }
@@ -189,7 +190,7 @@ extern "C" int smr_report_add_pair(smr_report* r, const char* header1, const cha
     }
   }
   // other.* (ReportFxOther::append): nothing when both mates aligned
-  if (!both) {
+  if (!both && !r->skip_fx) {
     for (int i = 0; i < 2; i++) {
       int idx = -1;
       if (r->num_out == 1) { if (o.paired_in ? !any : (o.paired_out || !hit[i])) idx = 0; }
@@ -215,6 +216,28 @@ extern "C" int smr_report_add_pair(smr_report* r, const char* header1, const cha
     if (o.otu_map) { const int rc = add_otu(r, hd[i], sq[i], alns[i], ic[i]); if (rc != SMR_OK) return rc; }
     const int rc = add_rows(r, hd[i], sq[i], ql[i], alns[i]); if (rc != SMR_OK) return rc;
   }
+  return SMR_OK;
+}
+
+extern "C" int smr_report_add_fastx(smr_report* r, const uint8_t* bytes, const uint64_t off[9]) {
+  if (!r || !off) return SMR_ERR_ARG;
+  for (int k = 0; k < 8; k++) {
+    if (off[k + 1] < off[k]) { r->err = "smr_report_add_fastx: the offsets decrease"; return SMR_ERR_ARG; }
+    const Out& f = k < 4 ? r->f_aligned[k] : r->f_other[k - 4];
+    if (off[k + 1] > off[k] && (!bytes || !f.is_open())) { r->err = "smr_report_add_fastx: stream " + std::to_string(k) + " is not empty and has no open file"; return SMR_ERR_ARG; }
+  }
+  for (int k = 0; k < 8; k++) {
+    Out& f = k < 4 ? r->f_aligned[k] : r->f_other[k - 4];
+    for (uint64_t at = off[k]; at < off[k + 1];) {                     // (gzwrite takes an unsigned count)
+      const uint64_t take = std::min<uint64_t>(off[k + 1] - at, 1u << 30);
+      f.put(bytes + at, (size_t)take); at += take;
+    }
+  }
+  return SMR_OK;
+}
+extern "C" int smr_report_skip_fastx(smr_report* r, int on) {
+  if (!r) return SMR_ERR_ARG;
+  r->skip_fx = on != 0;
   return SMR_OK;
 }
 

@@ -234,6 +234,7 @@ def pigeonhole_layout(index):
 
 ROUTE_RECORD, ROUTE_GATHER, ROUTE_CHAIN, ROUTE_EXT = 1, 2, 4, 8      # SMR_ROUTE_* of smr_hip.h (Engine.cand_routes)
 FASTX_VIEW = 1                                                       # SMR_FASTX_VIEW (Engine.upload_fastx)
+FASTX_KEEP = 2                                                       # SMR_FASTX_KEEP
 
 
 class Engine:
@@ -356,13 +357,14 @@ class Engine:
         self._chk(self.L.smr_reads_upload_batch(self.h, batch, reads.h, max_alignments_per_read), "smr_reads_upload_batch")
         self._batch_n[batch] = reads.count
 
-    def upload_fastx(self, data_or_path, max_alignments_per_read=1, batch=None, view=False):
+    def upload_fastx(self, data_or_path, max_alignments_per_read=1, batch=None, view=False, keep=False):
         """smr_reads_upload_fastx*: FASTA/FASTQ text (bytes), or the file at a path (str; gzip is inflated), parsed and 2-bit packed on the device
         into the selected batch -- or, with batch=k, into batch k on the upload stream.  Returns the Reads the host parser would have made of
         the same bytes, copied back from the device; view=True leaves the packed words there (SMR_FASTX_VIEW: record_text and the statistics
-        work, digest is 0, slice and upload raise)."""
+        work, digest is 0, slice and upload raise).  keep=True leaves the text with the batch on the device (SMR_FASTX_KEEP: the text plus 16 bytes
+        per record of device memory) for fastx_split."""
         h = C.c_void_p()
-        flags = FASTX_VIEW if view else 0
+        flags = (FASTX_VIEW if view else 0) | (FASTX_KEEP if keep else 0)
         keep = None
         if isinstance(data_or_path, str):
             if batch is not None:
@@ -393,6 +395,28 @@ class Engine:
         ms = (C.c_double * 5)()
         self._chk(self.L.smr_fastx_times(self.h, ms), "smr_fastx_times")
         return dict(zip(("h2d", "lines", "records", "pack", "d2h"), (float(x) for x in ms)))
+
+    def fastx_split(self, layout=0, mates=None, paired_in=False, paired_out=False, out2=False, sout=False, aligned=True, other=True, hit=None):
+        """smr_fastx_split: the aligned.* / other.* FASTX streams of the selected batch (uploaded with keep=True), written on the device -> a list
+        of eight bytes objects, aligned[0..3] then other[0..3].  layout 0: single reads; 1: mates interleaved; 2: the mates are the reads of batch
+        `mates`.  hit: one truth value per read (the selected batch's, then the mates') used instead of the batch's own is_hit."""
+        o = capi.FxSplitOpts(int(layout), int(bool(paired_in)), int(bool(paired_out)), int(bool(out2)), int(bool(sout)), int(bool(aligned)), int(bool(other)))
+        hb = None if hit is None else (C.c_uint8 * max(len(hit), 1))(*[1 if x else 0 for x in hit])
+        m = -1 if mates is None else int(mates)
+        off = (C.c_uint64 * 9)()
+        need = C.c_uint64(0)
+        self._chk(self.L.smr_fastx_split(self.h, m, C.byref(o), hb, None, 0, off, C.byref(need)), "smr_fastx_split")
+        buf = (C.c_uint8 * max(need.value, 1))()
+        if need.value:
+            self._chk(self.L.smr_fastx_split(self.h, m, C.byref(o), hb, buf, need.value, off, C.byref(need)), "smr_fastx_split")
+        raw = bytes(buf)
+        return [raw[off[k]:off[k + 1]] for k in range(8)]
+
+    def fastx_split_times(self):
+        """HIP-event ms of the last fastx_split: dict(measure, scans, copy, d2h)"""
+        ms = (C.c_double * 4)()
+        self._chk(self.L.smr_fastx_split_times(self.h, ms), "smr_fastx_split_times")
+        return dict(zip(("measure", "scans", "copy", "d2h"), (float(x) for x in ms)))
 
     def reset_state(self):
         self._chk(self.L.smr_state_reset(self.h), "smr_state_reset")

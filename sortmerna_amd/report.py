@@ -62,6 +62,18 @@ class Report:
         self._chk(self.L.smr_report_add_pair(self.h, h1.encode(), s1.encode(), q1.encode() if q1 else None, r1, len(r1),
                                              h2.encode(), s2.encode(), q2.encode() if q2 else None, r2, len(r2)), "smr_report_add_pair")
 
+    def add_fastx(self, streams):
+        """the eight streams of Engine.fastx_split (aligned[0..3], other[0..3]) appended to the open aligned.* / other.* files (smr_report_add_fastx)"""
+        off = (C.c_uint64 * 9)()
+        for k in range(8):
+            off[k + 1] = off[k] + len(streams[k])
+        blob = b"".join(streams)
+        self._chk(self.L.smr_report_add_fastx(self.h, blob if blob else None, off), "smr_report_add_fastx")
+
+    def skip_fastx(self, on=True):
+        """add / add_pair leave aligned.* / other.* alone: add_fastx writes them (smr_report_skip_fastx)"""
+        self._chk(self.L.smr_report_skip_fastx(self.h, int(bool(on))), "smr_report_skip_fastx")
+
     def merge_otu_from(self, other):
         """the OTU map entries of `other` (the next shard of the reads, in input order) behind this report's; `other` then writes no map"""
         self._chk(self.L.smr_report_otu_merge(self.h, other.h), "smr_report_otu_merge")
