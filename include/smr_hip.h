@@ -199,6 +199,10 @@ int  smr_device_count(void);   /* HIP devices this process sees (0: none -- ther
 int  smr_create(int device, smr_ctx** out, char* err, size_t errcap);
 void smr_destroy(smr_ctx*);
 const char* smr_last_error(const smr_ctx*);
+/* The environment switches of the library as this context latched them in smr_create (every switch of a context is read there, once; clamped):
+ * one NAME=value line per switch, NUL-terminated.  Returns the size needed (the buffer is filled when it is large enough) or SMR_ERR_ARG.
+ * INTEGRATION.md lists the names, defaults and meanings. */
+int  smr_tuning_text(const smr_ctx*, char* buf, size_t cap);
 
 /* Copy an index part to HBM; it stays resident under `slot` (0..63) until freed. */
 int smr_index_upload(smr_ctx*, const smr_index*, int slot);

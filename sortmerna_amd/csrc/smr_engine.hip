@@ -21,6 +21,7 @@
 #include "smr_pgbuild.hpp"
 #include "smr_hostmem.hpp"
 #include "smr_devbuf.hpp"
+#include "smr_tuning.hpp"
 
 using namespace smr;
 
@@ -124,6 +125,8 @@ struct FxSplitScratch {
 };
 
 struct smr_ctx {
+  const Tuning tune;                      // the environment switches as smr_create found them (smr_tuning.hpp)
+  explicit smr_ctx(const Tuning& t) : tune(t) {}
   int device = 0;
   DevStream stream, upload_stream;        // upload_stream: smr_reads_upload_batch, H2D of batch k+1 while batch k is aligned on `stream`
   std::string err;                        // last error; written under err_m (smr_reads_upload_batch runs on a second host thread)
@@ -137,23 +140,17 @@ struct smr_ctx {
   uint64_t n_pool_grown = 0;              // seed-hit pool regrows (C_ERR_POOL) since smr_create (smr_seed_pool_info)
   uint32_t pool_inline = 0;               // SeedBufs::seg_inline of the last seed-stage launch (smr_seed_pool_info)
   uint32_t hcap = 4;                      // lane-local hit list capacity of k_seed_search; doubles (and the part is redone) on overflow
-  int seed_exact = 0;                     // 1: k_seed_search for every wave (exact work counters); 0: k_seed_pg (+ redo of the waves whose pool overflowed)
+  int seed_exact = tune.seed_exact;       // 1: k_seed_search for every wave (exact work counters); 0: k_seed_pg (+ redo of the waves whose pool overflowed)
   // Bloom words per read in k_cand (a power of two, 64..512): fewer = more blocks of k_cand per CU, but more reads marked for k_chain by a false
   // collision.  Measured per 2 M-read launch (profiles/r3s18_*): 512 words k_cand 1.07 ms + k_chain 6.01 ms, 256: 0.59 + 6.06, 128: 0.48 + 6.07
   // (16 KB of LDS per block: the 8 blocks per CU that the wave slots allow)
-  uint32_t cand_bloom = 128;
-  // repeated seeds (k_seed_dedup): keys with at least this many tuples in a launch (and four times the average) are searched once per different seed; 0: off
-  uint32_t hot_min = getenv("SMR_SEED_DEDUP") ? (uint32_t)std::max(0, atoi(getenv("SMR_SEED_DEDUP"))) : 1024u;
-  // one seed sort for the index parts of a batch (SharedSort below): 0 off, 1 when the part in hand is not the batch's last, 2 always (tests)
-  int seed_shared = getenv("SMR_SEED_SHARED") ? atoi(getenv("SMR_SEED_SHARED")) : 1;
+  uint32_t cand_bloom = tune.cand_bloom;
+  int seed_shared = tune.seed_shared;     // one seed sort for the index parts of a batch (SharedSort below); 0 for good once its arrays found no room
   DevBuf<uint16_t> d_sw_scr; uint32_t sw_scr_stride = 0;      // scratch rows of the striped Smith-Waterman slow path (smr_sw_striped.hpp), one per block
   int last_seed_slot = -1;                 // index slot of the last smr_seed_scan (smr_seed_hits_fetch translates its ids back)
   SharedSort shared;
   uint64_t n_seed_shared = 0, n_seed_shared_builds = 0;      // smr_prof
-  uint32_t ccap = PG_CAND_CAP0;           // candidate records per wave of k_seed_pg; doubles when more than 1/64 of the waves of a part overflow
-  // k_seed_pg: waves of the launch (0: one per wave chunk the batch can have; else a wave walks chunks it, it + grid, ...), XCD-aware chunk order
-  uint32_t pg_grid = getenv("SMR_PG_GRID") ? (uint32_t)atoi(getenv("SMR_PG_GRID")) : 262144u;
-  int pg_swz = getenv("SMR_PG_SWZ") ? atoi(getenv("SMR_PG_SWZ")) : 0;
+  uint32_t ccap = tune.ccap;              // candidate records per wave of k_seed_pg; doubles when more than 1/64 of the waves of a part overflow
   SeedScratch seed; SeedBufs sb = {};     // seed-stage scratch and the kernels' view of it (smr_seed.hpp)
   uint64_t sb_slots = 0; uint32_t sb_nk = 0;
   uint32_t chain_blocks = 0;
@@ -165,28 +162,21 @@ struct smr_ctx {
   DevBuf<uint32_t> d_fidx; DevBuf<RState> d_fstate; DevBuf<AlignRec> d_faln;       // staging of smr_results_fetch
   DevBuf<uint32_t> d_fidcov;                                                       // ... of the per-read id / coverage counters
   DevBuf<uint8_t> d_xbytes; DevBuf<unsigned long long> d_xoff, d_xpart;            // staging of smr_state_export (d_xpart grows with d_xoff)
-  int sw_mode = getenv("SMR_SW_PACKED") ? atoi(getenv("SMR_SW_PACKED")) : 2;   // 1 / 2: packed 16-bit Smith-Waterman kernels (smr_sw_pk.hpp; 2 = lane hand-over by wave_ror, measured faster) where they apply
+  int sw_mode = tune.sw_packed;           // 0 once the packed kernels failed the self-check of smr_create
   // (keys_cap, pairs_cap, hits_cap: per block of k_chain, the layout its kernels are told)
   DevBuf<unsigned long long> d_keys; uint32_t keys_cap = 0;
   DevBuf<unsigned long long> d_pairs; DevBuf<uint32_t> d_lis; uint32_t pairs_cap = 0;
   DevBuf<uint2> d_hits; uint32_t hits_cap = 0;
   DevBuf<uint8_t> d_rdq;
-  // k_cand -> k_chain hand-over (smr_chain.hpp): {offset, npos} per read, the records (SMR_HANDOVER=0 switches it off)
-  int handover = getenv("SMR_HANDOVER") ? atoi(getenv("SMR_HANDOVER")) : 1;
+  // k_cand -> k_chain hand-over (smr_chain.hpp): {offset, npos} per read, the records (tune.handover)
   DevBuf<uint2> d_mrec; DevBuf<uint32_t> d_mpool;
-  // the candidate walk in rounds (smr_walk.hpp): walk kernel -> Smith-Waterman over a task list -> next list; SMR_WALK_SPLIT=0: k_chain walks every marked read
-  int walk_split = getenv("SMR_WALK_SPLIT") ? atoi(getenv("SMR_WALK_SPLIT")) : 1;
-  uint32_t walk_rounds = getenv("SMR_WALK_ROUNDS") ? (uint32_t)std::max(1, std::min(32, atoi(getenv("SMR_WALK_ROUNDS")))) : 8u;      // the last one scores in the kernel
-  uint32_t walk_k = getenv("SMR_WALK_K") ? (uint32_t)std::max(1, std::min((int)WK_MAX, atoi(getenv("SMR_WALK_K")))) : 4u;           // tasks a read leaves per round, at least (smr_walk.hpp walk_tasks_per_read)
-  int walk_gather = getenv("SMR_WALK_GATHER") ? atoi(getenv("SMR_WALK_GATHER")) : 1;     // 0: only reads with a record of k_cand go through the rounds (at most 64 positions)
-  uint32_t walk_assume = getenv("SMR_WALK_ASSUME") ? (uint32_t)atoi(getenv("SMR_WALK_ASSUME")) : 3u;                                 // round 0 predicts "aligns" from this many seeds of the best candidate
+  // the candidate walk in rounds (smr_walk.hpp): walk kernel -> Smith-Waterman over a task list -> next list (tune.walk_*)
   DevBuf<uint2> d_wlist[2]; DevBuf<WState> d_wstate[2]; DevBuf<WTask> d_wtask[2]; DevBuf<uint2> d_wres[2];
   DevBuf<uint32_t> d_wtidx, d_wslow; DevBuf<unsigned long long> d_wctr; size_t walk_cap = 0; uint32_t walk_kcap = 0;      // walk_cap x walk_kcap: the layout of d_wtidx
   size_t walk_lds_attr = 0, pg_lds_attr = 0, search_lds_attr = 0;
   uint64_t sw16_launches[8] = {};          // k_sw16<13 | 19 | 26 | 32> launched by the walk rounds [0..3] and by the begin-cell stage [4..7] (smr_sw16_launches)
   // rounds per (strand, pass): without SMR_WALK_ROUNDS the number adapts to what the previous part needed (the last round with more than a few
   // reads listed + the closing one: an empty round still costs three launches, ~70 us of stream time; 8 -> 4 rounds = 3 % of the bench step)
-  bool walk_rounds_fixed = getenv("SMR_WALK_ROUNDS") != nullptr;
   uint32_t walk_need[3] = {0, 0, 0};
   DevBuf<unsigned long long> d_wstat; uint32_t wstat_n = 0; int wstat_pass[8] = {}; uint32_t wstat_rm[8] = {};
   DevBuf<int> d_bound;                                                 // strip-boundary rows of the SW kernels (reads of more than one strip), per block
@@ -306,8 +296,9 @@ DIndex dindex(const DevIndex& d) {
 DReads dreads(const smr_ctx* c) { DReads r; r.words = c->b->d_words; r.rec_off = c->b->d_rec_off; r.len = c->b->d_len; r.n = c->b->n; r.max_len = c->b->max_len; return r; }
 
 // blocks of k_chain (the one place that says how many): 3 waves per SIMD by registers
+constexpr uint32_t CHAIN_WAVES_PER_CU = 12;
 uint32_t chain_blocks(smr_ctx* c) {
-  if (c->chain_blocks == 0) c->chain_blocks = (uint32_t)c->n_cu * (getenv("SMR_CHAIN_WPC") ? atoi(getenv("SMR_CHAIN_WPC")) : 12);
+  if (c->chain_blocks == 0) c->chain_blocks = (uint32_t)c->n_cu * CHAIN_WAVES_PER_CU;
   return c->chain_blocks;
 }
 // k_chain's scratch per block; the retry ladder of smr_align_part releases an array (and changes its *_cap) to have it made again here
@@ -385,16 +376,16 @@ extern "C" int smr_create(int device, smr_ctx** out, char* err, size_t errcap) {
     return SMR_ERR_DEVICE;
   }
   if (device < 0 || device >= ndev) { if (err && errcap) snprintf(err, errcap, "device %d out of range (%d devices)", device, ndev); return SMR_ERR_ARG; }
-  auto c = new smr_ctx();                                 // (deleting it releases whatever the steps below have made)
+  // every switch of the context is read here, once; the bounds and defaults that belong to the device headers go in by value
+  const TuningLimits lim = {WK_MAX, PG_CAND_CAP0, PG_CAND_CAP_MAX, CAND_BLOOM_WORDS, C_NSHARD, SEED_HOT_BIN_MIN, SEED_HOT_SUB, SMR_SW_SELFCHECK_CASES};
+  auto c = new smr_ctx(read_tuning(lim));                 // (deleting it releases whatever the steps below have made)
   c->device = device;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&c->stream.s) != hipSuccess || hipStreamCreate(&c->upload_stream.s) != hipSuccess ||
       c->d_ctr_snap.alloc(c, C_TOTAL) != SMR_OK) {
     if (err && errcap) snprintf(err, errcap, "cannot initialise device %d", device);
     delete c; return SMR_ERR_DEVICE;
   }
-  if (const char* e = getenv("SMR_SEED_EXACT")) c->seed_exact = atoi(e) != 0;
-  if (const char* e = getenv("SMR_CAND_BLOOM")) { uint32_t b = 64; while (b < CAND_BLOOM_WORDS && b < (uint32_t)atoi(e)) b <<= 1; c->cand_bloom = b; }      // measurement aid
-  if (const char* e = getenv("SMR_PG_CAND_CAP")) c->ccap = std::min<uint32_t>(PG_CAND_CAP_MAX, std::max<uint32_t>(4u, (uint32_t)atoi(e)));      // test aid: a small candidate pool
+  say(c->tune, "environment switches of this context:\n%s", tuning_text(c->tune).c_str());
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
   if (c->b->d_ctr.alloc(c, C_TOTAL) != SMR_OK) { if (err && errcap) snprintf(err, errcap, "hipMalloc failed"); delete c; return SMR_ERR_DEVICE; }
@@ -402,8 +393,7 @@ extern "C" int smr_create(int device, smr_ctx** out, char* err, size_t errcap) {
   c->b->used = true;
   if (c->sw_mode >= 1) {
     // the packed Smith-Waterman kernel must agree with the 32-bit kernel on this device, or it is not used
-    uint32_t cases = SMR_SW_SELFCHECK_CASES;
-    if (const char* e2 = getenv("SMR_SW_SELFCHECK")) cases = (uint32_t)atoi(e2);
+    const uint32_t cases = c->tune.sw_selfcheck;
     uint64_t bad = 0;
     if (cases > 0 && (smr_sw_selfcheck(c, cases, 20260926u, 700, &bad) != SMR_OK || bad != 0)) {
       fprintf(stderr, "libsmr_hip: packed Smith-Waterman kernel disagrees with the 32-bit kernel on %llu self-check cases; using the 32-bit kernel\n", (unsigned long long)bad);
@@ -419,6 +409,13 @@ extern "C" void smr_destroy(smr_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   delete c;
+}
+
+extern "C" int smr_tuning_text(const smr_ctx* c, char* buf, size_t cap) {
+  if (!c) return SMR_ERR_ARG;
+  const std::string s = tuning_text(c->tune);
+  if (buf && cap > s.size()) memcpy(buf, s.c_str(), s.size() + 1);
+  return (int)s.size() + 1;
 }
 
 extern "C" const char* smr_last_error(const smr_ctx* c) {
@@ -512,7 +509,7 @@ extern "C" int smr_index_upload(smr_ctx* c, const smr_index* ix, int slot) {
   }
   // The pigeonhole layout of the tries (what k_seed_pg reads) is built on the device from the arena just uploaded (smr_pgbuild.hpp).  An index
   // that already carries the host-built layout (smr_index_selfcheck, SMR_PG_HOST=1) is uploaded as it is.
-  bool host_pg = getenv("SMR_PG_HOST") && atoi(getenv("SMR_PG_HOST"));
+  bool host_pg = c->tune.pg_host;
   { std::lock_guard<std::mutex> l_(const_cast<smr_index*>(ix)->pg_mutex); host_pg = host_pg || !ix->root3.empty(); }     // (another context may be inside smr_build_pigeonhole on the same host index)
   if (host_pg) {
     std::string why;
@@ -523,8 +520,8 @@ extern "C" int smr_index_upload(smr_ctx* c, const smr_index* ix, int slot) {
     HIPCHK(c, hipMemcpyAsync(d.root3, ix->root3.data(), ix->root3.size() * 4, hipMemcpyHostToDevice, c->stream));
     d.pg_words = ix->pg.size() >= 4 ? ix->pg.size() - 4 : 0;
   } else if ((rc = build_pigeonhole_device(c, d, (uint32_t)ix->lookup.size(), ix->lnwin / 2))) return rc;
-  if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: index part: tries %.2f GB, pigeonhole arena %.2f GB (%s), positions %.2f GB\n", ix->trie.size() * 4e-9, d.pg_words * 4e-9,
-                                     host_pg ? "host-built" : "built on the device", ix->pos_arr.size() * 4e-9);
+  say(c->tune, "index part: tries %.2f GB, pigeonhole arena %.2f GB (%s), positions %.2f GB\n", ix->trie.size() * 4e-9, d.pg_words * 4e-9,
+      host_pg ? "host-built" : "built on the device", ix->pos_arr.size() * 4e-9);
   if ((rc = d.ref_seq.alloc(c, ix->ref_seq.size() + 64))) return rc;
   if ((rc = d.ref_off.alloc(c, ix->ref_off.size()))) return rc;
   HIPCHK(c, hipMemcpyAsync(d.ref_seq, ix->ref_seq.data(), ix->ref_seq.size(), hipMemcpyHostToDevice, c->stream));
@@ -665,8 +662,7 @@ extern "C" int smr_reads_upload_batch(smr_ctx* c, int batch, const smr_reads* r,
 namespace {
 int ensure_pool(smr_ctx* c) {          // seed-hit pool: scratch shared by all batches, sized for the selected one before its kernels run
   uint64_t want_pool = std::max<uint64_t>((uint64_t)c->b->n * 64 + (1u << 20), 1u << 22);
-  if (const char* e = getenv("SMR_SEED_POOL_WORDS"))          // test aid: start the pool small (regrow) or large (offsets above 2^30)
-    want_pool = std::min<uint64_t>(std::max<uint64_t>(strtoull(e, nullptr, 0), C_NSHARD), 0x7FFFFFF0ull);
+  if (c->tune.pool_words) want_pool = c->tune.pool_words;     // test aid: start the pool small (regrow) or large (offsets above 2^30)
   if (c->pool_words < want_pool) { int rc = c->d_pool.alloc(c, want_pool); if (rc) return rc; c->pool_words = want_pool; }
   return SMR_OK;
 }
@@ -714,8 +710,8 @@ int ensure_striped_scratch(smr_ctx* c, DParams& P, const smr_params* p) {
   const size_t need = (size_t)std::max<uint32_t>(chain_blocks(c), (uint32_t)c->n_cu * 8u) * stride;
   if (c->d_sw_scr.cap() < need || c->sw_scr_stride < stride) { int rc = c->d_sw_scr.alloc(c, need); if (rc) return rc; c->sw_scr_stride = stride; }
   P.sw_scratch = c->d_sw_scr; P.sw_scratch_stride = c->sw_scr_stride;
-  if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: scoring scheme %d/%d/%d (N %d): %s -- Smith-Waterman through the slow path that reproduces ssw.c's stripe geometry\n",
-                                     p->match, p->mismatch, p->gap_open, p->score_N, scheme_unsupported(p->mismatch, p->score_N, p->gap_open, p->gap_ext));
+  say(c->tune, "scoring scheme %d/%d/%d (N %d): %s -- Smith-Waterman through the slow path that reproduces ssw.c's stripe geometry\n",
+      p->match, p->mismatch, p->gap_open, p->score_N, scheme_unsupported(p->mismatch, p->score_N, p->gap_open, p->gap_ext));
   return SMR_OK;
 }
 
@@ -770,7 +766,7 @@ int judge_attempt(smr_ctx* c, const DParams& P, const std::vector<unsigned long 
     B.redo_seen = h[C_SEED_REDO]; B.win_seen = h[C_WINDOWS];
     if (!retry && redo * 64 > waves && c->ccap < PG_CAND_CAP_MAX) {
       c->ccap *= 2;
-      if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: %llu of ~%llu seed-search waves overflowed their candidate pool: %u records per wave from now on\n", redo, waves, c->ccap);
+      say(c->tune, "%llu of ~%llu seed-search waves overflowed their candidate pool: %u records per wave from now on\n", redo, waves, c->ccap);
     }
   }
   if (h[C_ERR_SCAP]) {
@@ -778,8 +774,8 @@ int judge_attempt(smr_ctx* c, const DParams& P, const std::vector<unsigned long 
     // per-block table in global memory; the candidate keys need room for as many members
     if (c->chain_ext) { set_err(c, "more than 49152 references share seeds with one read (candidate set capacity)"); return SMR_ERR_CAPACITY; }
     c->chain_ext = true; retry = true; c->cinfo_retry[4]++;
-    if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: a read shares seeds with more references than its wave's LDS table holds: per-block global candidate tables enabled (%.1f GB)\n",
-                                       (double)c->chain_blocks * (4.0 * CH_EXT_CAP * 4 + (double)c->pairs_cap * 8 + (double)CH_EXT_CAP * 8) / 1e9);
+    say(c->tune, "a read shares seeds with more references than its wave's LDS table holds: per-block global candidate tables enabled (%.1f GB)\n",
+        (double)c->chain_blocks * (4.0 * CH_EXT_CAP * 4 + (double)c->pairs_cap * 8 + (double)CH_EXT_CAP * 8) / 1e9);
     if (c->keys_cap < CH_EXT_CAP) { c->d_keys.release(); c->keys_cap = 0; c->keys_need = CH_EXT_CAP; }
   }
   if (h[C_ERR_SLOTS]) { set_err(c, "a read produced more alignments than max_alignments_per_read (smr_reads_upload)"); return SMR_ERR_CAPACITY; }
@@ -1136,7 +1132,7 @@ extern "C" int smr_prof_get(smr_ctx* c, smr_prof* o) {
     if (!c->bt[k].d_ctr) continue;
     HIPCHK(c, hipMemcpyAsync(t.data(), c->bt[k].d_ctr, C_TOTAL * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (getenv("SMR_DEBUG_PHASES")) {
+    if (c->tune.debug_phases) {
       unsigned long long ph[7] = {0, 0, 0, 0, 0, 0, 0};
       for (int s2 = 0; s2 < C_NSHARD; s2++) for (int q = 0; q < 7; q++) ph[q] += t[C_SHARDS + C_SHARD_W * s2 + C_SHARD_PH + q];
       fprintf(stderr, "[smr] phase cycles (batch %d): %llu %llu %llu %llu %llu %llu %llu  (-DSMR_CHAIN_PHASES: claim, gather+prefix, walk1, walk2+cands, pairs+sort, "

@@ -24,8 +24,9 @@ int ensure_bound(smr_ctx* c, uint32_t blocks, uint32_t rf) {
 // What one smr_align_part settles once for all its launches.  lng: the batch has reads of more than one Smith-Waterman strip (the short-read
 // instantiations carry none of their state).  striped: the slow path that reproduces ssw.c's stripe geometry (instantiations of its own); it
 // scores in k_chain and k_begins alone, so neither the candidate walk in rounds (split) nor four problems per wave (x4) go with it -- both
-// want the packed kernels.  rows: the k_sw16 instantiation for the batch's spans.
-struct AlignPlan { uint32_t ml, rf, rq; size_t lds; bool lng, striped, split, x4; int rows; };
+// want the packed kernels.  begins_sw16: the begin cells sixteen per wave through k_sw16 (launch_begins adds only whether the walk's task
+// buffers are there and large enough).  rows: the k_sw16 instantiation for the batch's spans.
+struct AlignPlan { uint32_t ml, rf, rq; size_t lds; bool lng, striped, split, x4, begins_sw16; int rows; };
 int sw16_rows(uint32_t max_len) {
   const uint32_t wmq = std::min<uint32_t>(max_len, WK_MAX_ROWS);
   return wmq <= 104 ? 13 : wmq <= 152 ? 19 : wmq <= 208 ? 26 : 32;
@@ -38,9 +39,9 @@ AlignPlan align_plan(const smr_ctx* c, const DParams& P) {
   a.lng = max_len > SW_X4_MAX_ROWS;
   a.striped = P.sw_mode < 0;
   // the split path takes the marked reads with a record of k_cand (the hand-over) whose Smith-Waterman problems fit the packed kernels
-  a.split = packed && c->walk_split && c->handover && sw_pk_fits((int)std::min<uint32_t>(max_len, WK_MAX_ROWS), (int)a.rq, P.match, P.mismatch, P.score_N, P.gap_open);
-  a.x4 = packed && !a.lng && (long long)max_len * P.match + 255 < 32768 && a.rf + 128 <= 8191 && P.gap_open + P.mismatch >= 0 && P.gap_open + P.score_N >= 0 &&
-         P.match + P.gap_open <= 255 && P.score_N + P.gap_open <= 255;
+  a.split = packed && c->tune.walk_split && c->tune.handover && sw_pk_fits((int)std::min<uint32_t>(max_len, WK_MAX_ROWS), (int)a.rq, P.match, P.mismatch, P.score_N, P.gap_open);
+  a.x4 = packed && !a.lng && sw_pk_fits((int)max_len, (int)a.rf, P.match, P.mismatch, P.score_N, P.gap_open);
+  a.begins_sw16 = a.x4 && c->tune.walk_split && !c->tune.begins_x4;
   a.rows = sw16_rows(max_len);
   return a;
 }
@@ -75,7 +76,7 @@ __global__ void k_wstat(const unsigned long long* __restrict__ wctr, unsigned lo
 // closing round takes in its stride, + that closing round; when the closing round itself was that full, two more next time.  Whatever the
 // number, the closing round ends every listed read's pass: the records do not depend on it (WALK_VARIANTS of the parity tests).
 int adapt_walk_rounds(smr_ctx* c) {
-  if (c->walk_rounds_fixed || !c->wstat_n || !c->d_wstat) return SMR_OK;
+  if (c->tune.walk_rounds_fixed || !c->wstat_n || !c->d_wstat) return SMR_OK;
   unsigned long long h[8 * 32];
   HIPCHK(c, hipMemcpyAsync(h, c->d_wstat, (size_t)c->wstat_n * 32 * 8, hipMemcpyDeviceToHost, c->stream));       // (on the context's stream, like read_ctr: no other stream is waited for)
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -88,8 +89,8 @@ int adapt_walk_rounds(smr_ctx* c) {
   }
   // more rounds at once; fewer by half the difference per part (parts of one run differ: eight databases, batches of a mixed sample)
   for (int p = 0; p < 3; p++) if (need[p]) {
-    const uint32_t prev = c->walk_need[p] ? c->walk_need[p] : c->walk_rounds;
-    c->walk_need[p] = std::min(c->walk_rounds, need[p] >= prev ? need[p] : prev - std::max(1u, (prev - need[p]) / 2u));
+    const uint32_t prev = c->walk_need[p] ? c->walk_need[p] : c->tune.walk_rounds;
+    c->walk_need[p] = std::min(c->tune.walk_rounds, need[p] >= prev ? need[p] : prev - std::max(1u, (prev - need[p]) / 2u));
   }
   c->wstat_n = 0;
   return SMR_OK;
@@ -109,14 +110,14 @@ int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, const AlignPl
   if ((rc = ensure_bound(c, c->chain_blocks, rf))) return rc;
   int* const gb = plan.lng ? c->d_bound.get() : nullptr;
   uint8_t* const grd = plan.lng ? c->d_rdq.get() : nullptr;
-  if (c->handover) {
+  if (c->tune.handover) {
     // {offset, npos} per read; CAND_REC_WORDS words per read of the batch, one slice per block of k_cand
     if ((rc = c->d_mrec.reserve(c, B.n)) || (rc = c->d_mpool.reserve(c, (size_t)((B.n + CAND_BLOCK - 1u) / CAND_BLOCK) * CAND_BLOCK * CAND_REC_WORDS))) return rc;
   }
-  const uint2* const mrec = c->handover ? c->d_mrec.get() : nullptr;
+  const uint2* const mrec = c->tune.handover ? c->d_mrec.get() : nullptr;
   const uint32_t wml = (std::min<uint32_t>(B.max_len, WK_MAX_ROWS) + 15) & ~15u;
-  const uint32_t RMX = c->walk_rounds, WK = c->walk_k;         // RMX: what d_wctr is laid out for; RM: the rounds of this launch
-  const uint32_t RM = (!c->walk_rounds_fixed && c->walk_need[pass]) ? std::min(RMX, c->walk_need[pass]) : RMX;
+  const uint32_t RMX = c->tune.walk_rounds, WK = c->tune.walk_k;         // RMX: what d_wctr is laid out for; RM: the rounds of this launch
+  const uint32_t RM = (!c->tune.walk_rounds_fixed && c->walk_need[pass]) ? std::min(RMX, c->walk_need[pass]) : RMX;
   if (split) {
     const size_t n = B.n;
     if (c->walk_cap < n || c->walk_kcap < WK) {
@@ -134,12 +135,12 @@ int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, const AlignPl
   const dim3 per_read((B.n + 255u) / 256u);
   ev_mark(c, KP_CAND);
   // the reads without any candidate reference end their pass in k_cand; k_chain walks the ones it marks
-  launch(c, k_cand, dim3((B.n + CAND_BLOCK - 1u) / CAND_BLOCK), dim3(256), CAND_LDS_BYTES(c->cand_bloom, c->handover), dreads(c), dindex(di), P, pass, is_last_strand, B.d_work, B.d_rw, c->d_pool, B.d_marks, c->cand_bloom,
-         c->handover ? c->d_mrec.get() : nullptr, c->d_mpool, c->d_mpool.cap());
+  launch(c, k_cand, dim3((B.n + CAND_BLOCK - 1u) / CAND_BLOCK), dim3(256), CAND_LDS_BYTES(c->cand_bloom, c->tune.handover), dreads(c), dindex(di), P, pass, is_last_strand, B.d_work, B.d_rw, c->d_pool, B.d_marks, c->cand_bloom,
+         c->tune.handover ? c->d_mrec.get() : nullptr, c->d_mpool, c->d_mpool.cap());
   if (split) {
     // rounds of walk -> Smith-Waterman -> next list (smr_walk.hpp); the last round scores in the walk kernel, so every listed read ends its pass here
     ev_mark(c, KP_WNEXT);
-    launch(c, k_wlist, dim3((B.n + 1023u) / 1024u), dim3(1024), 0, dreads(c), B.d_marks, mrec, (uint32_t)WK_MAX_ROWS, c->d_wlist[0], c->d_wslow, c->d_wctr, n_slow, getenv("SMR_WALK_DEBUG") ? n_slow + 8 : nullptr, (P.num_seeds >= 2 && c->walk_gather) ? 1 : 0);
+    launch(c, k_wlist, dim3((B.n + 1023u) / 1024u), dim3(1024), 0, dreads(c), B.d_marks, mrec, (uint32_t)WK_MAX_ROWS, c->d_wlist[0], c->d_wslow, c->d_wctr, n_slow, c->tune.walk_debug ? n_slow + 8 : nullptr, (P.num_seeds >= 2 && c->tune.walk_gather) ? 1 : 0);
     if (c->cinfo_on) launch(c, k_cand_route, per_read, dim3(256), 0, B.n, B.d_marks, mrec, c->d_wlist[0], c->d_wctr, 0, c->d_croute);
     const uint32_t walk_blocks = (uint32_t)c->n_cu * 4u * SMR_WALK_WAVES_PER_SIMD;
     for (uint32_t rnd = 0; rnd < RM; rnd++) {
@@ -149,7 +150,7 @@ int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, const AlignPl
       ev_mark(c, KP_WALK);
       launch(c, fin ? k_walk<true> : k_walk<false>, dim3(fin ? walk_blocks * 3u / SMR_WALK_WAVES_PER_SIMD : walk_blocks), dim3(64), fin ? (size_t)wml + rq : 0,
              dreads(c), dindex(di), P, pass, is_last_strand, B.d_work, B.d_work_aln, B.d_rw, B.d_ctr, mrec, c->d_mpool, c->d_pool, c->d_wlist[cur],
-             c->d_wstate[prv], c->d_wtask[prv], c->d_wres[prv], c->d_wstate[cur], c->d_wtask[cur], c->d_wtidx, c->d_wtidx + n_tix, wc, WK, n_tix, (int)rnd, wml, rq, c->walk_assume);
+             c->d_wstate[prv], c->d_wtask[prv], c->d_wres[prv], c->d_wstate[cur], c->d_wtask[cur], c->d_wtidx, c->d_wtidx + n_tix, wc, WK, n_tix, (int)rnd, wml, rq, c->tune.walk_assume);
       if (fin) continue;
       ev_mark(c, KP_SW16);
       launch_sw16(c, plan.rows, 0, 0, dreads(c), dindex(di), P, c->d_wtask[cur], c->d_wtidx, c->d_wtidx + n_tix, wc, c->d_wres[cur]);
@@ -157,11 +158,11 @@ int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, const AlignPl
       launch(c, k_wnext, dim3((uint32_t)c->n_cu * 2u), dim3(1024), 0, P, is_last_strand, B.d_work, B.d_rw, B.d_ctr, c->d_wlist[cur], c->d_wstate[cur],
              c->d_wres[cur], c->d_wlist[prv], wc, wc + WC_STRIDE, WK, n_tix, (int)rnd);
     }
-    if (!c->walk_rounds_fixed && c->wstat_n < 8) {         // the reads listed per round, kept for adapt_walk_rounds
+    if (!c->tune.walk_rounds_fixed && c->wstat_n < 8) {         // the reads listed per round, kept for adapt_walk_rounds
       launch(c, k_wstat, dim3(1), dim3(32), 0, c->d_wctr, c->d_wstat + (size_t)c->wstat_n * 32, RM);
       c->wstat_pass[c->wstat_n] = pass; c->wstat_rm[c->wstat_n] = RM; c->wstat_n++;
     }
-    if (getenv("SMR_WALK_DEBUG")) {                         // measurement aid: reads listed and tasks left per round, reads left to k_chain
+    if (c->tune.walk_debug) {                               // measurement aid: reads listed and tasks left per round, reads left to k_chain
       std::vector<unsigned long long> h((size_t)(RMX + 2) * WC_STRIDE);
       HIPCHK(c, hipMemcpyAsync(h.data(), c->d_wctr, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -202,7 +203,7 @@ int launch_begins(smr_ctx* c, const DevIndex& di, const DParams& P, const AlignP
   ev_mark(c, KP_BEGINS);
   launch(c, k_begins_collect, dim3((uint32_t)((ntot + 1023) / 1024)), dim3(1024), 0, B.n, B.slots, B.d_work, B.d_rw, B.d_work_aln, c->d_tasks, B.d_ctr);
   const size_t task_cap = (size_t)c->walk_cap * c->walk_kcap;
-  if (x4 && c->walk_split && c->d_wtask[0] && c->d_wctr && ntot <= task_cap && !getenv("SMR_BEGINS_X4")) {
+  if (plan.begins_sw16 && c->d_wtask[0] && c->d_wctr && ntot <= task_cap) {
     for (int stage = 0; stage < 2; stage++) {
       HIPCHK(c, hipMemsetAsync(c->d_wctr, 0, (size_t)WC_STRIDE * 8, c->stream));
       launch(c, k_begins_prep, dim3((uint32_t)c->n_cu * 2u), dim3(1024), 0, dindex(di), B.slots, c->d_tasks, &B.d_ctr[C_BEGIN_N], B.d_work_aln, stage, c->d_wtask[0], c->d_wtidx, c->d_wctr);

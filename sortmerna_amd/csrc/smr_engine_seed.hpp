@@ -26,11 +26,10 @@ int ensure_seed_bufs(smr_ctx* c, const DParams& P) {
       if ((rc = S.wseg[d].alloc(c, slots)) || (rc = S.fbits[d].alloc(c, slots / 32 + 2))) return rc;
     if ((rc = S.wbin.alloc(c, 2 * slots / 64 + 2)) || (rc = S.zbits.alloc(c, slots / 32 + 2)) || (rc = S.gflag.alloc(c, slots / 2048 + 2))) return rc;
     // skewed batches: a coarse bin of at least SEED_HOT_BIN_MIN tuples in sub-ranges of SEED_HOT_SUB (their fine histograms); the pieces of hot keys (>= 1024 tuples each)
-    c->sb.hbin_min = getenv("SMR_SEED_HOT_BIN") ? (uint32_t)std::max(1, atoi(getenv("SMR_SEED_HOT_BIN"))) : SEED_HOT_BIN_MIN;
-    c->sb.hsub = getenv("SMR_SEED_HOT_SUB") ? (uint32_t)std::max(1, atoi(getenv("SMR_SEED_HOT_SUB"))) : SEED_HOT_SUB;
+    c->sb.hbin_min = c->tune.hot_bin; c->sb.hsub = c->tune.hot_sub;
     c->sb.cap_hent = (uint32_t)(2 * slots / c->sb.hsub + 2 * slots / c->sb.hbin_min + 2);
     if ((rc = S.hh.alloc(c, (size_t)c->sb.cap_hent * 512))) return rc;
-    c->sb.cap_pieces = (uint32_t)std::min<uint64_t>(2 * slots / std::max(c->hot_min, 64u) + 2 * slots / SEED_DD_PIECE + 16, 1u << 26);
+    c->sb.cap_pieces = (uint32_t)std::min<uint64_t>(2 * slots / std::max(c->tune.hot_min, 64u) + 2 * slots / SEED_DD_PIECE + 16, 1u << 26);
     if ((rc = S.pieces.alloc(c, (size_t)c->sb.cap_pieces))) return rc;
     c->sb_slots = slots;
   }
@@ -38,7 +37,7 @@ int ensure_seed_bufs(smr_ctx* c, const DParams& P) {
   v.chist = S.chist; v.cbase = S.cbase; v.rows = S.rows; v.bcnt = S.bcnt; v.tmp = S.tmp; v.mid = S.mid; v.srt = S.srt; v.zbits = S.zbits; v.gflag = S.gflag; v.wbin = S.wbin;
   v.emap = S.emap; v.sn = S.sn; v.redo = S.redo; v.hpre = S.hpre; v.hlist = S.hlist; v.hh = S.hh; v.pieces = S.pieces;
   for (int d = 0; d < 2; d++) { v.wseg[d] = S.wseg[d]; v.fbits[d] = S.fbits[d]; }
-  c->sb.hot_min = c->hot_min;
+  c->sb.hot_min = c->tune.hot_min;
   c->sb.nk = nk; c->sb.nkh = nk / 2;
   c->sb.fb = std::min<uint32_t>(9, P.lnwin); c->sb.nc = nk >> c->sb.fb;       // L <= 20: at most 4096 coarse bins
   c->sb.cb = 2 * P.partialwin; c->sb.kbits = P.lnwin + 1;
@@ -132,16 +131,19 @@ SeedDirKernels seed_dir_kernels(int dir) {
   return {k_seed_pg<1>, k_seed_search<1>, k_seed_prop<1>};
 }
 
+// k_seed_pg: waves of the launch (a wave walks chunks it, it + grid, ...) and its XCD-aware chunk order (off) -- both settled by measurement
+constexpr uint32_t PG_GRID = 262144u;
+constexpr int PG_SWZ = 0;
 // the searches of one sorted array: forward (dir 0) or reverse launch, the overflow redo, the repeated seeds' windows
 int seed_search(smr_ctx* c, const DevIndex& di, const DParams& P, int pass, const SeedBufs& sb, int dir, uint32_t pool_words, size_t lds, size_t lds_pg) {
   const uint64_t slots = (uint64_t)sb.n * sb.maxwin;
   const uint32_t gw = std::max<uint32_t>(1u, (uint32_t)((2 * slots + 63) / 64));
   const uint32_t gr = std::min<uint32_t>(gw, SEED_REDO_CAP);
-  const uint32_t gp = c->pg_grid ? std::min<uint32_t>((gw + 7u) & ~7u, c->pg_grid) : ((gw + 7u) & ~7u);
+  const uint32_t gp = std::min<uint32_t>((gw + 7u) & ~7u, PG_GRID);
   const uint32_t gd = std::min<uint32_t>(sb.cap_pieces, (uint32_t)c->n_cu * 8u);
   HIPCHK(c, hipMemsetAsync(&sb.sn[SN_REDO], 0, 4, c->stream));
   const SeedDirKernels K = seed_dir_kernels(dir);
-  launch(c, K.pg, dim3(gp), dim3(64), lds_pg, dindex(di), P, pass, sb, c->ccap, c->d_pool, pool_words, c->b->d_ctr, c->pg_swz);
+  launch(c, K.pg, dim3(gp), dim3(64), lds_pg, dindex(di), P, pass, sb, c->ccap, c->d_pool, pool_words, c->b->d_ctr, PG_SWZ);
   launch(c, K.search, dim3(gr), dim3(64), lds, dindex(di), P, pass, sb, c->hcap, c->d_pool, pool_words, c->b->d_ctr, sb.redo);
   if (sb.hot_min) launch(c, K.prop, dim3(gd), dim3(256), 0, sb, c->b->d_ctr);
   return SMR_OK;
@@ -174,7 +176,7 @@ int ensure_shared_sort(smr_ctx* c, const DevIndex& di, const DParams& P) {
           for (int s2 = 0; s2 < 2; s2++) for (int p2 = 0; p2 < 3; p2++) { SharedSet& U = S.set[s2][p2]; U.srt.release(); U.wbin.release(); U.built = false; }
           for (int p2 = 0; p2 < 3; p2++) S.cap[p2] = 0;
           c->seed_shared = 0;
-          if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: no device memory for the shared seed sort: every index part sorts for itself\n");
+          say(c->tune, "no device memory for the shared seed sort: every index part sorts for itself\n");
           return SMR_OK;
         }
       }
@@ -197,7 +199,7 @@ int ensure_shared_sort(smr_ctx* c, const DevIndex& di, const DParams& P) {
   }
   S.usable = hot == 0 || c->seed_shared >= 2;
   c->n_seed_shared_builds++;
-  if (getenv("SMR_VERBOSE")) fprintf(stderr, "libsmr_hip: one seed sort for the parts of this batch: built (%u pieces of hot keys: %s)\n", hot, S.usable ? "in use" : "not used, every part sorts for itself");
+  say(c->tune, "one seed sort for the parts of this batch: built (%u pieces of hot keys: %s)\n", hot, S.usable ? "in use" : "not used, every part sorts for itself");
   return SMR_OK;
 }
 
@@ -213,11 +215,10 @@ int launch_seed(smr_ctx* c, const DevIndex& di, const DParams& P, int pass, bool
   sb.n = c->b->n;
   sb.cap_redo = SEED_REDO_CAP;
   sb.abits = nullptr; sb.inv_maxwin = 1.0 / (double)sb.maxwin;
-  sb.seg_inline = (c->pool_words <= (1ull << 30) && (uint64_t)di.n_ids + di.n_pos < (1ull << 30) && !(getenv("SMR_SEG_INLINE") && atoi(getenv("SMR_SEG_INLINE")) == 0)) ? 1u : 0u;
+  sb.seg_inline = (c->pool_words <= (1ull << 30) && (uint64_t)di.n_ids + di.n_pos < (1ull << 30) && c->tune.seg_inline) ? 1u : 0u;
   c->pool_inline = sb.seg_inline;
   if (c->seed_exact) sb.hot_min = 0;                         // the exact work counters count every window's search
-  const size_t lds = (size_t)SEED_LDS_WORDS(c->hcap) * 4, lds_pg1 = (size_t)PG_LDS_WORDS(c->ccap) * 4;
-  const size_t lds_pg = lds_pg1 + (getenv("SMR_PG_LDS_PAD") ? (size_t)atoi(getenv("SMR_PG_LDS_PAD")) : 0);      // (the variable: occupancy experiments)
+  const size_t lds = (size_t)SEED_LDS_WORDS(c->hcap) * 4, lds_pg = (size_t)PG_LDS_WORDS(c->ccap) * 4;
   // lists of more than 128 hits per search (a crafted neighbourhood: SEED_HCAP_MAX) take more than the default 64 KB of dynamic LDS
   if ((rc = raise_lds_limit(c, c->pg_lds_attr, lds_pg, 64 * 1024, seed_dir_kernels(0).pg, seed_dir_kernels(1).pg))) return rc;
   if ((rc = raise_lds_limit(c, c->search_lds_attr, lds, 64 * 1024, seed_dir_kernels(0).search, seed_dir_kernels(1).search))) return rc;
@@ -257,7 +258,7 @@ int launch_seed(smr_ctx* c, const DevIndex& di, const DParams& P, int pass, bool
     if (shared && (rc = seed_search(c, di, P, pass, sh, dir, pool_words, lds, lds_pg))) return rc;
     if (own && (rc = seed_search(c, di, P, pass, sb, dir, pool_words, lds, lds_pg))) return rc;
   }
-  if (getenv("SMR_SEED_DEBUG")) {                            // (debug aid: synchronises)
+  if (c->tune.seed_debug) {                                  // (debug aid: synchronises)
     uint32_t sn[SN_COUNT], hent = 0, sn2[SN_COUNT] = {0};
     HIPCHK(c, hipMemcpyAsync(sn, sb.sn, sizeof sn, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&hent, sb.hpre + sb.nc, 4, hipMemcpyDeviceToHost, c->stream));

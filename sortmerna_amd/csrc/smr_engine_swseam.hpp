@@ -207,7 +207,7 @@ extern "C" int smr_ssw_batch(smr_ctx* c, uint32_t n_pairs, const uint8_t* reads,
   if (mode == 3) {          // four pairs per wave (the kernel k_chain batches candidate windows with): spans up to SW_X4_MAX_ROWS, numbers within the packed range
     for (uint32_t i = 0; i < n_pairs; i++) {
       const uint64_t m = read_off[i + 1] - read_off[i], n = ref_off[i + 1] - ref_off[i];
-      if (m > SW_X4_MAX_ROWS || !((long long)m * match + 255 < 32768 && n + 128 <= 8191 && gap_open + mismatch >= 0 && gap_open + score_N >= 0 && match + gap_open <= 255 && score_N + gap_open <= 255)) {
+      if (m > SW_X4_MAX_ROWS || !sw_pk_fits((int)m, (int)n, match, mismatch, score_N, gap_open)) {
         set_err(c, "smr_ssw_batch mode 3: a pair is outside the range of the four-problem kernel"); return SMR_ERR_ARG;
       }
     }
@@ -354,6 +354,6 @@ extern "C" int smr_sw_mode(smr_ctx* c, int set_to) {      // set_to: 0 / 1 = sel
 // rounds the candidate walk of the next part runs per pass (smr_walk.hpp; adapts to what the previous part needed unless SMR_WALK_ROUNDS fixes it)
 extern "C" int smr_walk_rounds(const smr_ctx* c, uint32_t out[3]) {
   if (!c || !out) return SMR_ERR_ARG;
-  for (int p = 0; p < 3; p++) out[p] = (!c->walk_rounds_fixed && c->walk_need[p]) ? std::min(c->walk_rounds, c->walk_need[p]) : c->walk_rounds;
+  for (int p = 0; p < 3; p++) out[p] = (!c->tune.walk_rounds_fixed && c->walk_need[p]) ? std::min(c->tune.walk_rounds, c->walk_need[p]) : c->tune.walk_rounds;
   return SMR_OK;
 }

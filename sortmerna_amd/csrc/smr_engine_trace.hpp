@@ -80,8 +80,7 @@ static int traceback_core(smr_ctx* c, const DevIndex& di, const smr_params* p) {
   const uint64_t ntot = (uint64_t)c->b->n * c->b->slots;
   if ((rc = c->d_tasks.reserve(c, 2 * ntot))) return rc;     // two lists: in / handed on
   if (c->b->cigar_words == 0) {
-    c->b->cigar_words = std::max<uint64_t>(ntot * 16, 1u << 20);
-    if (const char* e = getenv("SMR_CIGAR_POOL_WORDS")) c->b->cigar_words = std::max<uint64_t>(strtoull(e, nullptr, 10), 16);   // debugging aid: start small, exercise the regrow
+    c->b->cigar_words = c->tune.cigar_words ? c->tune.cigar_words : std::max<uint64_t>(ntot * 16, 1u << 20);   // (the switch: start small, exercise the regrow)
     if ((rc = c->b->d_cigar.alloc(c, c->b->cigar_words))) return rc;
   }
   uint32_t ml, rf; size_t chain_bytes;
@@ -145,17 +144,17 @@ static int traceback_core(smr_ctx* c, const DevIndex& di, const smr_params* p) {
       if (level > 0 && level_band[level - 1] >= max_band) break;
       const uint32_t band = std::min(level_band[level], max_band);
       const uint32_t wcap = (2 * band + 1 + 63) & ~63u;
-      const bool rows_lds = (size_t)wcap * 8 + TR_CIG_STAGE * 4 <= 64 * 1024 && !getenv("SMR_TRACE_GLOBAL_ROWS");     // (the variable: debugging aid, forces the wide-band variant)
+      const bool rows_lds = (size_t)wcap * 8 + TR_CIG_STAGE * 4 <= 64 * 1024 && !c->tune.trace_global_rows;     // (the switch: debugging aid, forces the wide-band variant)
       const uint64_t flags_cap = (uint64_t)std::max(c->b->max_len, 1u) * (wcap / 2);
       const uint64_t per_block = flags_cap + (rows_lds ? 0 : (uint64_t)wcap * 8);
       // (measured on 5 kb reads, k_trace per 50 000-read step: 8 blocks per CU 762 ms; 16: 496; 32: 459: the kernel lives on waves in flight, profiles/r4s10_*)
-      static const int tw_bpc = getenv("SMR_TRACE_BPC") ? atoi(getenv("SMR_TRACE_BPC")) : 32;
+      constexpr uint32_t TRACE_WIDE_BLOCKS_PER_CU = 32;
       // (the tiles take at most 16 GiB and at most a quarter of what is free on the device now: with many resident batches and index parts, or on a
       // smaller device, fewer blocks run instead of the allocation failing)
       size_t mem_free = 0, mem_total = 0;
       if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) mem_free = (size_t)16 << 30;
       const uint64_t budget = std::min<uint64_t>(16ull << 30, std::max<uint64_t>(c->d_trflags.cap(), (uint64_t)mem_free / 4));
-      uint32_t blocks = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(budget / per_block, 1), (uint64_t)c->n_cu * tw_bpc);
+      uint32_t blocks = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(budget / per_block, 1), (uint64_t)c->n_cu * TRACE_WIDE_BLOCKS_PER_CU);
       blocks = std::min(blocks, n_tasks);
       const size_t lds_tw = (size_t)TR_CIG_STAGE * 4 + (rows_lds ? (size_t)wcap * 8 : 0);
       if ((rc = c->d_trflags.reserve(c, (size_t)blocks * flags_cap))) return rc;

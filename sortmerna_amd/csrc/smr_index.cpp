@@ -31,14 +31,13 @@
 #include "smr_host.hpp"
 #include "smr_trie_layout.hpp"
 #include "smr_hostmem.hpp"
+#include "smr_tuning.hpp"
 
 using namespace smr;
 
 namespace smr {
 uint32_t host_threads() {
-  uint32_t t = std::max(1u, std::thread::hardware_concurrency());
-  if (const char* e = getenv("SMR_HOST_THREADS")) t = std::min<uint32_t>(t, (uint32_t)std::max(1, atoi(e)));
-  return t;
+  return tuning_host_threads(std::max(1u, std::thread::hardware_concurrency()));
 }
 }  // namespace smr
 
@@ -144,7 +143,7 @@ bool load_stats(const std::string& prefix, Stats& st) {
 }
 
 struct StageTimer {
-  bool on = getenv("SMR_IB_TIMING") != nullptr;
+  bool on = tuning_ib_timing();
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
   void lap(const char* what) {
     if (!on) return;
@@ -323,8 +322,7 @@ extern "C" int smr_index_load_files(const char* prefix, uint32_t part, const cha
       !pb.open(std::string(prefix) + ".pos_" + p + ".dat")) {
     delete ix; set_err(err, errcap, "cannot read index part files"); return SMR_ERR_IO;
   }
-  uint32_t threads = std::min<uint32_t>(64, smr::host_threads());
-  if (const char* e = getenv("SMR_LOAD_THREADS")) threads = std::min<uint32_t>(256, std::max(1, atoi(e)));      // test aid: many loader threads on a small machine
+  const uint32_t threads = tuning_load_threads(std::min<uint32_t>(64, smr::host_threads()));
   // the reference sequences and the position lists load in threads of their own while the tries are parsed
   bool refs_ok = false;
   // (an exception inside a std::thread would end the process: the bodies catch and report -- a damaged file must come back as SMR_ERR_IO)

@@ -564,6 +564,12 @@ class Engine:
         self._chk(self.L.smr_seed_tuples_fetch(self.h, tup.ctypes.data, len(tup), cbase.ctypes.data, len(cbase), meta), "smr_seed_tuples_fetch")
         return tup[: meta[0]], cbase, dict(n=meta[0], n_fwd=meta[1], nc=meta[2], fb=meta[3], cb=meta[4], nkh=meta[5], ccap=meta[6], redo=meta[7])
 
+    def tuning(self):
+        """dict(NAME -> int) of the library's environment switches as this engine latched them when it was created (smr_tuning_text)"""
+        buf = C.create_string_buffer(max(self.L.smr_tuning_text(self.h, None, 0), 1))
+        self.L.smr_tuning_text(self.h, buf, len(buf))
+        return {k: int(v) for k, v in (line.split("=") for line in buf.value.decode().splitlines())}
+
     def seed_pool_info(self):
         """dict(words, grown, hi, inline) of the seed-hit pool (smr_seed_pool_info: a test seam): its size in words, its regrows since the engine
         was created, one past the highest word the last seed stage handed out, whether that stage inlined one-hit windows"""

@@ -47,19 +47,27 @@ def check(engine, kinds=None, max_pairs=None, schemes=None):
     return n
 
 
-def check_variants(engine):
+def check_variants():
     """the same vectors through the code paths that ordinary inputs do not reach: DP rows of the wide kernel in global memory (bands too
-    wide for LDS) and a CIGAR pool that has to be regrown several times"""
-    import os
+    wide for LDS) and a CIGAR pool that has to be regrown several times.  A context reads its switches when it is created: one context per
+    variant, made after the variant's variables are set and closed before the next"""
+    import sortmerna_amd as smr
+    variants = [({"SMR_TRACE_GLOBAL_ROWS": "1"}, [dict(kinds=["indels"], max_pairs=40), dict(kinds=["long"], max_pairs=2, schemes=[0, 2])]),
+                ({"SMR_CIGAR_POOL_WORDS": "64"}, [dict(kinds=["short", "indels"], max_pairs=60, schemes=[0])])]
+    names = [k for env, _ in variants for k in env]
     n = 0
     try:
-        os.environ["SMR_TRACE_GLOBAL_ROWS"] = "1"
-        n += check(engine, kinds=["indels"], max_pairs=40)
-        n += check(engine, kinds=["long"], max_pairs=2, schemes=[0, 2])
-        del os.environ["SMR_TRACE_GLOBAL_ROWS"]
-        os.environ["SMR_CIGAR_POOL_WORDS"] = "64"
-        n += check(engine, kinds=["short", "indels"], max_pairs=60, schemes=[0])
+        for env, runs in variants:
+            for k in names:
+                os.environ.pop(k, None)
+            os.environ.update(env)
+            engine = smr.Engine(0)
+            try:
+                for kw in runs:
+                    n += check(engine, **kw)
+            finally:
+                engine.close()
     finally:
-        os.environ.pop("SMR_TRACE_GLOBAL_ROWS", None)
-        os.environ.pop("SMR_CIGAR_POOL_WORDS", None)
+        for k in names:
+            os.environ.pop(k, None)
     return n

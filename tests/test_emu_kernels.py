@@ -234,7 +234,7 @@ def test_traceback_kernels_equal_the_reference_banded_sw(emulator):
     n = tracegold.check(e, kinds=["short", "tiny", "indels"])
     n += tracegold.check(e, kinds=["long"], max_pairs=3)
     assert n > 1700
-    assert tracegold.check_variants(e) > 150
+    assert tracegold.check_variants() > 150
     e.close()
 
 

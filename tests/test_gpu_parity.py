@@ -525,6 +525,35 @@ def seg_inline_off_body(wl, monkeypatch, mode):
         e.close()
 
 
+def test_a_context_keeps_the_switches_it_was_created_with(wl, monkeypatch):
+    """A context reads its environment switches when it is created (csrc/smr_tuning.hpp) and never again: (a) SMR_SEG_INLINE=0 at creation and
+    deleted before the first launch still means no inlining; (b) unset at creation and set to 0 before the first launch still means inlining.
+    Both give the oracle's records and counters.  One context after the other."""
+    recs_o, ctr_o = wl.oracle_records()
+
+    def put(v):
+        if v is None:
+            monkeypatch.delenv("SMR_SEG_INLINE", raising=False)
+        else:
+            monkeypatch.setenv("SMR_SEG_INLINE", v)
+
+    for at_creation, later, inline in (("0", None, False), (None, "0", True)):
+        what = "SMR_SEG_INLINE %s at creation, %s afterwards" % (at_creation, later)
+        put(at_creation)
+        e = smr.Engine(0)
+        try:
+            put(later)
+            assert e.tuning()["SMR_SEG_INLINE"] == int(inline), what
+            if not inline:
+                assert not e.seed_pool_info()["inline"], what        # before any launch
+            recs_g, ctr_g = wl.gpu_records(e)
+            assert e.seed_pool_info()["inline"] == inline, what
+            _compare(recs_g, recs_o, what)
+            _counters_equal(ctr_g, ctr_o, what)
+        finally:
+            e.close()
+
+
 def pool_above_2_30_body(wl, monkeypatch, mode, words):
     """A seed-hit pool of `words` > 2^30 words: the host turns inlining off and the upper shards hand out offsets with bit 30 set, which the
     readers (k_seed_search<1>'s forward list, k_seed_finish's merge and upper bound) must not take for inlined ids.  The seed stage alone

@@ -34,7 +34,7 @@ def test_traceback_kernels_equal_the_reference_banded_sw(engine):
     gapless / single-indel short reads, multi-indel reads, windows narrower than their band, 0.7-3 kb noisy reads with long gaps, four scoring schemes"""
     from helpers import tracegold
     assert tracegold.check(engine) > 1800
-    assert tracegold.check_variants(engine) > 150
+    assert tracegold.check_variants() > 150
 
 
 def test_packed_smith_waterman_selfcheck_on_the_device(engine):
