@@ -309,6 +309,39 @@ int smr_fastx_split(smr_ctx*, int mates /* batch number, layout 2 only; else -1 
                     const uint8_t* hit /* NULL: the batches' own is_hit */, uint8_t* bytes, uint64_t cap, uint64_t off[9], uint64_t* need);
 /* HIP-event milliseconds of the last smr_fastx_split: {measure and route, scans, copy, bytes D2H} (the last two 0 for a sizes-only call) */
 int smr_fastx_split_times(const smr_ctx*, double ms[4]);
+/* The rows of aligned.sam and of the BLAST tabular report (-blast '1 ...') of the selected batch for ONE (index, part), written on the device
+ * (csrc/smr_rows.hpp) from the text that SMR_FASTX_KEEP left there, the packed letters, the stored alignments with their CIGARs and the part's
+ * reference letters: what smr_results_fetch + smr_reads_record_text + smr_result_record + smr_report_add append to the report's rows of that
+ * (index, part) one read at a time ("Writing SAM and BLAST rows from the device").  Call order as smr_idcov_part: after
+ * smr_align_part + smr_traceback of every (index, part) of the run, once per (index, part) with that part resident in `slot`; `ix` is the host
+ * object of that part (its sq_header gives the reference ids; they are uploaded the first time the call sees the slot and go with the slot).
+ * Two streams: the SAM rows are bytes[off[0], off[1]), the BLAST rows bytes[off[1], off[2]), off[0] = 0, off[2] = *need; a stream that is not
+ * wanted is empty.  Each holds exactly the bytes the host writer appends for the reads of the batch in order: rows in read order, within a read
+ * in alignment-slot order, alignments of other (index, part) keys skipped; no SAM header lines.  That includes the writer's quirk with QUAL (one
+ * copy of the quality per key, reversed in place at every reverse-strand alignment of the key) and `%.3g` of %id and qcov, whose digits are
+ * found in exact integer arithmetic on the double.  BLAST pairwise (-blast 0) stays with the host writer.
+ *   bytes  NULL: sizes only.  cap < *need: SMR_ERR_CAPACITY, off and *need valid, bytes untouched.  Otherwise exactly *need bytes are written
+ *          and nothing behind them is touched.  May be pinned memory.
+ * SMR_ERR_STATE: a batch without kept text (the message names SMR_FASTX_KEEP); an alignment of the part without a CIGAR (smr_traceback first).
+ * SMR_ERR_ARG: neither stream wanted; an unknown word in blast_cols; `ix` is not the part in `slot`; and -- checked on the device before any
+ * byte is written, imported state can hold them and the host writer would read out of bounds -- a CIGAR without columns, a CIGAR that runs
+ * past its read or its reference sequence, ref_num >= the part's references.  Every refusal leaves a message, writes nothing and leaves the
+ * context usable.  Runs on the engine's stream; needs no smr_results_fetch and leaves the host copy alone; changes no stored state (it does not
+ * mark alignments as smr_idcov_part does); may be repeated and gives the same bytes.  Device memory, kept for the next call: 16 bytes per
+ * alignment slot, 32 per read, the output. */
+typedef struct {
+  int  want_sam, want_blast;       /* BLAST tabular only */
+  char blast_cols[64];             /* as smr_report_opts.blast_cols: "cigar", "qcov", "qstrand", space separated, in output order */
+  double lambda, K;                /* as smr_report_set_db: e-value and bit score of the BLAST row */
+  uint64_t full_ref_corr, full_read_corr;
+} smr_rows_opts;
+int smr_rows_part(smr_ctx*, int slot, const smr_params*, const smr_index* ix, const smr_rows_opts*,
+                  uint8_t* bytes, uint64_t cap, uint64_t off[3], uint64_t* need);
+/* HIP-event milliseconds of the last smr_rows_part: {alignment statistics, sizes and scans, write, bytes D2H} (the last two 0 for a sizes-only call) */
+int smr_rows_times(const smr_ctx*, double ms[4]);
+/* Test seam of the device's number formatter: out[16 i ..] = the text of `stream << (double)num[i] / (double)den[i] * 100` at precision 3
+ * (`%.3g`), NUL padded, for n pairs with den > 0 (SMR_ERR_ARG otherwise). */
+int smr_rows_fmt_batch(smr_ctx*, uint32_t n, const uint32_t* num, const uint32_t* den, char* out);
 /* Forget all per-read results/counters of the resident batch (reads stay resident). */
 int smr_state_reset(smr_ctx*);
 
@@ -534,6 +567,13 @@ int smr_report_add_pair(smr_report*, const char* header1, const char* seq1, cons
 /* The streams of smr_fastx_split: stream k is appended to the open aligned.* (k < 4) / other.* (k - 4) file of that index, through gzip under
  * zip_out.  SMR_ERR_ARG, and nothing is written, when a stream that is not empty has no open file. */
 int smr_report_add_fastx(smr_report*, const uint8_t* bytes, const uint64_t off[9]);
+/* The streams of smr_rows_part for (index_num, part): appended to the report's SAM / BLAST rows of that key, so that smr_report_close writes the
+ * files as ever.  SMR_ERR_ARG, and nothing is appended, when a stream that is not empty belongs to a report not opened for it (sam /
+ * blast_tabular), when the offsets decrease, or when the (index, part) was not registered with smr_report_set_part. */
+int smr_report_add_rows(smr_report*, uint32_t index_num, uint32_t part, const uint8_t* bytes, const uint64_t off[3]);
+/* on != 0: smr_report_add / smr_report_add_pair leave the SAM and BLAST tabular rows alone (smr_report_add_rows brings them); FASTX, the OTU
+ * map, aligned_denovo.* and BLAST pairwise are unaffected */
+int smr_report_skip_rows(smr_report*, int on);
 /* on != 0: smr_report_add / smr_report_add_pair leave aligned.* / other.* alone (smr_report_add_fastx writes them); BLAST, SAM, the OTU map and
  * aligned_denovo.* are unaffected */
 int smr_report_skip_fastx(smr_report*, int on);

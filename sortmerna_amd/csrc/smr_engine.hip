@@ -17,10 +17,12 @@
 #include "smr_export.hpp"
 #include "smr_fastx.hpp"
 #include "smr_fxsplit.hpp"
+#include "smr_rows.hpp"
 #include "smr_ibuild.hpp"
 #include "smr_pgbuild.hpp"
 #include "smr_hostmem.hpp"
 #include "smr_devbuf.hpp"
+#include "smr_score_text.hpp"
 #include "smr_tuning.hpp"
 
 using namespace smr;
@@ -35,6 +37,8 @@ struct DevIndex {
   uint32_t n_refs = 0, n_ids = 0, lnwin = 0;
   uint32_t ref_any_n = 1;     // does any reference hold an ambiguous letter (0 only when the upload looked and found none)
   uint64_t trie_words = 0, n_pos = 0, ref_bytes = 0, pg_words = 0;
+  // smr_rows_part: the names of the part's references as one text + offsets, uploaded by the first call that sees the slot (rows_part: for which part number)
+  DevBuf<uint8_t> rows_names; DevBuf<uint32_t> rows_name_off; int64_t rows_part = -1;
 };
 
 struct EvMark { hipEvent_t e; int kind; };        // kind < 0: end of a run of intervals
@@ -124,6 +128,18 @@ struct FxSplitScratch {
   ~FxSplitScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
+// scratch and staging of smr_rows_part (smr_rows.hpp), grow-only; the e-value / bit-score table with the database it was made for
+struct RowsScratch {
+  DevBuf<uint4> stat, meta; DevBuf<unsigned long long> excl_s, excl_b, part_s, part_b; DevBuf<uint32_t> err; DevBuf<uint8_t> tab, out;
+  uint32_t tab_n = 0; double tab_lambda = 0, tab_K = 0; uint64_t tab_ref = 0, tab_read = 0;
+  hipEvent_t ev[7] = {};
+  double ms[4] = {0, 0, 0, 0};            // of the last call: stats, sizes and scans, write, D2H
+  RowsScratch() = default;
+  RowsScratch(const RowsScratch&) = delete;
+  RowsScratch& operator=(const RowsScratch&) = delete;
+  ~RowsScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
 struct smr_ctx {
   const Tuning tune;                      // the environment switches as smr_create found them (smr_tuning.hpp)
   explicit smr_ctx(const Tuning& t) : tune(t) {}
@@ -195,6 +211,7 @@ struct smr_ctx {
   FxScratch fx[2];
   uint64_t fx_info[4] = {0, 0, 0, 0}; double fx_ms[5] = {0, 0, 0, 0, 0};
   FxSplitScratch fxs;
+  RowsScratch rows;
 };
 struct KpSave { double ms[KP_COUNT]; uint64_t l[KP_COUNT]; };
 
@@ -833,6 +850,7 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
 #include "smr_engine_export.hpp"
 #include "smr_engine_fastx.hpp"
 #include "smr_engine_fxsplit.hpp"
+#include "smr_engine_rows.hpp"
 extern "C" int smr_counters(smr_ctx* c, uint64_t* out, uint32_t n_db) {
   if (!c || !out) return SMR_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));

@@ -25,6 +25,7 @@
 #include <zlib.h>
 
 #include "smr_host.hpp"
+#include "smr_score_text.hpp"
 
 namespace {
 // one report file, plain or gzip (the reference deflates its reports when the reads file is gzip, or with -zip-out; the names get ".gz")
@@ -97,6 +98,7 @@ struct smr_report {
   std::map<std::pair<uint32_t, uint32_t>, std::string> blast, sam;     // rows per (index, part)
   std::string err, cmdline = "libsmr_hip";
   bool skip_fx = false;                                                // smr_report_skip_fastx: aligned.* / other.* come from smr_report_add_fastx
+  bool skip_rows = false;                                              // smr_report_skip_rows: the SAM and BLAST tabular rows come from smr_report_add_rows
 };
 
 extern "C" int smr_report_open(const char* out_dir, const smr_report_opts* opts, int is_fastq, smr_report** out, char* err, size_t errcap) {
@@ -235,6 +237,24 @@ extern "C" int smr_report_add_fastx(smr_report* r, const uint8_t* bytes, const u
   }
   return SMR_OK;
 }
+extern "C" int smr_report_add_rows(smr_report* r, uint32_t index_num, uint32_t part, const uint8_t* bytes, const uint64_t off[3]) {
+  if (!r || !off) return SMR_ERR_ARG;
+  if (off[1] < off[0] || off[2] < off[1]) { r->err = "smr_report_add_rows: the offsets decrease"; return SMR_ERR_ARG; }
+  const std::pair<uint32_t, uint32_t> key{index_num, part};
+  if (r->parts.find(key) == r->parts.end()) { r->err = "smr_report_add_rows: the (index, part) was not registered"; return SMR_ERR_ARG; }
+  const bool has_sam = off[1] > off[0], has_blast = off[2] > off[1];
+  if ((has_sam || has_blast) && !bytes) { r->err = "smr_report_add_rows: rows without bytes"; return SMR_ERR_ARG; }
+  if (has_sam && !r->o.sam) { r->err = "smr_report_add_rows: SAM rows for a report that was not opened with sam"; return SMR_ERR_ARG; }
+  if (has_blast && !r->o.blast_tabular) { r->err = "smr_report_add_rows: BLAST rows for a report that was not opened with blast_tabular"; return SMR_ERR_ARG; }
+  if (has_sam) r->sam[key].append(reinterpret_cast<const char*>(bytes) + off[0], (size_t)(off[1] - off[0]));
+  if (has_blast) r->blast[key].append(reinterpret_cast<const char*>(bytes) + off[1], (size_t)(off[2] - off[1]));
+  return SMR_OK;
+}
+extern "C" int smr_report_skip_rows(smr_report* r, int on) {
+  if (!r) return SMR_ERR_ARG;
+  r->skip_rows = on != 0;
+  return SMR_OK;
+}
 extern "C" int smr_report_skip_fastx(smr_report* r, int on) {
   if (!r) return SMR_ERR_ARG;
   r->skip_fx = on != 0;
@@ -289,7 +309,9 @@ int add_otu(smr_report* r, const char* header, const char* seq, const std::vecto
 }
 
 int add_rows(smr_report* r, const char* header, const char* seq, const char* qual, const std::vector<Aln>& alns) {
-  if (alns.empty() || (!r->o.blast_tabular && !r->o.blast_pairwise && !r->o.sam)) return SMR_OK;
+  // (smr_report_skip_rows: SAM and BLAST tabular are written elsewhere; BLAST pairwise stays here)
+  const bool do_tab = r->o.blast_tabular && !r->skip_rows, do_sam = r->o.sam && !r->skip_rows, do_pair = r->o.blast_pairwise && !r->o.blast_tabular;
+  if (alns.empty() || (!do_tab && !do_pair && !do_sam)) return SMR_OK;
   // Read::getSeqId (read.cpp:371-377)
   std::string id(header);
   id = id.substr(0, id.find(' '));
@@ -327,12 +349,12 @@ int add_rows(smr_report* r, const char* header, const char* seq, const char* qua
     }
     const double idf = (double)n_match / (double)(n_miss + n_gap + n_match);
     const double cov = (double)std::abs(a.read_end1 - a.read_begin1 + 1) / (double)a.readlen;
-    if (r->o.blast_pairwise && !r->o.blast_tabular) {
+    if (do_pair) {
       // The alignment as rows of at most 60 columns: reference letters ('-' where the read has an insertion), match marks,
       // read letters ('-' where the read has a deletion); the numbers are the 1-based first / last position of the row.
       const Db& d = dit->second;
-      const uint32_t bitscore = (uint32_t)((float)(d.lambda * a.score1 - std::log(d.K)) / (float)std::log(2));
-      const double evalue = (double)d.K * d.full_ref * d.full_read * std::exp(-d.lambda * a.score1);
+      std::string evalue, bitscore;
+      smr::score_texts(d.lambda, d.K, d.full_ref, d.full_read, a.score1, evalue, bitscore);
       std::ostringstream ss;
       ss << "Sequence ID: " << ref_id << "\n" << "Query ID: " << id << "\n";
       ss << "Score: " << a.score1 << " bits (" << bitscore << ")\t";
@@ -360,10 +382,10 @@ int add_rows(smr_report* r, const char* header, const char* seq, const char* qua
       }
       r->blast[key] += ss.str();
     }
-    if (r->o.blast_tabular) {
+    if (do_tab) {
       const Db& d = dit->second;
-      const uint32_t bitscore = (uint32_t)((float)(d.lambda * a.score1 - std::log(d.K)) / (float)std::log(2));
-      const double evalue = (double)d.K * d.full_ref * d.full_read * std::exp(-d.lambda * a.score1);
+      std::string evalue, bitscore;
+      smr::score_texts(d.lambda, d.K, d.full_ref, d.full_read, a.score1, evalue, bitscore);
       std::ostringstream ss;
       ss << id << "\t" << ref_id << "\t";
       ss.precision(3);
@@ -380,7 +402,7 @@ int add_rows(smr_report* r, const char* header, const char* seq, const char* qua
       ss << "\n";
       r->blast[key] += ss.str();
     }
-    if (r->o.sam) {
+    if (do_sam) {
       std::ostringstream ss;
       ss << id << (a.strand ? "\t0\t" : "\t16\t") << ref_id << "\t" << a.ref_begin1 + 1 << "\t255\t" << cigar_text(a, len) << "\t*\t0\t0\t";
       for (size_t i = 0; i < len; i++) ss << nt_map[(int)iseq[i]];

@@ -418,6 +418,37 @@ class Engine:
         self._chk(self.L.smr_fastx_split_times(self.h, ms), "smr_fastx_split_times")
         return dict(zip(("measure", "scans", "copy", "d2h"), (float(x) for x in ms)))
 
+    def rows_part(self, slot, params, index, sam=True, blast=False, cols="", lam=0.0, K=0.0, full_ref=0, full_read=0):
+        """smr_rows_part: the rows of aligned.sam and of the BLAST tabular report of the selected batch (uploaded with keep=True) for the
+        (index, part) of `params`, resident in `slot`, written on the device -> (sam_bytes, blast_bytes).  cols: "cigar", "qcov", "qstrand",
+        space separated or as a list, in output order; lam, K, full_ref, full_read: what Report.set_db takes for that index."""
+        o = capi.RowsOpts()
+        o.want_sam, o.want_blast = int(bool(sam)), int(bool(blast))
+        o.blast_cols = (cols if isinstance(cols, str) else " ".join(cols)).encode()
+        o.lam, o.K, o.full_ref_corr, o.full_read_corr = float(lam), float(K), int(full_ref), int(full_read)
+        off = (C.c_uint64 * 3)()
+        need = C.c_uint64(0)
+        self._chk(self.L.smr_rows_part(self.h, slot, C.byref(params), index.h, C.byref(o), None, 0, off, C.byref(need)), "smr_rows_part")
+        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
+        if need.value:
+            self._chk(self.L.smr_rows_part(self.h, slot, C.byref(params), index.h, C.byref(o), buf.ctypes.data, need.value, off, C.byref(need)), "smr_rows_part")
+        raw = buf.tobytes()
+        return raw[off[0]:off[1]], raw[off[1]:off[2]]
+
+    def rows_times(self):
+        """HIP-event ms of the last rows_part: dict(stats, sizes, write, d2h)"""
+        ms = (C.c_double * 4)()
+        self._chk(self.L.smr_rows_times(self.h, ms), "smr_rows_times")
+        return dict(zip(("stats", "sizes", "write", "d2h"), (float(x) for x in ms)))
+
+    def rows_fmt_batch(self, num, den):
+        """smr_rows_fmt_batch (a test seam): the device's `%.3g` of 100 * num[i] / den[i] -> list of str"""
+        num = np.ascontiguousarray(num, dtype=np.uint32)
+        den = np.ascontiguousarray(den, dtype=np.uint32)
+        out = np.zeros((len(num), 16), dtype=np.uint8)
+        self._chk(self.L.smr_rows_fmt_batch(self.h, len(num), num.ctypes.data, den.ctypes.data, out.ctypes.data), "smr_rows_fmt_batch")
+        return [bytes(r).rstrip(b"\0").decode() for r in out] if len(num) < 4096 else out.view("S16").ravel().astype(str).tolist()
+
     def reset_state(self):
         self._chk(self.L.smr_state_reset(self.h), "smr_state_reset")
 

@@ -74,6 +74,16 @@ class Report:
         """add / add_pair leave aligned.* / other.* alone: add_fastx writes them (smr_report_skip_fastx)"""
         self._chk(self.L.smr_report_skip_fastx(self.h, int(bool(on))), "smr_report_skip_fastx")
 
+    def add_rows(self, index_num, part, sam, blast):
+        """the two streams of Engine.rows_part appended to the report's SAM / BLAST rows of (index_num, part) (smr_report_add_rows)"""
+        off = (C.c_uint64 * 3)(0, len(sam), len(sam) + len(blast))
+        blob = bytes(sam) + bytes(blast)
+        self._chk(self.L.smr_report_add_rows(self.h, index_num, part, blob if blob else None, off), "smr_report_add_rows")
+
+    def skip_rows(self, on=True):
+        """add / add_pair leave SAM and BLAST tabular alone: add_rows brings them (smr_report_skip_rows)"""
+        self._chk(self.L.smr_report_skip_rows(self.h, int(bool(on))), "smr_report_skip_rows")
+
     def merge_otu_from(self, other):
         """the OTU map entries of `other` (the next shard of the reads, in input order) behind this report's; `other` then writes no map"""
         self._chk(self.L.smr_report_otu_merge(self.h, other.h), "smr_report_otu_merge")
