@@ -322,6 +322,8 @@ hipError_t hipFree(void* p) {
   abort();
 }
 // device allocations that have not been freed (the guard table: 0 throughout with SMR_EMU_GUARD=0): what a test of the engine's ownership counts
+// what hipGetDeviceProperties reports as multiProcessorCount (a test sizes its batches so that every kernel's grid loops)
+extern "C" int emu_multiprocessor_count() { hipDeviceProp_t p; hipGetDeviceProperties(&p, 0); return p.multiProcessorCount; }
 extern "C" size_t emu_live_allocations() { std::lock_guard<std::mutex> g(g_guard_mu); return g_guard.size(); }
 hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }

@@ -11,7 +11,7 @@ import os
 import pytest
 
 import sortmerna_amd as smr
-from helpers import golden, orc, paths, refrun
+from helpers import golden, orc, paths, refrun, tracegold, tracelimits
 from helpers.cases import CASES, oracle_run
 
 
@@ -101,6 +101,34 @@ def test_oracle_vs_live_reference_on_bundled_data(tmp_path, extra, params):
     assert not bad, "%d differ, first %d" % (len(bad), bad[0])
     assert run.counters.num_aligned == res.log["num_aligned"] > 300
     run.close()
+
+
+@pytest.mark.parametrize("fixture", ["trace_pairs", "trace_limits"])
+def test_orc_ssw_returns_the_stored_alignments_and_cigars_of_ssw_c(fixture):
+    """The oracle's banded_sw restatement is what every record-level CIGAR comparison rests on: pinned here to the alignments AND the CIGARs ssw.c itself
+    returned (tests/golden/trace_pairs.json.gz: seeded random pairs; trace_limits.json.gz: pairs constructed on the band, strip and run-count limits)."""
+    import ctypes as C
+    import numpy as np
+    L = orc.lib()
+    tr = bytes.maketrans(b"ACGTN", bytes(range(5)))
+    cap = len(orc.SswResult().cigar)
+    n = skipped = 0
+    for c in (tracegold if fixture == "trace_pairs" else tracelimits).load():
+        sc = c["scoring"]
+        mat = np.array([(sc["match"] if a == b else sc["mismatch"]) if a < 4 and b < 4 else sc["score_N"] for a in range(5) for b in range(5)], dtype=np.int8)
+        for i, (rd, rf, e, cg) in enumerate(zip(c["reads"], c["refs"], c["expected"], c["cigars"])):
+            if len(cg) > cap:                                            # orc_ssw_result holds 4 096 runs
+                skipped += 1
+                continue
+            read = np.frombuffer(rd.encode().translate(tr), dtype=np.int8).copy()
+            ref = np.frombuffer(rf.encode().translate(tr), dtype=np.int8).copy()
+            r = orc.SswResult()
+            ok = L.orc_ssw(read.ctypes.data, len(read), ref.ctypes.data, len(ref), mat.ctypes.data, sc["gap_open"], sc["gap_ext"], sc["filters"], C.byref(r))
+            what = "%s, scoring %s, %s pair %d" % (fixture, sc, c["kind"], i)
+            assert ok and [r.score1, r.ref_begin1, r.ref_end1, r.read_begin1, r.read_end1] == e, what
+            assert [int(r.cigar[k]) for k in range(r.cigar_len)] == cg, what
+            n += 1
+    assert skipped == 0 and n == (1821 if fixture == "trace_pairs" else len(tracelimits.pairs()))
 
 
 def _affine_score(read, ref, match, mismatch, go, ge):
