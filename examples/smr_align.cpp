@@ -12,7 +12,10 @@
 // smr_report_add / smr_report_add_pair.  Every output file is the same.
 // --rows device (needs --pack device): the rows of aligned.sam and of the BLAST tabular report come from one smr_rows_part call per (index, part)
 // (smr_report_add_rows) instead of read by read; the default, --rows host, is smr_report_add.  Single reads and interleaved mates; refused with
-// --blast 0 and with two reads files, whose rows stay with the host writer.  Every output file is the same.
+// --blast 0 (unless --pairwise device takes it) and with two reads files, whose rows stay with the host writer.  Every output file is the same.
+// --pairwise device (needs --pack device and --blast 0): the BLAST pairwise text comes from one smr_pairwise_part call per (index, part)
+// (smr_report_add_pairwise) instead of read by read; the default, --pairwise host, is smr_report_add.  Single reads and interleaved mates;
+// refused with two reads files.  With --rows device and --split device the per-read loop feeds the report nothing.  Every output file is the same.
 // Build:  g++ -std=c++17 -O2 examples/smr_align.cpp -Iinclude -Lsortmerna_amd/lib -lsmr_hip -Wl,-rpath,$PWD/sortmerna_amd/lib -o smr_align
 // There is no CPU fallback: without a HIP device smr_create fails and the program exits like the reference does (ERR + exit 1).
 #include <cstdint>
@@ -37,7 +40,7 @@ int main(int argc, char** argv) {
   smr_params base; smr_params_default(&base);
   double evalue = 1.0;
   int device = 0;
-  bool pack_device = false, split_device = false, rows_device = false;
+  bool pack_device = false, split_device = false, rows_device = false, pair_device = false;
   smr_report_opts ro; memset(&ro, 0, sizeof ro);
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -64,6 +67,7 @@ int main(int argc, char** argv) {
     else if (a == "-pack" || a == "--pack") { const std::string v = val(); if (v != "host" && v != "device") die("--pack: host or device"); pack_device = v == "device"; }
     else if (a == "-split" || a == "--split") { const std::string v = val(); if (v != "host" && v != "device") die("--split: host or device"); split_device = v == "device"; }
     else if (a == "-rows" || a == "--rows") { const std::string v = val(); if (v != "host" && v != "device") die("--rows: host or device"); rows_device = v == "device"; }
+    else if (a == "-pairwise" || a == "--pairwise") { const std::string v = val(); if (v != "host" && v != "device") die("--pairwise: host or device"); pair_device = v == "device"; }
     else if (a == "-fastx" || a == "--fastx") ro.fastx = 1;
     else if (a == "-other" || a == "--other") ro.other = 1;
     else if (a == "-sam" || a == "--sam") ro.sam = 1;
@@ -86,13 +90,16 @@ int main(int argc, char** argv) {
       printf("usage: smr_align --ref DB.fasta --gumbel LAMBDA K [--idx PREFIX] [--ref ...] --reads READS.fa|fq[.gz] [--reads MATES] [--out DIR]\n"
              "       [-e EVALUE] [-num_alignments N] [-no-best] [-min_lis N] [-num_seeds N] [-edges N] [-full_search] [-F|-R]\n"
              "       [-match N -mismatch N -gap_open N -gap_ext N] [-device K] [--fastx] [--other] [--blast '0' | '1 cigar qcov qstrand'] [--sam [-SQ]]\n"
-             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [--rows host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
+             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [--rows host|device] [--pairwise host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
       return 0;
     } else die("unknown option " + a);
   }
   if (split_device && !pack_device) die("--split device writes aligned.* / other.* from the text the device parsed: it needs --pack device");
   if (rows_device && !pack_device) die("--rows device writes the SAM / BLAST rows from the text the device parsed: it needs --pack device");
-  if (rows_device && ro.blast_pairwise) die("--rows device writes BLAST tabular rows only: --blast 0 (pairwise) stays with --rows host");
+  if (pair_device && !pack_device) die("--pairwise device writes the BLAST pairwise text from the text the device parsed: it needs --pack device");
+  if (pair_device && !ro.blast_pairwise) die("--pairwise device writes the pairwise text of --blast 0: without --blast 0 there is none");
+  if (pair_device && reads_paths.size() == 2) die("--pairwise device takes one reads file (single reads or interleaved mates): the blocks of mates in two files alternate between the batches and stay with --pairwise host");
+  if (rows_device && ro.blast_pairwise && !pair_device) die("--rows device writes BLAST tabular rows only: --blast 0 (pairwise) stays with --rows host");
   if (rows_device && reads_paths.size() == 2) die("--rows device takes one reads file (single reads or interleaved mates): the rows of mates in two files alternate between the batches and stay with --rows host");
   if (dbs.empty() || reads_paths.empty()) die("--ref and --reads are required (see --help)");
   if (const char* why = smr_params_refused(&base)) die(std::string("these options are outside what libsmr_hip aligns (the reference accepts them): ") + why);
@@ -114,7 +121,7 @@ int main(int argc, char** argv) {
   for (size_t b = 0; b < rf.size(); b++) {
     if (pack_device) {
       if (smr_batch_select(gpu, (int)b) != SMR_OK) die(smr_last_error(gpu));
-      if (smr_reads_upload_fastx_file(gpu, reads_paths[b].c_str(), slots, SMR_FASTX_VIEW | ((split_device || rows_device) ? SMR_FASTX_KEEP : 0u), &rf[b], err, sizeof err) != SMR_OK) die(err);
+      if (smr_reads_upload_fastx_file(gpu, reads_paths[b].c_str(), slots, SMR_FASTX_VIEW | ((split_device || rows_device || pair_device) ? SMR_FASTX_KEEP : 0u), &rf[b], err, sizeof err) != SMR_OK) die(err);
     } else if (smr_reads_load_fastx_text(reads_paths[b].c_str(), 0, &rf[b], err, sizeof err) != SMR_OK) die(err);
     n += smr_reads_count(rf[b]); total_len += smr_reads_total_len(rf[b]);
     if (smr_reads_count(rf[b])) { min_len = std::min(min_len, smr_reads_min_len(rf[b])); max_len = std::max(max_len, smr_reads_max_len(rf[b])); }
@@ -159,7 +166,8 @@ int main(int argc, char** argv) {
   size_t n_parts_all = 0;
   for (auto& d : dbs) n_parts_all += d.parts.size();
   const bool rows_dev = rows_device && (ro.sam || ro.blast_tabular);
-  const bool keep_part = rows_dev && n_parts_all == 1;               // --rows device with one part in all: it stays resident for smr_rows_part
+  const bool pair_dev = pair_device && !ro.blast_tabular;            // (with tabular rows as well the host writes no pairwise text either)
+  const bool keep_part = (rows_dev || pair_dev) && n_parts_all == 1; // --rows / --pairwise device with one part in all: it stays resident for smr_rows_part / smr_pairwise_part
   for (size_t k = 0; k < dbs.size(); k++) {
     smr_index_info info; smr_index_get_info(dbs[k].parts[0], &info);
     smr_params p = base;
@@ -195,7 +203,6 @@ int main(int argc, char** argv) {
   // --split device: aligned.* / other.* of the whole input in one call (layout 0: single reads, 1: mates interleaved, 2: mates in batch 1); the
   // loop below then leaves those files alone, and needs the text of a read only for the BLAST and SAM rows
   const bool split_fx = split_device && rep && (ro.fastx || ro.other);
-  const bool rows = ro.blast_tabular || ro.blast_pairwise || ro.sam;
   if (split_fx) {
     smr_fxsplit_opts so; memset(&so, 0, sizeof so);
     so.layout = rf.size() == 2 ? 2 : paired ? 1 : 0;
@@ -208,8 +215,8 @@ int main(int argc, char** argv) {
     smr_report_skip_fastx(rep, 1);
   }
   // --rows device: the SAM / BLAST rows of every (index, part) in one call each, after all alignment (the call order of smr_idcov_part); a run of
-  // more than one part uploads each part again for it
-  if (rows_dev) {
+  // more than one part uploads each part again for it.  --pairwise device: the pairwise text of the part, while it is there
+  if (rows_dev || pair_dev) {
     std::vector<uint8_t> rb;
     if (smr_batch_select(gpu, 0) != SMR_OK) die(smr_last_error(gpu));
     for (size_t k = 0; k < dbs.size(); k++) {
@@ -225,16 +232,26 @@ int main(int argc, char** argv) {
         p.part = (uint32_t)part;
         if (!keep_part && smr_index_upload(gpu, dbs[k].parts[part], 0) != SMR_OK) die(smr_last_error(gpu));
         uint64_t off[3], need = 0;
-        if (smr_rows_part(gpu, 0, &p, dbs[k].parts[part], &wo, nullptr, 0, off, &need) != SMR_OK) die(smr_last_error(gpu));
-        if (rb.size() < need + 1) rb.resize((size_t)need + 1);
-        if (need && smr_rows_part(gpu, 0, &p, dbs[k].parts[part], &wo, rb.data(), need, off, &need) != SMR_OK) die(smr_last_error(gpu));
-        if (smr_report_add_rows(rep, (uint32_t)k, (uint32_t)part, rb.data(), off) != SMR_OK) die(smr_report_last_error(rep));
+        if (rows_dev) {
+          if (smr_rows_part(gpu, 0, &p, dbs[k].parts[part], &wo, nullptr, 0, off, &need) != SMR_OK) die(smr_last_error(gpu));
+          if (rb.size() < need + 1) rb.resize((size_t)need + 1);
+          if (need && smr_rows_part(gpu, 0, &p, dbs[k].parts[part], &wo, rb.data(), need, off, &need) != SMR_OK) die(smr_last_error(gpu));
+          if (smr_report_add_rows(rep, (uint32_t)k, (uint32_t)part, rb.data(), off) != SMR_OK) die(smr_report_last_error(rep));
+        }
+        if (pair_dev) {
+          if (smr_pairwise_part(gpu, 0, &p, dbs[k].parts[part], wo.lambda, wo.K, wo.full_ref_corr, wo.full_read_corr, nullptr, 0, &need) != SMR_OK) die(smr_last_error(gpu));
+          if (rb.size() < need + 1) rb.resize((size_t)need + 1);
+          if (need && smr_pairwise_part(gpu, 0, &p, dbs[k].parts[part], wo.lambda, wo.K, wo.full_ref_corr, wo.full_read_corr, rb.data(), need, &need) != SMR_OK) die(smr_last_error(gpu));
+          if (smr_report_add_pairwise(rep, (uint32_t)k, (uint32_t)part, rb.data(), need) != SMR_OK) die(smr_report_last_error(rep));
+        }
         smr_index_unload(gpu, 0);
       }
     }
-    smr_report_skip_rows(rep, 1);
+    if (rows_dev) smr_report_skip_rows(rep, 1);
+    if (pair_dev) smr_report_skip_pairwise(rep, 1);
   }
-  const bool feed = rep && (!split_fx || (rows && !rows_dev));                     // does the report take the reads one by one at all
+  // does the report take the reads one by one at all: for aligned.* / other.*, or for rows / pairwise text that no device call has brought
+  const bool feed = rep && (!split_fx || ((ro.sam || ro.blast_tabular) && !rows_dev) || (ro.blast_pairwise && !pair_dev));
   // kvdb.put(read.id, read.toBinString()) (processor.cpp:150-155) -> records.bin ; Readstats -> summary.txt
   const std::string rp = out_dir + "/records.bin", sp = out_dir + "/summary.txt";
   FILE* f = fopen(rp.c_str(), "wb");

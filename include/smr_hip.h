@@ -319,7 +319,7 @@ int smr_fastx_split_times(const smr_ctx*, double ms[4]);
  * wanted is empty.  Each holds exactly the bytes the host writer appends for the reads of the batch in order: rows in read order, within a read
  * in alignment-slot order, alignments of other (index, part) keys skipped; no SAM header lines.  That includes the writer's quirk with QUAL (one
  * copy of the quality per key, reversed in place at every reverse-strand alignment of the key) and `%.3g` of %id and qcov, whose digits are
- * found in exact integer arithmetic on the double.  BLAST pairwise (-blast 0) stays with the host writer.
+ * found in exact integer arithmetic on the double.  BLAST pairwise (-blast 0) has its own call, smr_pairwise_part below.
  *   bytes  NULL: sizes only.  cap < *need: SMR_ERR_CAPACITY, off and *need valid, bytes untouched.  Otherwise exactly *need bytes are written
  *          and nothing behind them is touched.  May be pinned memory.
  * SMR_ERR_STATE: a batch without kept text (the message names SMR_FASTX_KEEP); an alignment of the part without a CIGAR (smr_traceback first).
@@ -342,6 +342,27 @@ int smr_rows_times(const smr_ctx*, double ms[4]);
 /* Test seam of the device's number formatter: out[16 i ..] = the text of `stream << (double)num[i] / (double)den[i] * 100` at precision 3
  * (`%.3g`), NUL padded, for n pairs with den > 0 (SMR_ERR_ARG otherwise). */
 int smr_rows_fmt_batch(smr_ctx*, uint32_t n, const uint32_t* num, const uint32_t* den, char* out);
+/* The BLAST-like pairwise text (-blast 0) of the selected batch for ONE (index, part), written on the device (csrc/smr_pairwise.hpp) from what
+ * smr_rows_part reads ("Writing the BLAST pairwise report from the device").  Call order and the meaning of slot / params / ix
+ * as smr_rows_part: the key is index_num and part of the params; lambda, K and the two corrected sizes as given to smr_report_set_db.  The
+ * stream holds exactly what the host writer (smr_report_add of a report opened with blast_pairwise) appends for the reads of the batch in order:
+ * blocks in read order, within a read in alignment-slot order, alignments of other (index, part) keys skipped.  A block: "Sequence ID: <ref
+ * id>", "Query ID: <read id>", the score line (score1, bit score, e-value, strand; both texts from the table smr_rows_part builds, the device
+ * formats no float), then for every 60 alignment columns the Target line, the marks and the Query line, each letter line between its first
+ * 1-based position (setw 8 / 9, never truncated) and the running 0-based position behind the chunk -- which for a chunk made of insertions
+ * only is one less than the Target line's first number, as the host prints it.
+ *   bytes  NULL: the size only.  cap < *need: SMR_ERR_CAPACITY, *need valid, bytes untouched.  Otherwise exactly *need bytes are written and
+ *          nothing behind them is touched.  May be pinned memory.  Offsets are 64 bit.
+ * SMR_ERR_STATE: a batch without kept text (the message names SMR_FASTX_KEEP); an alignment of the part without a CIGAR (smr_traceback first).
+ * SMR_ERR_ARG: `ix` is not the part in `slot`; an e-value or bit-score text too long for the table; and -- counted on the device before any
+ * byte is written -- a CIGAR without columns, a CIGAR that runs past its read or its reference sequence, ref_num >= the part's references.
+ * Every refusal leaves a message that names the call, writes nothing and leaves the context usable.  Runs on the engine's stream; needs no
+ * smr_results_fetch and leaves the host copy alone; changes no stored state; may be repeated and gives the same bytes.  Device memory: that of
+ * smr_rows_part, shared with it. */
+int smr_pairwise_part(smr_ctx*, int slot, const smr_params*, const smr_index* ix, double lambda, double K, uint64_t full_ref_corr, uint64_t full_read_corr,
+                      uint8_t* bytes, uint64_t cap, uint64_t* need);
+/* HIP-event milliseconds of the last smr_pairwise_part: {guards / statistics, sizes and scans, write, bytes D2H} (the last two 0 for a size-only call) */
+int smr_pairwise_times(const smr_ctx*, double ms[4]);
 /* Forget all per-read results/counters of the resident batch (reads stay resident). */
 int smr_state_reset(smr_ctx*);
 
@@ -574,6 +595,14 @@ int smr_report_add_rows(smr_report*, uint32_t index_num, uint32_t part, const ui
 /* on != 0: smr_report_add / smr_report_add_pair leave the SAM and BLAST tabular rows alone (smr_report_add_rows brings them); FASTX, the OTU
  * map, aligned_denovo.* and BLAST pairwise are unaffected */
 int smr_report_skip_rows(smr_report*, int on);
+/* The stream of smr_pairwise_part for (index_num, part): its n bytes are appended to the report's BLAST text of that key, so that
+ * smr_report_close writes aligned.blast as ever (through gzip under zip_out).  SMR_ERR_ARG, and nothing is appended, for a stream that is not
+ * empty when the report was not opened with blast_pairwise, when it was opened with blast_tabular as well (the host writes no pairwise text
+ * then), or when the (index, part) was not registered with smr_report_set_part. */
+int smr_report_add_pairwise(smr_report*, uint32_t index_num, uint32_t part, const uint8_t* bytes, uint64_t n);
+/* on != 0: smr_report_add / smr_report_add_pair leave the BLAST pairwise text alone (smr_report_add_pairwise brings it); FASTX, SAM, BLAST
+ * tabular rows, the OTU map and aligned_denovo.* are unaffected */
+int smr_report_skip_pairwise(smr_report*, int on);
 /* on != 0: smr_report_add / smr_report_add_pair leave aligned.* / other.* alone (smr_report_add_fastx writes them); BLAST, SAM, the OTU map and
  * aligned_denovo.* are unaffected */
 int smr_report_skip_fastx(smr_report*, int on);

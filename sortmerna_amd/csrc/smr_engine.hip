@@ -18,6 +18,7 @@
 #include "smr_fastx.hpp"
 #include "smr_fxsplit.hpp"
 #include "smr_rows.hpp"
+#include "smr_pairwise.hpp"
 #include "smr_ibuild.hpp"
 #include "smr_pgbuild.hpp"
 #include "smr_hostmem.hpp"
@@ -140,6 +141,16 @@ struct RowsScratch {
   ~RowsScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
+// the events and times of smr_pairwise_part (smr_pairwise.hpp); its device buffers are those of RowsScratch
+struct PairScratch {
+  hipEvent_t ev[7] = {};
+  double ms[4] = {0, 0, 0, 0};            // of the last call: guards / statistics, sizes and scans, write, D2H
+  PairScratch() = default;
+  PairScratch(const PairScratch&) = delete;
+  PairScratch& operator=(const PairScratch&) = delete;
+  ~PairScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
 struct smr_ctx {
   const Tuning tune;                      // the environment switches as smr_create found them (smr_tuning.hpp)
   explicit smr_ctx(const Tuning& t) : tune(t) {}
@@ -212,6 +223,7 @@ struct smr_ctx {
   uint64_t fx_info[4] = {0, 0, 0, 0}; double fx_ms[5] = {0, 0, 0, 0, 0};
   FxSplitScratch fxs;
   RowsScratch rows;
+  PairScratch pair;
 };
 struct KpSave { double ms[KP_COUNT]; uint64_t l[KP_COUNT]; };
 
@@ -851,6 +863,7 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
 #include "smr_engine_fastx.hpp"
 #include "smr_engine_fxsplit.hpp"
 #include "smr_engine_rows.hpp"
+#include "smr_engine_pairwise.hpp"
 extern "C" int smr_counters(smr_ctx* c, uint64_t* out, uint32_t n_db) {
   if (!c || !out) return SMR_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));

@@ -23,7 +23,7 @@ bool rows_parse_cols(const char* text, RowsOpts& D) {
 }
 
 // the names of the references of part `part` as the rows print them: sq_header[first_seq + ref_num].first, "*" beyond the table
-int rows_names(smr_ctx* c, DevIndex& d, const smr_index* ix, uint32_t part) {
+int rows_names(smr_ctx* c, DevIndex& d, const smr_index* ix, uint32_t part, const char* who = "smr_rows_part") {
   if (d.rows_names && d.rows_part == (int64_t)part) return SMR_OK;
   size_t first_seq = 0;
   for (uint32_t q = 0; q < part && q < ix->parts.size(); q++) first_seq += ix->parts[q].numseq_part;
@@ -32,7 +32,7 @@ int rows_names(smr_ctx* c, DevIndex& d, const smr_index* ix, uint32_t part) {
   for (uint32_t r = 0; r < d.n_refs; r++) {
     off[r] = (uint32_t)all.size();
     if (first_seq + r < ix->sq_header.size()) all += ix->sq_header[first_seq + r].first; else all += '*';
-    if (all.size() >= 0xFFFFFF00ull) { set_err(c, "smr_rows_part: the reference names of the part take 4 GiB or more"); return SMR_ERR_CAPACITY; }
+    if (all.size() >= 0xFFFFFF00ull) { set_err(c, std::string(who) + ": the reference names of the part take 4 GiB or more"); return SMR_ERR_CAPACITY; }
   }
   off[d.n_refs] = (uint32_t)all.size();
   all.resize((all.size() + 8u) & ~(size_t)3u, '\0');     // (the kernels fetch a byte as part of its aligned dword)
@@ -47,14 +47,14 @@ int rows_names(smr_ctx* c, DevIndex& d, const smr_index* ix, uint32_t part) {
 }
 
 // the texts of e-value and bit score for score1 = 0 .. n_tab - 1 under the database of `o`; kept until another database or a higher score asks
-int rows_table(smr_ctx* c, const smr_rows_opts* o, uint32_t n_tab) {
+int rows_table(smr_ctx* c, const smr_rows_opts* o, uint32_t n_tab, const char* who = "smr_rows_part") {
   RowsScratch& S = c->rows;
   if (S.tab && S.tab_n >= n_tab && S.tab_lambda == o->lambda && S.tab_K == o->K && S.tab_ref == o->full_ref_corr && S.tab_read == o->full_read_corr) return SMR_OK;
   std::vector<uint8_t> h((size_t)n_tab * ROWS_TAB_ENTRY, 0);
   std::string ev, bs;
   for (uint32_t s = 0; s < n_tab; s++) {
     score_texts(o->lambda, o->K, o->full_ref_corr, o->full_read_corr, s, ev, bs);
-    if (ev.size() > 14u || bs.size() > 16u) { set_err(c, "smr_rows_part: an e-value or bit score of more than 14 / 16 characters"); return SMR_ERR_ARG; }
+    if (ev.size() > 14u || bs.size() > 16u) { set_err(c, std::string(who) + ": an e-value or bit score of more than 14 / 16 characters"); return SMR_ERR_ARG; }
     uint8_t* e = h.data() + (size_t)s * ROWS_TAB_ENTRY;
     e[0] = (uint8_t)ev.size(); e[1] = (uint8_t)bs.size();
     memcpy(e + 2, ev.data(), ev.size()); memcpy(e + 16, bs.data(), bs.size());

@@ -99,6 +99,7 @@ struct smr_report {
   std::string err, cmdline = "libsmr_hip";
   bool skip_fx = false;                                                // smr_report_skip_fastx: aligned.* / other.* come from smr_report_add_fastx
   bool skip_rows = false;                                              // smr_report_skip_rows: the SAM and BLAST tabular rows come from smr_report_add_rows
+  bool skip_pair = false;                                              // smr_report_skip_pairwise: the BLAST pairwise text comes from smr_report_add_pairwise
 };
 
 extern "C" int smr_report_open(const char* out_dir, const smr_report_opts* opts, int is_fastq, smr_report** out, char* err, size_t errcap) {
@@ -255,6 +256,22 @@ extern "C" int smr_report_skip_rows(smr_report* r, int on) {
   r->skip_rows = on != 0;
   return SMR_OK;
 }
+extern "C" int smr_report_add_pairwise(smr_report* r, uint32_t index_num, uint32_t part, const uint8_t* bytes, uint64_t n) {
+  if (!r) return SMR_ERR_ARG;
+  if (n == 0) return SMR_OK;
+  if (!bytes) { r->err = "smr_report_add_pairwise: text without bytes"; return SMR_ERR_ARG; }
+  if (!r->o.blast_pairwise) { r->err = "smr_report_add_pairwise: pairwise text for a report that was not opened with blast_pairwise"; return SMR_ERR_ARG; }
+  if (r->o.blast_tabular) { r->err = "smr_report_add_pairwise: the report was opened with blast_tabular as well, and then holds no pairwise text"; return SMR_ERR_ARG; }
+  const std::pair<uint32_t, uint32_t> key{index_num, part};
+  if (r->parts.find(key) == r->parts.end()) { r->err = "smr_report_add_pairwise: the (index, part) was not registered"; return SMR_ERR_ARG; }
+  r->blast[key].append(reinterpret_cast<const char*>(bytes), (size_t)n);
+  return SMR_OK;
+}
+extern "C" int smr_report_skip_pairwise(smr_report* r, int on) {
+  if (!r) return SMR_ERR_ARG;
+  r->skip_pair = on != 0;
+  return SMR_OK;
+}
 extern "C" int smr_report_skip_fastx(smr_report* r, int on) {
   if (!r) return SMR_ERR_ARG;
   r->skip_fx = on != 0;
@@ -309,8 +326,8 @@ int add_otu(smr_report* r, const char* header, const char* seq, const std::vecto
 }
 
 int add_rows(smr_report* r, const char* header, const char* seq, const char* qual, const std::vector<Aln>& alns) {
-  // (smr_report_skip_rows: SAM and BLAST tabular are written elsewhere; BLAST pairwise stays here)
-  const bool do_tab = r->o.blast_tabular && !r->skip_rows, do_sam = r->o.sam && !r->skip_rows, do_pair = r->o.blast_pairwise && !r->o.blast_tabular;
+  // (smr_report_skip_rows: SAM and BLAST tabular are written elsewhere; smr_report_skip_pairwise: BLAST pairwise is)
+  const bool do_tab = r->o.blast_tabular && !r->skip_rows, do_sam = r->o.sam && !r->skip_rows, do_pair = r->o.blast_pairwise && !r->o.blast_tabular && !r->skip_pair;
   if (alns.empty() || (!do_tab && !do_pair && !do_sam)) return SMR_OK;
   // Read::getSeqId (read.cpp:371-377)
   std::string id(header);

@@ -441,6 +441,23 @@ class Engine:
         self._chk(self.L.smr_rows_times(self.h, ms), "smr_rows_times")
         return dict(zip(("stats", "sizes", "write", "d2h"), (float(x) for x in ms)))
 
+    def pairwise_part(self, slot, params, index, lam=0.0, K=0.0, full_ref=0, full_read=0):
+        """smr_pairwise_part: the BLAST-like pairwise text (-blast 0) of the selected batch (uploaded with keep=True) for the (index, part) of
+        `params`, resident in `slot`, written on the device -> bytes.  lam, K, full_ref, full_read: what Report.set_db takes for that index."""
+        need = C.c_uint64(0)
+        args = (self.h, slot, C.byref(params), index.h, float(lam), float(K), int(full_ref), int(full_read))
+        self._chk(self.L.smr_pairwise_part(*args, None, 0, C.byref(need)), "smr_pairwise_part")
+        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
+        if need.value:
+            self._chk(self.L.smr_pairwise_part(*args, buf.ctypes.data, need.value, C.byref(need)), "smr_pairwise_part")
+        return buf[:need.value].tobytes()
+
+    def pairwise_times(self):
+        """HIP-event ms of the last pairwise_part: dict(stats, sizes, write, d2h)"""
+        ms = (C.c_double * 4)()
+        self._chk(self.L.smr_pairwise_times(self.h, ms), "smr_pairwise_times")
+        return dict(zip(("stats", "sizes", "write", "d2h"), (float(x) for x in ms)))
+
     def rows_fmt_batch(self, num, den):
         """smr_rows_fmt_batch (a test seam): the device's `%.3g` of 100 * num[i] / den[i] -> list of str"""
         num = np.ascontiguousarray(num, dtype=np.uint32)

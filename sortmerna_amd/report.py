@@ -84,6 +84,15 @@ class Report:
         """add / add_pair leave SAM and BLAST tabular alone: add_rows brings them (smr_report_skip_rows)"""
         self._chk(self.L.smr_report_skip_rows(self.h, int(bool(on))), "smr_report_skip_rows")
 
+    def add_pairwise(self, index_num, part, data):
+        """the stream of Engine.pairwise_part appended to the report's BLAST pairwise text of (index_num, part) (smr_report_add_pairwise)"""
+        data = bytes(data)
+        self._chk(self.L.smr_report_add_pairwise(self.h, index_num, part, data if data else None, len(data)), "smr_report_add_pairwise")
+
+    def skip_pairwise(self, on=True):
+        """add / add_pair leave the BLAST pairwise text alone: add_pairwise brings it (smr_report_skip_pairwise)"""
+        self._chk(self.L.smr_report_skip_pairwise(self.h, int(bool(on))), "smr_report_skip_pairwise")
+
     def merge_otu_from(self, other):
         """the OTU map entries of `other` (the next shard of the reads, in input order) behind this report's; `other` then writes no map"""
         self._chk(self.L.smr_report_otu_merge(self.h, other.h), "smr_report_otu_merge")
