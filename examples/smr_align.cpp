@@ -16,6 +16,11 @@
 // --pairwise device (needs --pack device and --blast 0): the BLAST pairwise text comes from one smr_pairwise_part call per (index, part)
 // (smr_report_add_pairwise) instead of read by read; the default, --pairwise host, is smr_report_add.  Single reads and interleaved mates;
 // refused with two reads files.  With --rows device and --split device the per-read loop feeds the report nothing.  Every output file is the same.
+// -otu_map -de_novo_otu -id X -coverage X: the %id / %coverage pass (smr_idcov_part, the reference's denovo_stats) per (index, part) after all
+// alignment, otu_map.txt and aligned_denovo.fa|fq, the two Results lines of aligned.log; defaults and refusals are the reference's.
+// --otu device (needs --pack device): the members of otu_map.txt come from one smr_otu_part call per (index, part) (smr_report_add_otu) and
+// aligned_denovo.* from one smr_fastx_denovo call (smr_report_add_denovo) instead of read by read; the default, --otu host, is smr_report_add.
+// Single reads and interleaved mates; refused with two reads files.  Every output file is the same.
 // Build:  g++ -std=c++17 -O2 examples/smr_align.cpp -Iinclude -Lsortmerna_amd/lib -lsmr_hip -Wl,-rpath,$PWD/sortmerna_amd/lib -o smr_align
 // There is no CPU fallback: without a HIP device smr_create fails and the program exits like the reference does (ERR + exit 1).
 #include <cstdint>
@@ -40,7 +45,8 @@ int main(int argc, char** argv) {
   smr_params base; smr_params_default(&base);
   double evalue = 1.0;
   int device = 0;
-  bool pack_device = false, split_device = false, rows_device = false, pair_device = false;
+  bool pack_device = false, split_device = false, rows_device = false, pair_device = false, otu_device = false;
+  bool id_given = false, cov_given = false;
   smr_report_opts ro; memset(&ro, 0, sizeof ro);
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -68,6 +74,11 @@ int main(int argc, char** argv) {
     else if (a == "-split" || a == "--split") { const std::string v = val(); if (v != "host" && v != "device") die("--split: host or device"); split_device = v == "device"; }
     else if (a == "-rows" || a == "--rows") { const std::string v = val(); if (v != "host" && v != "device") die("--rows: host or device"); rows_device = v == "device"; }
     else if (a == "-pairwise" || a == "--pairwise") { const std::string v = val(); if (v != "host" && v != "device") die("--pairwise: host or device"); pair_device = v == "device"; }
+    else if (a == "-otu" || a == "--otu") { const std::string v = val(); if (v != "host" && v != "device") die("--otu: host or device"); otu_device = v == "device"; }
+    else if (a == "-otu_map" || a == "--otu_map") ro.otu_map = 1;
+    else if (a == "-de_novo_otu" || a == "--de_novo_otu") ro.denovo = 1;
+    else if (a == "-id" || a == "--id") { ro.min_id = atof(val().c_str()); id_given = true; }
+    else if (a == "-coverage" || a == "--coverage") { ro.min_cov = atof(val().c_str()); cov_given = true; }
     else if (a == "-fastx" || a == "--fastx") ro.fastx = 1;
     else if (a == "-other" || a == "--other") ro.other = 1;
     else if (a == "-sam" || a == "--sam") ro.sam = 1;
@@ -90,7 +101,7 @@ int main(int argc, char** argv) {
       printf("usage: smr_align --ref DB.fasta --gumbel LAMBDA K [--idx PREFIX] [--ref ...] --reads READS.fa|fq[.gz] [--reads MATES] [--out DIR]\n"
              "       [-e EVALUE] [-num_alignments N] [-no-best] [-min_lis N] [-num_seeds N] [-edges N] [-full_search] [-F|-R]\n"
              "       [-match N -mismatch N -gap_open N -gap_ext N] [-device K] [--fastx] [--other] [--blast '0' | '1 cigar qcov qstrand'] [--sam [-SQ]]\n"
-             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [--rows host|device] [--pairwise host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
+             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [--rows host|device] [--pairwise host|device] [-otu_map [-id X] [-coverage X]] [-de_novo_otu] [--otu host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
       return 0;
     } else die("unknown option " + a);
   }
@@ -101,6 +112,14 @@ int main(int argc, char** argv) {
   if (pair_device && reads_paths.size() == 2) die("--pairwise device takes one reads file (single reads or interleaved mates): the blocks of mates in two files alternate between the batches and stay with --pairwise host");
   if (rows_device && ro.blast_pairwise && !pair_device) die("--rows device writes BLAST tabular rows only: --blast 0 (pairwise) stays with --rows host");
   if (rows_device && reads_paths.size() == 2) die("--rows device takes one reads file (single reads or interleaved mates): the rows of mates in two files alternate between the batches and stay with --rows host");
+  // the reference's rules for the four options (options.cpp:1623-1628, 1667-1674, 1744-1757)
+  if ((id_given || cov_given) && !ro.otu_map) die("options '-id' and '-coverage' can only be used together with '-otu_map': they are the thresholds of the OTU map");
+  if (ro.otu_map && !base.is_best) die("option '-otu_map' cannot be used with '-no-best': the OTU map is built from the best alignments");
+  if (ro.otu_map) { if (!id_given) ro.min_id = 0.97; if (!cov_given) ro.min_cov = 0.97; }
+  if (!(ro.min_id >= 0 && ro.min_id <= 1 && ro.min_cov >= 0 && ro.min_cov <= 1)) die("-id and -coverage take a value within [0, 1]");
+  const bool idcov = ro.otu_map || ro.denovo;
+  if (otu_device && !pack_device) die("--otu device writes the OTU map and aligned_denovo.* from the text the device parsed: it needs --pack device");
+  if (otu_device && reads_paths.size() == 2) die("--otu device takes one reads file (single reads or interleaved mates): the members of a group of mates in two files alternate between the batches and stay with --otu host");
   if (dbs.empty() || reads_paths.empty()) die("--ref and --reads are required (see --help)");
   if (const char* why = smr_params_refused(&base)) die(std::string("these options are outside what libsmr_hip aligns (the reference accepts them): ") + why);
   // minimal_score (which reads count as aligned) and the e-values / bit scores of the BLAST report depend on the Gumbel parameters of the
@@ -121,7 +140,7 @@ int main(int argc, char** argv) {
   for (size_t b = 0; b < rf.size(); b++) {
     if (pack_device) {
       if (smr_batch_select(gpu, (int)b) != SMR_OK) die(smr_last_error(gpu));
-      if (smr_reads_upload_fastx_file(gpu, reads_paths[b].c_str(), slots, SMR_FASTX_VIEW | ((split_device || rows_device || pair_device) ? SMR_FASTX_KEEP : 0u), &rf[b], err, sizeof err) != SMR_OK) die(err);
+      if (smr_reads_upload_fastx_file(gpu, reads_paths[b].c_str(), slots, SMR_FASTX_VIEW | ((split_device || rows_device || pair_device || (otu_device && idcov)) ? SMR_FASTX_KEEP : 0u), &rf[b], err, sizeof err) != SMR_OK) die(err);
     } else if (smr_reads_load_fastx_text(reads_paths[b].c_str(), 0, &rf[b], err, sizeof err) != SMR_OK) die(err);
     n += smr_reads_count(rf[b]); total_len += smr_reads_total_len(rf[b]);
     if (smr_reads_count(rf[b])) { min_len = std::min(min_len, smr_reads_min_len(rf[b])); max_len = std::max(max_len, smr_reads_max_len(rf[b])); }
@@ -167,7 +186,8 @@ int main(int argc, char** argv) {
   for (auto& d : dbs) n_parts_all += d.parts.size();
   const bool rows_dev = rows_device && (ro.sam || ro.blast_tabular);
   const bool pair_dev = pair_device && !ro.blast_tabular;            // (with tabular rows as well the host writes no pairwise text either)
-  const bool keep_part = (rows_dev || pair_dev) && n_parts_all == 1; // --rows / --pairwise device with one part in all: it stays resident for smr_rows_part / smr_pairwise_part
+  const bool otu_dev = otu_device && idcov;
+  const bool keep_part = (rows_dev || pair_dev || idcov) && n_parts_all == 1; // one part in all: it stays resident for the pass and for smr_rows_part / smr_pairwise_part / smr_otu_part
   for (size_t k = 0; k < dbs.size(); k++) {
     smr_index_info info; smr_index_get_info(dbs[k].parts[0], &info);
     smr_params p = base;
@@ -183,14 +203,36 @@ int main(int argc, char** argv) {
       if (!keep_part) smr_index_unload(gpu, 0);
     }
   }
+  // denovo_stats (processor.cpp:287-438): after ALL alignment -- the pass counts final alignments --, per (index, part), before the records are fetched
+  uint64_t idc[4] = {0, 0, 0, 0};
+  if (idcov) {
+    for (size_t k = 0; k < dbs.size(); k++) {
+      smr_params p = base;
+      p.index_num = (uint32_t)k;
+      for (size_t part = 0; part < dbs[k].parts.size(); part++) {
+        p.part = (uint32_t)part;
+        if (!keep_part && smr_index_upload(gpu, dbs[k].parts[part], 0) != SMR_OK) die(smr_last_error(gpu));
+        for (size_t b = 0; b < rf.size(); b++)
+          if (smr_batch_select(gpu, (int)b) != SMR_OK || smr_idcov_part(gpu, 0, &p, ro.min_id, ro.min_cov) != SMR_OK) die(smr_last_error(gpu));
+        if (!keep_part) smr_index_unload(gpu, 0);
+      }
+    }
+    for (size_t b = 0; b < rf.size(); b++) {
+      uint64_t c4[4];
+      if (smr_batch_select(gpu, (int)b) != SMR_OK || smr_idcov_counters(gpu, c4) != SMR_OK) die(smr_last_error(gpu));
+      for (int q = 0; q < 4; q++) idc[q] += c4[q];
+    }
+  }
   for (size_t b = 0; b < rf.size(); b++) if (smr_batch_select(gpu, (int)b) != SMR_OK || smr_results_fetch(gpu) != SMR_OK) die(smr_last_error(gpu));
 
   // reports (writeReports, output.cpp:169-272)
   smr_report* rep = nullptr;
   std::string cmdline;
   for (int i = 0; i < argc; i++) { cmdline += argv[i]; cmdline += ' '; }       // the reference's opts.cmdline keeps the trailing blank
-  if (ro.fastx || ro.other || ro.blast_tabular || ro.blast_pairwise || ro.sam) {
+  uint64_t total_otu = 0;
+  if (ro.fastx || ro.other || ro.blast_tabular || ro.blast_pairwise || ro.sam || idcov) {
     if (smr_report_open(out_dir.c_str(), &ro, is_fastq, &rep, err, sizeof err) != SMR_OK) die(err);
+    if (ro.otu_map && smr_report_otu_count(rep, &total_otu) != SMR_OK) die("smr_report_otu_count failed");
     smr_report_set_cmdline(rep, cmdline.c_str());
     for (size_t k = 0; k < dbs.size(); k++) {
       smr_index_info info; smr_index_get_info(dbs[k].parts[0], &info);
@@ -216,8 +258,11 @@ int main(int argc, char** argv) {
   }
   // --rows device: the SAM / BLAST rows of every (index, part) in one call each, after all alignment (the call order of smr_idcov_part); a run of
   // more than one part uploads each part again for it.  --pairwise device: the pairwise text of the part, while it is there
-  if (rows_dev || pair_dev) {
+  // --otu device: the members of the map of the part from smr_otu_part, in the same visit
+  const bool map_dev = otu_dev && ro.otu_map;
+  if (rows_dev || pair_dev || map_dev) {
     std::vector<uint8_t> rb;
+    std::vector<smr_otu_group> gb;
     if (smr_batch_select(gpu, 0) != SMR_OK) die(smr_last_error(gpu));
     for (size_t k = 0; k < dbs.size(); k++) {
       smr_index_info info; smr_index_get_info(dbs[k].parts[0], &info);
@@ -244,14 +289,38 @@ int main(int argc, char** argv) {
           if (need && smr_pairwise_part(gpu, 0, &p, dbs[k].parts[part], wo.lambda, wo.K, wo.full_ref_corr, wo.full_read_corr, rb.data(), need, &need) != SMR_OK) die(smr_last_error(gpu));
           if (smr_report_add_pairwise(rep, (uint32_t)k, (uint32_t)part, rb.data(), need) != SMR_OK) die(smr_report_last_error(rep));
         }
+        if (map_dev) {
+          uint64_t need2[2] = {0, 0}; int any = 0;
+          if (smr_otu_part(gpu, 0, &p, dbs[k].parts[part], ro.min_id, ro.min_cov, nullptr, 0, nullptr, 0, need2, &any) != SMR_OK) die(smr_last_error(gpu));
+          if (rb.size() < need2[0] + 1) rb.resize((size_t)need2[0] + 1);
+          if (gb.size() < need2[1] + 1) gb.resize((size_t)need2[1] + 1);
+          if (need2[1] && smr_otu_part(gpu, 0, &p, dbs[k].parts[part], ro.min_id, ro.min_cov, rb.data(), need2[0], gb.data(), need2[1], need2, &any) != SMR_OK) die(smr_last_error(gpu));
+          if (smr_report_add_otu(rep, (uint32_t)k, (uint32_t)part, rb.data(), need2[0], gb.data(), need2[1], any) != SMR_OK) die(smr_report_last_error(rep));
+        }
         smr_index_unload(gpu, 0);
       }
     }
+    if (map_dev) smr_report_skip_otu(rep, 1);
     if (rows_dev) smr_report_skip_rows(rep, 1);
     if (pair_dev) smr_report_skip_pairwise(rep, 1);
   }
-  // does the report take the reads one by one at all: for aligned.* / other.*, or for rows / pairwise text that no device call has brought
-  const bool feed = rep && (!split_fx || ((ro.sam || ro.blast_tabular) && !rows_dev) || (ro.blast_pairwise && !pair_dev));
+  // --otu device: aligned_denovo.* of the whole input in one call (layout 0: single reads, 1: mates interleaved)
+  const bool dn_dev = otu_dev && ro.denovo;
+  if (dn_dev) {
+    smr_fxsplit_opts so; memset(&so, 0, sizeof so);
+    so.layout = paired ? 1 : 0;
+    so.paired_in = ro.paired_in; so.paired_out = ro.paired_out; so.out2 = ro.out2; so.sout = ro.sout;
+    uint64_t off[5], need = 0;
+    if (smr_batch_select(gpu, 0) != SMR_OK || smr_fastx_denovo(gpu, -1, &so, nullptr, nullptr, 0, off, &need) != SMR_OK) die(smr_last_error(gpu));
+    std::vector<uint8_t> fx((size_t)need + 1);
+    if (need && smr_fastx_denovo(gpu, -1, &so, nullptr, fx.data(), need, off, &need) != SMR_OK) die(smr_last_error(gpu));
+    if (smr_report_add_denovo(rep, fx.data(), off) != SMR_OK) die(smr_report_last_error(rep));
+    smr_report_skip_denovo(rep, 1);
+  }
+  // does the report take the reads one by one at all: for aligned.* / other.*, for rows / pairwise text, for the map or aligned_denovo.* that no
+  // device call has brought
+  const bool feed = rep && (!split_fx || ((ro.sam || ro.blast_tabular) && !rows_dev) || (ro.blast_pairwise && !pair_dev) || (ro.otu_map && !map_dev) ||
+                            (ro.denovo && !dn_dev));
   // kvdb.put(read.id, read.toBinString()) (processor.cpp:150-155) -> records.bin ; Readstats -> summary.txt
   const std::string rp = out_dir + "/records.bin", sp = out_dir + "/summary.txt";
   FILE* f = fopen(rp.c_str(), "wb");
@@ -314,6 +383,8 @@ int main(int argc, char** argv) {
   fprintf(f, "Total reads = %llu\nTotal reads passing E-value threshold = %llu\nToo short reads (last part) = %llu\n", (unsigned long long)n,
           (unsigned long long)ctr[0], (unsigned long long)ctr[1]);
   for (size_t k = 0; k < dbs.size(); k++) fprintf(f, "%s\t%llu\n", dbs[k].fasta.c_str(), (unsigned long long)ctr[2 + k]);
+  if (idcov) fprintf(f, "num_yid_ycov = %llu\nnum_yid_ncov = %llu\nnum_nid_ycov = %llu\nnum_denovo = %llu\nTotal OTUs = %llu\n", (unsigned long long)idc[0],
+                     (unsigned long long)idc[1], (unsigned long long)idc[2], (unsigned long long)idc[3], (unsigned long long)total_otu);
   fclose(f);
   {  // aligned.log (Summary::write, summary.cpp:57-100)
     std::vector<smr_summary_db> sdb(dbs.size());
@@ -336,6 +407,7 @@ int main(int argc, char** argv) {
     sm.total_reads = n; sm.num_aligned = ctr[0]; sm.all_reads_len = total_len;
     sm.min_read_len = min_len; sm.max_read_len = max_len;
     sm.dbs = sdb.data(); sm.n_dbs = (uint32_t)sdb.size();
+    sm.is_denovo = ro.denovo; sm.total_denovo = idc[3]; sm.is_otu_map = ro.otu_map; sm.total_id_cov = idc[0]; sm.total_otu = total_otu;
     if (smr_summary_write((out_dir + "/aligned.log").c_str(), &sm) != SMR_OK) die("cannot write aligned.log");
   }
   printf("%llu reads, %llu aligned, %llu records -> %s\n", (unsigned long long)n, (unsigned long long)ctr[0], (unsigned long long)nrec, rp.c_str());

@@ -363,6 +363,43 @@ int smr_pairwise_part(smr_ctx*, int slot, const smr_params*, const smr_index* ix
                       uint8_t* bytes, uint64_t cap, uint64_t* need);
 /* HIP-event milliseconds of the last smr_pairwise_part: {guards / statistics, sizes and scans, write, bytes D2H} (the last two 0 for a size-only call) */
 int smr_pairwise_times(const smr_ctx*, double ms[4]);
+/* The members of otu_map.txt (-otu_map) of the selected batch for ONE (index, part), found, grouped and written on the device (csrc/smr_otu.hpp):
+ * what smr_results_fetch + smr_reads_record_text + smr_result_record + smr_report_add leave in the report's map entries of that key one read at
+ * a time ("Writing the OTU map and aligned_denovo.* from the device").  Call it after smr_idcov_part has run for every (index,
+ * part) of the run, once per (index, part) with that part resident in `slot`; slot, params and ix as for smr_rows_part.  As the host writer
+ * (fill_otu_map2, otumap.cpp:131-198) it classifies AGAIN every stored alignment of the key of every read whose c_yid_ycov > 0, over the
+ * FORWARD read letters whatever the strand, rounding with `floor(x * 1000.0 + 0.5) * 0.001` (not `/ 1000.0` as the pass does: 9 * 0.001 >
+ * 9 / 1000.0); an alignment that passes both thresholds adds the read's id (the header up to the first space, without '>' / '@') to the group
+ * of its reference.  Groups come in ascending ref_num, the members of a group in read order, then alignment-slot order; the text of group g is
+ * bytes[groups[g].off, groups[g + 1].off or need[0]): its ids joined by '\t', no terminator; groups lie back to back.  *any_yid_ycov: does any
+ * read of the batch have c_yid_ycov > 0 -- whether the map file exists at all, whatever passed for this key.
+ *   bytes / groups  either NULL: sizes only.  cap < need[0] or groups_cap < need[1]: SMR_ERR_CAPACITY, need valid, nothing written.  Otherwise
+ *                   exactly need[0] bytes and need[1] groups are written and nothing behind them is touched.  `bytes` may be pinned memory.
+ * SMR_ERR_STATE: a batch without kept text (the message names SMR_FASTX_KEEP); for a read with c_yid_ycov > 0, an alignment of the key without
+ * a CIGAR.  SMR_ERR_ARG: thresholds outside [0, 1] or NaN; `ix` is not the part in `slot`; and -- for reads with c_yid_ycov > 0, counted on the
+ * device before any byte is written -- a CIGAR with an M column outside its read or its reference (what the host writer refuses; insertions or deletions
+ * that alone run past the end are accepted as there), a negative read_begin1 / ref_begin1, ref_num >= the part's references.  A batch on which the
+ * pass never ran gives zero groups and *any_yid_ycov = 0.  Every refusal leaves a message that names the call, writes nothing and leaves the
+ * context usable.  Runs on the engine's stream; needs no smr_results_fetch; changes no stored state (it sets no mark as smr_idcov_part does);
+ * may be repeated and gives the same bytes.  Device memory, kept for the next call: 1 byte per alignment slot, 24 per read, 32 per member,
+ * 2 KB per 1024 members, the output. */
+typedef struct { uint32_t ref_num, n_reads; uint64_t off; } smr_otu_group;
+int smr_otu_part(smr_ctx*, int slot, const smr_params*, const smr_index* ix, double min_id, double min_cov,
+                 uint8_t* bytes, uint64_t cap, smr_otu_group* groups, uint64_t groups_cap, uint64_t need[2] /* bytes, groups */, int* any_yid_ycov);
+/* HIP-event milliseconds of the last smr_otu_part: {classify, sizes and scans, sort, write, D2H} (the last two 0 for a sizes-only call) */
+int smr_otu_times(const smr_ctx*, double ms[5]);
+/* Test seam of the sort of smr_otu_part: perm[0..n) = the STABLE permutation that orders keys[] (each below 2^key_bits, key_bits <= 32:
+ * SMR_ERR_ARG otherwise) ascending -- ceil(key_bits / 8) radix passes, none for key_bits = 0. */
+int smr_otu_sort_batch(smr_ctx*, uint32_t n, const uint32_t* keys, uint32_t key_bits, uint32_t* perm);
+/* The aligned_denovo.* FASTX outputs (-de_novo_otu) of the selected batch, written on the device beside smr_fastx_split, whose layouts, `mates`
+ * and size / capacity / state contract it shares (want_aligned / want_other are ignored).  Four streams; stream j is bytes[off[j], off[j + 1]),
+ * off[4] = *need, and belongs to the aligned_denovo file smr_report_open gives index j.  A read is a de novo read when n_denovo > 0 and the other
+ * three counters of smr_idcov_part are 0 (a batch without the pass has none) -- or, with `dn`, when its byte there is non-zero (the reads of the
+ * selected batch, then, layout 2, those of batch `mates`).  Layout 0 routes as smr_report_add, layouts 1 and 2 by the table of
+ * smr_report_add_pair (ReportDenovo::append, report_denovo.cpp:57-134), its two quirks under out2 included: nothing for a pair under paired_out
+ * unless both mates are de novo reads, and otherwise BOTH mates written, the one that is no de novo read to file 0. */
+int smr_fastx_denovo(smr_ctx*, int mates, const smr_fxsplit_opts*, const uint8_t* dn /* NULL: the batches' own counters */,
+                     uint8_t* bytes, uint64_t cap, uint64_t off[5], uint64_t* need);
 /* Forget all per-read results/counters of the resident batch (reads stay resident). */
 int smr_state_reset(smr_ctx*);
 
@@ -606,6 +643,25 @@ int smr_report_skip_pairwise(smr_report*, int on);
 /* on != 0: smr_report_add / smr_report_add_pair leave aligned.* / other.* alone (smr_report_add_fastx writes them); BLAST, SAM, the OTU map and
  * aligned_denovo.* are unaffected */
 int smr_report_skip_fastx(smr_report*, int on);
+/* The groups of smr_otu_part for (index_num, part): appended to the report's map entries of that key, behind what the key already holds; the
+ * reference id of a group is sq_header[first_seq + ref_num], "*" beyond the table, as smr_report_add finds it.  Afterwards smr_report_close,
+ * smr_report_otu_merge and smr_report_otu_count give the file, the merge and the count they would give had the same reads gone through
+ * smr_report_add.  any_yid_ycov != 0: the map file exists.  SMR_ERR_ARG, and nothing is appended, when the report was opened without otu_map,
+ * when the (index, part) was not registered, when offsets decrease or run past n_bytes, or when a group has n_reads == 0 or fewer ids than
+ * members.  Two things differ from what smr_report_add leaves behind, neither in the file of a part whose references print distinct ids:
+ * (1) a group's text is cut into its n_reads entries at tabs, so an id that itself holds a tab (a header with a tab before its first space) is
+ * stored as pieces -- adjacent, so the file and the line count are the same, but the entries are not the ids; (2) where several references of
+ * the part print the same id (duplicate ids, or several beyond the table, all "*"), their members are appended reference after reference,
+ * where smr_report_add has them in read order. */
+int smr_report_add_otu(smr_report*, uint32_t index_num, uint32_t part, const uint8_t* bytes, uint64_t n_bytes, const smr_otu_group* groups,
+                       uint64_t n_groups, int any_yid_ycov);
+/* on != 0: smr_report_add / smr_report_add_pair leave the OTU map alone (smr_report_add_otu brings it); everything else is unaffected */
+int smr_report_skip_otu(smr_report*, int on);
+/* The streams of smr_fastx_denovo: stream j is appended to the open aligned_denovo file of that index, through gzip under zip_out.
+ * SMR_ERR_ARG, and nothing is written, when a stream that is not empty has no open file or the offsets decrease. */
+int smr_report_add_denovo(smr_report*, const uint8_t* bytes, const uint64_t off[5]);
+/* on != 0: smr_report_add / smr_report_add_pair leave aligned_denovo.* alone (smr_report_add_denovo writes them); everything else is unaffected */
+int smr_report_skip_denovo(smr_report*, int on);
 /* *total_otu = lines of otu_map.txt (Readstats::total_otu, for smr_summary), stored when smr_report_close runs: the pointer must live until then */
 int smr_report_otu_count(smr_report*, uint64_t* total_otu);
 /* One otu_map.txt for a run whose reads went through several report objects (one per device, each fed a contiguous shard of the reads in input

@@ -19,6 +19,7 @@
 #include "smr_fxsplit.hpp"
 #include "smr_rows.hpp"
 #include "smr_pairwise.hpp"
+#include "smr_otu.hpp"
 #include "smr_ibuild.hpp"
 #include "smr_pgbuild.hpp"
 #include "smr_hostmem.hpp"
@@ -151,6 +152,18 @@ struct PairScratch {
   ~PairScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
+// scratch and staging of smr_otu_part (smr_otu.hpp), grow-only
+struct OtuScratch {
+  DevBuf<uint8_t> pass, out; DevBuf<uint2> meta; DevBuf<uint4> pairs; DevBuf<uint32_t> key[2], val[2], gstart, err;
+  DevBuf<unsigned long long> excl, part, hist, wexcl, wpart, gexcl, gpart; DevBuf<OtuGroup> groups;
+  hipEvent_t ev[10] = {};
+  double ms[5] = {0, 0, 0, 0, 0};         // of the last call: classify, size + scans, sort, write, D2H
+  OtuScratch() = default;
+  OtuScratch(const OtuScratch&) = delete;
+  OtuScratch& operator=(const OtuScratch&) = delete;
+  ~OtuScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
 struct smr_ctx {
   const Tuning tune;                      // the environment switches as smr_create found them (smr_tuning.hpp)
   explicit smr_ctx(const Tuning& t) : tune(t) {}
@@ -224,6 +237,7 @@ struct smr_ctx {
   FxSplitScratch fxs;
   RowsScratch rows;
   PairScratch pair;
+  OtuScratch otu;
 };
 struct KpSave { double ms[KP_COUNT]; uint64_t l[KP_COUNT]; };
 
@@ -864,6 +878,7 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
 #include "smr_engine_fxsplit.hpp"
 #include "smr_engine_rows.hpp"
 #include "smr_engine_pairwise.hpp"
+#include "smr_engine_otu.hpp"
 extern "C" int smr_counters(smr_ctx* c, uint64_t* out, uint32_t n_db) {
   if (!c || !out) return SMR_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));

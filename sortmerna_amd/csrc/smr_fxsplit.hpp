@@ -154,6 +154,87 @@ __global__ void __launch_bounds__(FXS_BLOCK) k_fxs_measure(uint32_t n_log, FxsOp
   }
 }
 
+// ---- aligned_denovo.* (smr_fastx_denovo): the same measuring, another predicate and another table; k_fxs_scan and k_fxs_copy serve both ----
+// is logical record p a de novo read: n_denovo > 0 and the other three counters 0 (is_dn of smr_report.cpp), or what the caller's bytes say
+__device__ __forceinline__ bool fxs_dn(const FxsOpts& o, const uint32_t* __restrict__ ic_a, const uint32_t* __restrict__ ic_b, const uint8_t* __restrict__ dn, uint32_t n_a, uint32_t p) {
+  const bool second = o.layout == 2u && (p & 1u);
+  const uint32_t i = o.layout == 2u ? p >> 1 : p;
+  if (dn) return dn[second ? n_a + i : i] != 0;
+  const uint32_t* const ic = second ? ic_b : ic_a;
+  if (!ic) return false;                                          // (the pass never ran on the batch)
+  const uint4 v = *reinterpret_cast<const uint4*>(ic + 4 * (size_t)i);
+  return v.w > 0u && v.x == 0u && v.y == 0u && v.z == 0u;
+}
+// smr_report_add (layout 0) / the aligned_denovo table of smr_report_add_pair (ReportDenovo::append): mate m, d: it is a de novo read, dm: its
+// mate is.  Two quirks of the reference under out2 are the table's, not this function's: under paired_out a pair of which one mate only is a
+// de novo read writes nothing; otherwise BOTH mates are written, the one that is no de novo read to file 0.
+__device__ __forceinline__ uint32_t fxs_route_dn(const FxsOpts& o, uint32_t m, bool d, bool dm) {
+  if (o.layout == 0u) return d ? 0u : FXS_NONE;
+  if (!d && !dm) return FXS_NONE;
+  const bool both = d && dm;
+  const uint32_t num_out = (o.out2 && o.sout) ? 4u : (o.out2 || o.sout) ? 2u : 1u;
+  if (num_out == 1u) return (o.paired_in || d) ? 0u : FXS_NONE;
+  if (num_out == 2u && o.out2) { if (o.paired_out && !both) return FXS_NONE; return (o.paired_in || d) ? m : 0u; }
+  if (num_out == 2u) return both ? 0u : d ? 1u : FXS_NONE;
+  return both ? m : d ? m + 2u : FXS_NONE;
+}
+
+// k_fxs_measure with fxs_dn / fxs_route_dn: rec[], woff[] and part[][8] as there, the streams 0..3 only
+__global__ void __launch_bounds__(FXS_BLOCK) k_fxs_dn_measure(uint32_t n_log, FxsOpts o, FxsSrc a, FxsSrc b, const uint32_t* __restrict__ ic_a, const uint32_t* __restrict__ ic_b,
+                                                              const uint8_t* __restrict__ dn, uint4* __restrict__ rec, unsigned long long* __restrict__ woff,
+                                                              unsigned long long* __restrict__ part) {
+  __shared__ unsigned long long s_w[4][16];
+  const uint32_t p = blockIdx.x * FXS_BLOCK + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  uint32_t stream = FXS_NONE;
+  unsigned long long size = 0ull;
+  if (p < n_log) {
+    const bool second = o.layout == 2u && (p & 1u);
+    const uint32_t i = o.layout == 2u ? p >> 1 : p;
+    const uint8_t* const text = second ? b.text : a.text;
+    const uint32_t n = second ? b.n : a.n;
+    const uint32_t h0 = (uint32_t)(second ? b.hoff : a.hoff)[i], s0 = (uint32_t)(second ? b.soff : a.soff)[i], len = (second ? b.len : a.len)[i];
+    const uint32_t n_a = o.layout == 2u ? n_log >> 1 : n_log;                   // reads of the selected batch
+    const bool d = fxs_dn(o, ic_a, ic_b, dn, n_a, p);
+    const bool dm = o.layout != 0u && fxs_dn(o, ic_a, ic_b, dn, n_a, p ^ 1u);
+    stream = fxs_route_dn(o, p & 1u, d, dm);
+    uint32_t hl = 0, ql = 0, qoff = 0, flags = 0;
+    if (stream != FXS_NONE) {                                                   // (few reads are de novo reads: the others' text is not looked at)
+      hl = fxs_rtrim(text, h0, fxs_find_nl(text, n, h0)) - h0;
+      size = (unsigned long long)hl + 1ull + len + 1ull;
+      if (o.fastq) {
+        const uint32_t plus = min(fxs_find_nl(text, n, s0 + len) + 1u, n);
+        qoff = min(fxs_find_nl(text, n, plus) + 1u, n);
+        ql = fxs_rtrim(text, qoff, fxs_find_nl(text, n, qoff)) - qoff;
+        size += 2ull + ql + 1ull;
+      } else if (len) {
+        const uint32_t e = fxs_find_nl(text, n, s0);
+        if (fxs_rtrim(text, s0, e) - s0 != len) flags = FXS_WRAPPED | FXS_WIDE;
+      }
+      if (size > FXS_SHORT) flags |= FXS_WIDE;
+    }
+    rec[p] = make_uint4(hl, ql, qoff, stream | flags);
+  }
+  unsigned long long mine = 0ull;
+#pragma unroll
+  for (uint32_t k = 0; k < 4u; k++) {
+    const unsigned long long incl = exp_wave_scan(stream == k ? size : 0ull);
+    if (lane == 63u) s_w[k][wv] = incl;
+    if (stream == k) mine = incl;
+  }
+  __syncthreads();
+  if (p < n_log) {
+    unsigned long long before = 0ull;
+    if (stream < 4u) for (uint32_t q = 0; q < wv; q++) before += s_w[stream][q];
+    woff[p] = before + mine - size;
+  }
+  if (threadIdx.x < 8u) {
+    unsigned long long all = 0ull;
+    if (threadIdx.x < 4u) for (uint32_t q = 0; q < FXS_BLOCK / 64u; q++) all += s_w[threadIdx.x][q];
+    part[(size_t)blockIdx.x * 8u + threadIdx.x] = all;
+  }
+}
+
 // part[b][k] -> the bytes of stream k in the blocks in front of b; tot[k] = where stream k starts, tot[8] = all bytes
 __global__ void __launch_bounds__(FXS_BLOCK) k_fxs_scan(unsigned long long* __restrict__ part, uint32_t np, unsigned long long* __restrict__ tot) {
   __shared__ unsigned long long s_w[16];

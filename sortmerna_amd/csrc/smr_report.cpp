@@ -9,6 +9,10 @@
 //   %id / mismatches / gaps    Read::calc_miss_gap_match          read.cpp:547-589
 //   aligned_denovo.fa|fq       ReportDenovo::append               report_denovo.cpp:57-134 (which reads: output.cpp:133-143)
 //   otu_map.txt                fill_otu_map2 / OtuMap::write      otumap.cpp:72-105, 131-281
+// The same outputs from streams the device wrote (smr_engine_*.hpp), each with a switch that makes smr_report_add leave that output alone:
+//   smr_report_add_fastx / _add_rows / _add_pairwise   aligned.* and other.*, the SAM and BLAST tabular rows, the BLAST pairwise text
+//   smr_report_add_otu         the groups of smr_otu_part, appended to the map entries of their (index, part)
+//   smr_report_add_denovo      the four aligned_denovo.* streams of smr_fastx_denovo
 // Input per read: the original header line, letters, quality and the Read::toBinString record (read.cpp:429-462) that
 // smr_result_record returns.  Rows are buffered per (index, part) and written in that order, like the reference's loop.
 #include <algorithm>
@@ -100,6 +104,8 @@ struct smr_report {
   bool skip_fx = false;                                                // smr_report_skip_fastx: aligned.* / other.* come from smr_report_add_fastx
   bool skip_rows = false;                                              // smr_report_skip_rows: the SAM and BLAST tabular rows come from smr_report_add_rows
   bool skip_pair = false;                                              // smr_report_skip_pairwise: the BLAST pairwise text comes from smr_report_add_pairwise
+  bool skip_otu = false;                                               // smr_report_skip_otu: the map entries come from smr_report_add_otu
+  bool skip_dn = false;                                                // smr_report_skip_denovo: aligned_denovo.* come from smr_report_add_denovo
 };
 
 extern "C" int smr_report_open(const char* out_dir, const smr_report_opts* opts, int is_fastq, smr_report** out, char* err, size_t errcap) {
@@ -166,8 +172,8 @@ extern "C" int smr_report_add(smr_report* r, const char* header, const char* seq
   uint32_t ic[4];
   if (!parse_record(record, record_len, is_hit, alns, ic)) { r->err = "malformed record"; return SMR_ERR_ARG; }
   if (!r->skip_fx) write_fx(r, is_hit ? r->f_aligned[0] : r->f_other[0], header, seq, qual);
-  if (r->o.denovo && is_dn(ic)) write_fx(r, r->f_denovo[0], header, seq, qual);
-  if (r->o.otu_map) { const int rc = add_otu(r, header, seq, alns, ic); if (rc != SMR_OK) return rc; }
+  if (r->o.denovo && !r->skip_dn && is_dn(ic)) write_fx(r, r->f_denovo[0], header, seq, qual);
+  if (r->o.otu_map && !r->skip_otu) { const int rc = add_otu(r, header, seq, alns, ic); if (rc != SMR_OK) return rc; }
   return add_rows(r, header, seq, qual, alns);
 }
 
@@ -204,7 +210,7 @@ extern "C" int smr_report_add_pair(smr_report* r, const char* header1, const cha
     }
   }
   // aligned_denovo.* (ReportDenovo::append, report_denovo.cpp:57-134): called when either mate is a de novo read (output.cpp:133-143)
-  if (o.denovo && (is_dn(ic[0]) || is_dn(ic[1]))) {
+  if (o.denovo && !r->skip_dn && (is_dn(ic[0]) || is_dn(ic[1]))) {
     const bool dn[2] = {is_dn(ic[0]), is_dn(ic[1])}, both_dn = dn[0] && dn[1];
     for (int i = 0; i < 2; i++) {
       int idx = 0;
@@ -216,7 +222,7 @@ extern "C" int smr_report_add_pair(smr_report* r, const char* header1, const cha
     }
   }
   for (int i = 0; i < 2; i++) {
-    if (o.otu_map) { const int rc = add_otu(r, hd[i], sq[i], alns[i], ic[i]); if (rc != SMR_OK) return rc; }
+    if (o.otu_map && !r->skip_otu) { const int rc = add_otu(r, hd[i], sq[i], alns[i], ic[i]); if (rc != SMR_OK) return rc; }
     const int rc = add_rows(r, hd[i], sq[i], ql[i], alns[i]); if (rc != SMR_OK) return rc;
   }
   return SMR_OK;
@@ -275,6 +281,72 @@ extern "C" int smr_report_skip_pairwise(smr_report* r, int on) {
 extern "C" int smr_report_skip_fastx(smr_report* r, int on) {
   if (!r) return SMR_ERR_ARG;
   r->skip_fx = on != 0;
+  return SMR_OK;
+}
+extern "C" int smr_report_add_otu(smr_report* r, uint32_t index_num, uint32_t part, const uint8_t* bytes, uint64_t n_bytes, const smr_otu_group* groups,
+                                  uint64_t n_groups, int any_yid_ycov) {
+  if (!r) return SMR_ERR_ARG;
+  if (!r->o.otu_map) { r->err = "smr_report_add_otu: the report was not opened with otu_map"; return SMR_ERR_ARG; }
+  const std::pair<uint32_t, uint32_t> key{index_num, part};
+  auto pit = r->parts.find(key);
+  if (pit == r->parts.end()) { r->err = "smr_report_add_otu: the (index, part) was not registered"; return SMR_ERR_ARG; }
+  if (n_groups && (!groups || (n_bytes && !bytes))) { r->err = "smr_report_add_otu: groups without their table or their bytes"; return SMR_ERR_ARG; }
+  // every group is looked at before one is appended
+  uint64_t n_members = 0;
+  for (uint64_t g = 0; g < n_groups; g++) {
+    const uint64_t b = groups[g].off, e = g + 1 < n_groups ? groups[g + 1].off : n_bytes;
+    if (e < b || e > n_bytes) { r->err = "smr_report_add_otu: the offsets decrease or run past the bytes"; return SMR_ERR_ARG; }
+    if (groups[g].n_reads == 0) { r->err = "smr_report_add_otu: a group without members"; return SMR_ERR_ARG; }
+    const uint64_t tabs = (uint64_t)std::count(bytes + b, bytes + e, (uint8_t)'\t');
+    if (tabs + 1 < groups[g].n_reads) { r->err = "smr_report_add_otu: a group with fewer ids than members"; return SMR_ERR_ARG; }
+    n_members += groups[g].n_reads;
+  }
+  const smr_index* ix = pit->second;
+  size_t first_seq = 0;
+  for (uint32_t q = 0; q < part && q < ix->parts.size(); q++) first_seq += ix->parts[q].numseq_part;
+  // add_otu appends in read order; the groups of one key may be appended group by group: smr_report_close gathers by reference id and
+  // keeps, within an id, the order of the entries -- which inside a group is the read order
+  auto& dst = r->otu[key];
+  dst.reserve(dst.size() + (size_t)n_members);
+  for (uint64_t g = 0; g < n_groups; g++) {
+    const uint64_t b = groups[g].off, e = g + 1 < n_groups ? groups[g + 1].off : n_bytes;
+    const std::string ref_id = first_seq + groups[g].ref_num < ix->sq_header.size() ? ix->sq_header[first_seq + groups[g].ref_num].first : std::string("*");
+    const char* t = reinterpret_cast<const char*>(bytes);
+    uint64_t at = b;
+    // (the text is cut at tabs: an id that holds one -- a header with a tab before its first space -- becomes adjacent pieces, the last member
+    // takes the rest; the file and the line count are those of smr_report_add, the entries are not the ids: smr_hip.h says so)
+    for (uint32_t k = 0; k < groups[g].n_reads; k++) {
+      uint64_t end = e;
+      if (k + 1 < groups[g].n_reads) { const void* q = memchr(t + at, '\t', (size_t)(e - at)); end = q ? (uint64_t)((const char*)q - t) : e; }
+      dst.emplace_back(ref_id, std::string(t + at, (size_t)(end - at)));
+      at = std::min(e, end + 1);
+    }
+  }
+  r->any_yid_ycov = r->any_yid_ycov || any_yid_ycov != 0;
+  return SMR_OK;
+}
+extern "C" int smr_report_skip_otu(smr_report* r, int on) {
+  if (!r) return SMR_ERR_ARG;
+  r->skip_otu = on != 0;
+  return SMR_OK;
+}
+extern "C" int smr_report_add_denovo(smr_report* r, const uint8_t* bytes, const uint64_t off[5]) {
+  if (!r || !off) return SMR_ERR_ARG;
+  for (int k = 0; k < 4; k++) {
+    if (off[k + 1] < off[k]) { r->err = "smr_report_add_denovo: the offsets decrease"; return SMR_ERR_ARG; }
+    if (off[k + 1] > off[k] && (!bytes || !r->f_denovo[k].is_open())) { r->err = "smr_report_add_denovo: stream " + std::to_string(k) + " is not empty and has no open file"; return SMR_ERR_ARG; }
+  }
+  for (int k = 0; k < 4; k++) {
+    for (uint64_t at = off[k]; at < off[k + 1];) {                     // (gzwrite takes an unsigned count)
+      const uint64_t take = std::min<uint64_t>(off[k + 1] - at, 1u << 30);
+      r->f_denovo[k].put(bytes + at, (size_t)take); at += take;
+    }
+  }
+  return SMR_OK;
+}
+extern "C" int smr_report_skip_denovo(smr_report* r, int on) {
+  if (!r) return SMR_ERR_ARG;
+  r->skip_dn = on != 0;
   return SMR_OK;
 }
 

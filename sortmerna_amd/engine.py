@@ -11,6 +11,10 @@ import numpy as np
 from . import capi
 
 
+# smr_otu_group of include/smr_hip.h
+OTU_GROUP = np.dtype([("ref_num", np.uint32), ("n_reads", np.uint32), ("off", np.uint64)])
+
+
 class SmrError(RuntimeError):
     pass
 
@@ -457,6 +461,56 @@ class Engine:
         ms = (C.c_double * 4)()
         self._chk(self.L.smr_pairwise_times(self.h, ms), "smr_pairwise_times")
         return dict(zip(("stats", "sizes", "write", "d2h"), (float(x) for x in ms)))
+
+    def otu_part(self, slot, params, index, min_id, min_cov):
+        """smr_otu_part: the members of otu_map.txt of the selected batch (uploaded with keep=True, after idcov_part of every part) for the
+        (index, part) of `params`, resident in `slot`, grouped and written on the device -> (bytes, groups, any): groups is a structured array
+        (ref_num, n_reads, off), ascending in ref_num; the text of group g is bytes[off[g]:off[g + 1]] (the last: to the end), its ids joined
+        by tabs; any: does a read of the batch have c_yid_ycov > 0 (is there a map file at all)"""
+        need = (C.c_uint64 * 2)()
+        any_ = C.c_int(0)
+        args = (self.h, slot, C.byref(params), index.h, float(min_id), float(min_cov))
+        self._chk(self.L.smr_otu_part(*args, None, 0, None, 0, need, C.byref(any_)), "smr_otu_part")
+        buf = np.zeros(max(need[0], 1), dtype=np.uint8)
+        groups = np.zeros(max(need[1], 1), dtype=OTU_GROUP)
+        if need[1]:
+            self._chk(self.L.smr_otu_part(*args, buf.ctypes.data, need[0], groups.ctypes.data, need[1], need, C.byref(any_)), "smr_otu_part")
+        return buf[:need[0]].tobytes(), groups[:need[1]], bool(any_.value)
+
+    def otu_times(self):
+        """HIP-event ms of the last otu_part: dict(classify, sizes, sort, write, d2h)"""
+        ms = (C.c_double * 5)()
+        self._chk(self.L.smr_otu_times(self.h, ms), "smr_otu_times")
+        return dict(zip(("classify", "sizes", "sort", "write", "d2h"), (float(x) for x in ms)))
+
+    def otu_sort_batch(self, keys, key_bits):
+        """smr_otu_sort_batch (a test seam): the stable permutation that sorts keys (each below 2 ** key_bits) ascending, found by the radix
+        sort of otu_part -> uint32 array"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        perm = np.zeros(max(len(keys), 1), dtype=np.uint32)
+        self._chk(self.L.smr_otu_sort_batch(self.h, len(keys), keys.ctypes.data if len(keys) else None, int(key_bits), perm.ctypes.data), "smr_otu_sort_batch")
+        return perm[:len(keys)]
+
+    def fastx_denovo(self, opts=None, mates=-1, dn=None, **kw):
+        """smr_fastx_denovo: the aligned_denovo.* FASTX streams of the selected batch (uploaded with keep=True), written on the device -> a list
+        of four bytes objects.  opts: a capi.FxSplitOpts, or a dict / keywords out of layout, paired_in, paired_out, out2, sout as fastx_split
+        takes them (want_aligned / want_other are ignored); mates: the batch of the mates under layout 2, else -1.  dn: one truth value per
+        read (the selected batch's, then the mates') used instead of the counters idcov_part left"""
+        if isinstance(opts, capi.FxSplitOpts):
+            o = opts
+        else:
+            d = dict(opts or {}, **kw)
+            o = capi.FxSplitOpts(int(d.get("layout", 0)), int(bool(d.get("paired_in"))), int(bool(d.get("paired_out"))), int(bool(d.get("out2"))), int(bool(d.get("sout"))), 1, 0)
+        db = None if dn is None else (C.c_uint8 * max(len(dn), 1))(*[1 if x else 0 for x in dn])
+        m = -1 if mates is None else int(mates)
+        off = (C.c_uint64 * 5)()
+        need = C.c_uint64(0)
+        self._chk(self.L.smr_fastx_denovo(self.h, m, C.byref(o), db, None, 0, off, C.byref(need)), "smr_fastx_denovo")
+        buf = (C.c_uint8 * max(need.value, 1))()
+        if need.value:
+            self._chk(self.L.smr_fastx_denovo(self.h, m, C.byref(o), db, buf, need.value, off, C.byref(need)), "smr_fastx_denovo")
+        raw = bytes(buf)
+        return [raw[off[k]:off[k + 1]] for k in range(4)]
 
     def rows_fmt_batch(self, num, den):
         """smr_rows_fmt_batch (a test seam): the device's `%.3g` of 100 * num[i] / den[i] -> list of str"""

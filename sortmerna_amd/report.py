@@ -2,8 +2,10 @@
 from the per-read records -- the reference's writeReports() pass (output.cpp:169-272)."""
 import ctypes as C
 
+import numpy as np
+
 from . import capi
-from .engine import SmrError
+from .engine import OTU_GROUP, SmrError
 
 
 def corrected_sizes(K, info, all_reads_count, all_reads_len, full_read_scale=1):
@@ -92,6 +94,29 @@ class Report:
     def skip_pairwise(self, on=True):
         """add / add_pair leave the BLAST pairwise text alone: add_pairwise brings it (smr_report_skip_pairwise)"""
         self._chk(self.L.smr_report_skip_pairwise(self.h, int(bool(on))), "smr_report_skip_pairwise")
+
+    def add_otu(self, index_num, part, data, groups, any_yid_ycov):
+        """the result of Engine.otu_part appended to the report's OTU map entries of (index_num, part) (smr_report_add_otu)"""
+        data = bytes(data)
+        g = np.ascontiguousarray(groups, dtype=OTU_GROUP)
+        self._chk(self.L.smr_report_add_otu(self.h, index_num, part, data if data else None, len(data), g.ctypes.data if len(g) else None, len(g), int(bool(any_yid_ycov))),
+                  "smr_report_add_otu")
+
+    def skip_otu(self, on=True):
+        """add / add_pair leave the OTU map alone: add_otu brings it (smr_report_skip_otu)"""
+        self._chk(self.L.smr_report_skip_otu(self.h, int(bool(on))), "smr_report_skip_otu")
+
+    def add_denovo(self, streams):
+        """the four streams of Engine.fastx_denovo appended to the open aligned_denovo.* files (smr_report_add_denovo)"""
+        off = (C.c_uint64 * 5)()
+        for k in range(4):
+            off[k + 1] = off[k] + len(streams[k])
+        blob = b"".join(streams)
+        self._chk(self.L.smr_report_add_denovo(self.h, blob if blob else None, off), "smr_report_add_denovo")
+
+    def skip_denovo(self, on=True):
+        """add / add_pair leave aligned_denovo.* alone: add_denovo writes them (smr_report_skip_denovo)"""
+        self._chk(self.L.smr_report_skip_denovo(self.h, int(bool(on))), "smr_report_skip_denovo")
 
     def merge_otu_from(self, other):
         """the OTU map entries of `other` (the next shard of the reads, in input order) behind this report's; `other` then writes no map"""
