@@ -561,6 +561,26 @@ typedef struct {
 } smr_sw16_task;
 int smr_sw16_batch(smr_ctx*, uint32_t n_tasks, const smr_sw16_task* tasks, const uint8_t* ref, uint64_t ref_len, int force_any_n,
                    int match, int mismatch, int score_N, int gap_open, int gap_ext, uint32_t filters, int rows, uint32_t blocks, int32_t* out);
+/* The PREFIX tasks of k_sw16 at the same seam (the kernel's third list): task i scores only the first `cols` columns of its window and returns an
+ * interval that holds the score of the whole window: out[2 i ..] = {lo, hi}, lo = the best score over those columns, hi = max(lo, s min(m, rem),
+ * max over the rows i < m of (best score of row i over those columns + s min(m - 1 - i, rem))) with rem = nref - cols and
+ * s = max(match, mismatch, score_N, 0).  Everything else as smr_sw16_batch; SMR_ERR_ARG also for cols = 0, cols not a multiple of 4 (the kernel's
+ * period of four columns) and cols >= nref. */
+typedef struct {
+  uint32_t read, win_off;
+  uint16_t aq, m, nref, cols;
+  uint8_t reversed, pad_[3];
+} smr_sw16_prefix_task;
+int smr_sw16_prefix_batch(smr_ctx*, uint32_t n_tasks, const smr_sw16_prefix_task* tasks, const uint8_t* ref, uint64_t ref_len, int force_any_n,
+                          int match, int mismatch, int score_N, int gap_open, int gap_ext, int rows, uint32_t blocks, int32_t* out);
+/* How the candidate walk uses prefix tasks, since smr_prof_reset.  Under best N (N > 0) a look-ahead task of a read that is expected to align is
+ * scored over the first SMR_WALK_PREFIX per cent of its window's columns (default 44, 0 = off): the interval decides the task when it lies above
+ * the minimal score, below the highest possible score and not above the lowest stored score of a read whose N slots are full -- the walk then
+ * does with it what it does with every score inside; otherwise the task is scored again in full.  Records never depend on the switch.
+ * out[0] prefix tasks scored, [1] consumed decisively, [2] met undecided and scored again, [3] never looked at; [4] / [5] the look-ahead tasks
+ * (and their cells) of reads expected to align under best N, whatever the mode; [6] the switch as the context latched it; [7] 1 while the context leaves prefix tasks, 0 while it has stopped: after a part that met
+ * fewer than two decided intervals per undecided one it leaves none for the next 64 parts, then tries again. */
+int smr_walk_prefix_stats(smr_ctx*, uint64_t out[8]);
 /* Launches of k_sw16<13 | 19 | 26 | 32> since smr_create: out[0..3] by the rounds of the candidate walk, out[4..7] by the begin-cell stage
  * (which instantiation a batch gets follows from its longest read; a batch that never takes the walk path counts nothing). */
 int smr_sw16_launches(const smr_ctx*, uint64_t out[8]);

@@ -218,6 +218,8 @@ struct smr_ctx {
   // rounds per (strand, pass): without SMR_WALK_ROUNDS the number adapts to what the previous part needed (the last round with more than a few
   // reads listed + the closing one: an empty round still costs three launches, ~70 us of stream time; 8 -> 4 rounds = 3 % of the bench step)
   uint32_t walk_need[3] = {0, 0, 0};
+  DevBuf<unsigned long long> d_wpstat;     // WPS_N counters of the prefix tasks since smr_prof_reset (smr_walk_prefix_stats)
+  bool pfx_live = true; uint32_t pfx_parts_off = 0; unsigned long long pfx_seen[2] = {0, 0};      // adapt_walk_prefix: the mode as the last part's intervals left it; parts since it went off; decided / redone at the last look
   DevBuf<unsigned long long> d_wstat; uint32_t wstat_n = 0; int wstat_pass[8] = {}; uint32_t wstat_rm[8] = {};
   DevBuf<int> d_bound;                                                 // strip-boundary rows of the SW kernels (reads of more than one strip), per block
   DevBuf<uint32_t> d_tasks;                                            // two lists of reads x slots entries
@@ -858,6 +860,7 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
     if ((rc = judge_attempt(c, P, h, retry))) return rc;
     if (retry) { kp_restore(c, kp0); continue; }              // (the timings of a discarded attempt go with it)
     if ((rc = adapt_walk_rounds(c))) return rc;
+    if ((rc = adapt_walk_prefix(c))) return rc;
     if ((rc = launch_begins(c, di, P, plan))) return rc;
     // only a clean attempt is committed to the persistent per-read state (kvdb.put, processor.cpp:150-155)
     launch(c, k_commit_part, dim3((c->b->n + 255u) / 256u), dim3(256), 0, c->b->n, P, c->b->d_saved, c->b->d_saved_aln, c->b->d_work, c->b->d_work_aln, c->b->d_rw);
@@ -1160,6 +1163,7 @@ extern "C" int smr_prof_reset(smr_ctx* c) {
   HIPCHK(c, hipSetDevice(c->device));
   for (int k = 0; k < KP_COUNT; k++) { c->kp_ms[k] = 0; c->kp_l[k] = 0; }
   c->n_seed_shared = c->n_seed_shared_builds = 0;
+  if (c->d_wpstat) HIPCHK(c, hipMemsetAsync(c->d_wpstat, 0, WPS_N * 8, c->stream));
   for (int k = 0; k < SMR_MAX_BATCHES; k++)
     if (c->bt[k].d_ctr) {
       HIPCHK(c, hipMemsetAsync(&c->bt[k].d_ctr[C_WINDOWS], 0, 9 * 8, c->stream));

@@ -62,10 +62,10 @@ begins_fn begins_kernel(bool lng, bool striped) {
 // test seam); blocks 0: what fills the device
 typedef decltype(&k_sw16<13>) sw16_fn;
 void launch_sw16(smr_ctx* c, int rows, int counted, uint32_t blocks, const DReads& rd, const DIndex& ix, const DParams& P, const WTask* tasks, const uint32_t* tix, const uint32_t* tix2,
-                 const unsigned long long* wc, uint2* res) {
+                 const uint32_t* tix3, const unsigned long long* wc, uint2* res) {
   static const sw16_fn K[4] = {k_sw16<13>, k_sw16<19>, k_sw16<26>, k_sw16<32>};
   const int v = rows == 13 ? 0 : rows == 19 ? 1 : rows == 26 ? 2 : 3;
-  launch(c, K[v], dim3(blocks ? blocks : (uint32_t)c->n_cu * 4u * (uint32_t)SW16_WAVES(rows)), dim3(64), 0, rd, ix, P, tasks, tix, tix2, wc, res);
+  launch(c, K[v], dim3(blocks ? blocks : (uint32_t)c->n_cu * 4u * (uint32_t)SW16_WAVES(rows)), dim3(64), 0, rd, ix, P, tasks, tix, tix2, tix3, wc, res);
   if (counted >= 0) c->sw16_launches[counted + v]++;
 }
 
@@ -96,6 +96,29 @@ int adapt_walk_rounds(smr_ctx* c) {
   return SMR_OK;
 }
 
+// After a part (the stream is idle): did its prefix tasks pay?  An undecided interval is a window scored twice and a read listed for one more round,
+// so data whose scores lie close together (real amplicon reads against references clustered at 95 % identity) loses by the mode what families of
+// distant members win.  The context stops leaving prefix tasks when a part met fewer than two decided intervals per undecided one, and tries
+// again WALK_PREFIX_RETRY parts later (the parts of a run differ: eight databases, batches of a mixed sample).  Only which windows are scored
+// over a prefix depends on it, never a record.
+#define WALK_PREFIX_RETRY 64u
+#define WALK_PREFIX_MIN_SEEN 64ull                       // intervals consumed in a part before it says anything
+int adapt_walk_prefix(smr_ctx* c) {
+  if (!c->tune.walk_prefix || !c->d_wpstat) return SMR_OK;
+  if (!c->pfx_live) { if (++c->pfx_parts_off >= WALK_PREFIX_RETRY) { c->pfx_live = true; c->pfx_parts_off = 0; } return SMR_OK; }
+  unsigned long long h[WPS_N];
+  HIPCHK(c, hipMemcpyAsync(h, c->d_wpstat, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (h[WPS_DECIDED] < c->pfx_seen[0] || h[WPS_REDONE] < c->pfx_seen[1]) c->pfx_seen[0] = c->pfx_seen[1] = 0;      // (smr_prof_reset in between)
+  const unsigned long long dec = h[WPS_DECIDED] - c->pfx_seen[0], redo = h[WPS_REDONE] - c->pfx_seen[1];
+  c->pfx_seen[0] = h[WPS_DECIDED]; c->pfx_seen[1] = h[WPS_REDONE];
+  if (dec + redo >= WALK_PREFIX_MIN_SEEN && dec < 2 * redo) {
+    c->pfx_live = false; c->pfx_parts_off = 0;
+    say(c->tune, "prefix tasks off for %u parts: %llu intervals decided, %llu undecided in the last part\n", WALK_PREFIX_RETRY, dec, redo);
+  }
+  return SMR_OK;
+}
+
 int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, const AlignPlan& plan, int pass, int is_last_strand) {
   Batch& B = *c->b;
   const uint32_t ml = plan.ml, rf = plan.rf, rq = plan.rq;
@@ -123,14 +146,15 @@ int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, const AlignPl
     if (c->walk_cap < n || c->walk_kcap < WK) {
       for (int q = 0; q < 2; q++)
         if ((rc = c->d_wlist[q].alloc(c, n)) || (rc = c->d_wstate[q].alloc(c, n)) || (rc = c->d_wtask[q].alloc(c, n * WK)) || (rc = c->d_wres[q].alloc(c, n * WK))) return rc;
-      if ((rc = c->d_wtidx.alloc(c, 2 * n * WK)) || (rc = c->d_wslow.alloc(c, n))) return rc;
+      if ((rc = c->d_wtidx.alloc(c, 3 * n * WK)) || (rc = c->d_wslow.alloc(c, n))) return rc;
       c->walk_cap = n; c->walk_kcap = WK;
     }
     if ((rc = c->d_wctr.reserve(c, (size_t)(RMX + 2) * WC_STRIDE)) || (rc = c->d_wstat.reserve(c, (size_t)8 * 32))) return rc;      // (RMX is the context's: made once)
     HIPCHK(c, hipMemsetAsync(c->d_wctr, 0, (size_t)(RMX + 2) * WC_STRIDE * 8, c->stream));
+    if (!c->d_wpstat) { if ((rc = c->d_wpstat.alloc(c, WPS_N))) return rc; HIPCHK(c, hipMemsetAsync(c->d_wpstat, 0, WPS_N * 8, c->stream)); }
     if ((rc = raise_lds_limit(c, c->walk_lds_attr, (size_t)wml + rq, 64 * 1024, k_walk<true>))) return rc;
   }
-  const size_t n_tix = (size_t)c->walk_cap * c->walk_kcap;     // the second half of d_wtidx: the score-only tasks
+  const size_t n_tix = (size_t)c->walk_cap * c->walk_kcap;     // the second third of d_wtidx: the score-only tasks, the last third: the prefix tasks
   unsigned long long* const n_slow = split ? c->d_wctr + (size_t)(RMX + 1) * WC_STRIDE : nullptr;
   const dim3 per_read((B.n + 255u) / 256u);
   ev_mark(c, KP_CAND);
@@ -150,10 +174,11 @@ int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, const AlignPl
       ev_mark(c, KP_WALK);
       launch(c, fin ? k_walk<true> : k_walk<false>, dim3(fin ? walk_blocks * 3u / SMR_WALK_WAVES_PER_SIMD : walk_blocks), dim3(64), fin ? (size_t)wml + rq : 0,
              dreads(c), dindex(di), P, pass, is_last_strand, B.d_work, B.d_work_aln, B.d_rw, B.d_ctr, mrec, c->d_mpool, c->d_pool, c->d_wlist[cur],
-             c->d_wstate[prv], c->d_wtask[prv], c->d_wres[prv], c->d_wstate[cur], c->d_wtask[cur], c->d_wtidx, c->d_wtidx + n_tix, wc, WK, n_tix, (int)rnd, wml, rq, c->tune.walk_assume);
+             c->d_wstate[prv], c->d_wtask[prv], c->d_wres[prv], c->d_wstate[cur], c->d_wtask[cur], c->d_wtidx, c->d_wtidx + n_tix, c->d_wtidx + 2 * n_tix, wc, WK, n_tix, (int)rnd, wml, rq, c->tune.walk_assume,
+             c->pfx_live ? c->tune.walk_prefix : 0u, c->d_wpstat);
       if (fin) continue;
       ev_mark(c, KP_SW16);
-      launch_sw16(c, plan.rows, 0, 0, dreads(c), dindex(di), P, c->d_wtask[cur], c->d_wtidx, c->d_wtidx + n_tix, wc, c->d_wres[cur]);
+      launch_sw16(c, plan.rows, 0, 0, dreads(c), dindex(di), P, c->d_wtask[cur], c->d_wtidx, c->d_wtidx + n_tix, c->d_wtidx + 2 * n_tix, wc, c->d_wres[cur]);
       ev_mark(c, KP_WNEXT);
       launch(c, k_wnext, dim3((uint32_t)c->n_cu * 2u), dim3(1024), 0, P, is_last_strand, B.d_work, B.d_rw, B.d_ctr, c->d_wlist[cur], c->d_wstate[cur],
              c->d_wres[cur], c->d_wlist[prv], wc, wc + WC_STRIDE, WK, n_tix, (int)rnd);
@@ -168,8 +193,13 @@ int launch_chain(smr_ctx* c, const DevIndex& di, const DParams& P, const AlignPl
       HIPCHK(c, hipStreamSynchronize(c->stream));
       { const unsigned long long* q = &h[(size_t)(RMX + 1) * WC_STRIDE];
         fprintf(stderr, "libsmr_hip: walk rounds (pass %d): slow %llu (positions <= 64 / 128 / 256 / 512 / more / > 64 hits: %llu %llu %llu %llu %llu %llu);", pass, q[0], q[8], q[9], q[10], q[11], q[12], q[13]); }
-      for (uint32_t rnd = 0; rnd < RM; rnd++) fprintf(stderr, " %llu/%llu+%llu", h[(size_t)rnd * WC_STRIDE + WC_NLIST], h[(size_t)rnd * WC_STRIDE + WC_NTASK], h[(size_t)rnd * WC_STRIDE + WC_NTASK2]);
+      for (uint32_t rnd = 0; rnd < RM; rnd++) fprintf(stderr, " %llu/%llu+%llu+%llu", h[(size_t)rnd * WC_STRIDE + WC_NLIST], h[(size_t)rnd * WC_STRIDE + WC_NTASK], h[(size_t)rnd * WC_STRIDE + WC_NTASK2], h[(size_t)rnd * WC_STRIDE + WC_NTASK3]);
       fprintf(stderr, "\n");
+      unsigned long long ps[WPS_N];                         // (since smr_prof_reset, all launches of the context)
+      HIPCHK(c, hipMemcpyAsync(ps, c->d_wpstat, sizeof ps, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      fprintf(stderr, "libsmr_hip: prefix tasks so far (SMR_WALK_PREFIX=%u): scored %llu decided %llu redone %llu; look-ahead tasks of reads expected to align under best N %llu, their cells %llu\n",
+              c->tune.walk_prefix, ps[WPS_SCORED], ps[WPS_DECIDED], ps[WPS_REDONE], ps[WPS_AHEAD], ps[WPS_AHEAD_CELLS]);
     }
   }
   ev_mark(c, KP_CHAIN);
@@ -207,7 +237,7 @@ int launch_begins(smr_ctx* c, const DevIndex& di, const DParams& P, const AlignP
     for (int stage = 0; stage < 2; stage++) {
       HIPCHK(c, hipMemsetAsync(c->d_wctr, 0, (size_t)WC_STRIDE * 8, c->stream));
       launch(c, k_begins_prep, dim3((uint32_t)c->n_cu * 2u), dim3(1024), 0, dindex(di), B.slots, c->d_tasks, &B.d_ctr[C_BEGIN_N], B.d_work_aln, stage, c->d_wtask[0], c->d_wtidx, c->d_wctr);
-      launch_sw16(c, plan.rows, 4, 0, dreads(c), dindex(di), P, c->d_wtask[0], c->d_wtidx, c->d_wtidx + task_cap, c->d_wctr, c->d_wres[0]);
+      launch_sw16(c, plan.rows, 4, 0, dreads(c), dindex(di), P, c->d_wtask[0], c->d_wtidx, c->d_wtidx + task_cap, c->d_wtidx + 2 * task_cap, c->d_wctr, c->d_wres[0]);
       launch(c, k_begins_apply, dim3((uint32_t)c->n_cu * 4u), dim3(256), 0, c->d_tasks, &B.d_ctr[C_BEGIN_N], B.d_work_aln, stage, c->d_wtask[0], c->d_wres[0], B.d_ctr);
     }
   } else

@@ -290,7 +290,7 @@ extern "C" int smr_sw16_batch(smr_ctx* c, uint32_t n_tasks, const smr_sw16_task*
   if (!ib.empty()) HIPCHK(c, hipMemcpyAsync(d_ib, ib.data(), ib.size() * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_wc, wc, sizeof wc, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(d_res, 0xEE, (size_t)n_tasks * sizeof(uint2), c->stream));
-  launch_sw16(c, rows, -1, blocks, dreads(c), ix, P, d_tk, d_ia, d_ib, d_wc, d_res);
+  launch_sw16(c, rows, -1, blocks, dreads(c), ix, P, d_tk, d_ia, d_ib, d_ib, d_wc, d_res);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(res.data(), d_res, (size_t)n_tasks * sizeof(uint2), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -326,7 +326,7 @@ extern "C" int smr_sw16_batch(smr_ctx* c, uint32_t n_tasks, const smr_sw16_task*
   HIPCHK(c, hipMemcpyAsync(d_ia, beg.data(), beg.size() * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_wc, wc, sizeof wc, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(d_res, 0xEE, (size_t)n_tasks * sizeof(uint2), c->stream));
-  launch_sw16(c, rows, -1, blocks, dreads(c), ix, P, d_tk, d_ia, d_ib, d_wc, d_res);
+  launch_sw16(c, rows, -1, blocks, dreads(c), ix, P, d_tk, d_ia, d_ib, d_ib, d_wc, d_res);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(res.data(), d_res, (size_t)n_tasks * sizeof(uint2), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -336,6 +336,88 @@ extern "C" int smr_sw16_batch(smr_ctx* c, uint32_t n_tasks, const smr_sw16_task*
     const int b_ref = (int)(res[i].y >> 16) - 1, b_read = (int)(res[i].y & 0xFFFFu);
     o[1] = o[2] - b_ref; o[3] = o[4] - b_read;
   }
+  return SMR_OK;
+}
+
+// the prefix tasks of k_sw16 at the same seam: all tasks in the third list, each over the first `cols` columns of its window
+extern "C" int smr_sw16_prefix_batch(smr_ctx* c, uint32_t n_tasks, const smr_sw16_prefix_task* tasks, const uint8_t* ref, uint64_t ref_len, int force_any_n,
+                                     int match, int mismatch, int score_N, int gap_open, int gap_ext, int rows, uint32_t blocks, int32_t* out) {
+  if (!c || (n_tasks && (!tasks || !out)) || (ref_len && !ref)) return SMR_ERR_ARG;
+  if (rows != 13 && rows != 19 && rows != 26 && rows != 32) { set_err(c, "smr_sw16_prefix_batch: rows must be 13, 19, 26 or 32"); return SMR_ERR_ARG; }
+  if (blocks > 65536u) { set_err(c, "smr_sw16_prefix_batch: at most 65536 blocks"); return SMR_ERR_ARG; }
+  if (match <= 0 || match > 127 || mismatch > 0 || mismatch < -127 || score_N < -127 || gap_open < 0 || gap_open > 255 || gap_ext < 0 || gap_ext > 255) { set_err(c, "smr_sw16_prefix_batch: bad scoring options"); return SMR_ERR_ARG; }
+  if (const char* why = scheme_unsupported(mismatch, score_N, gap_open, gap_ext)) { set_err(c, why); return SMR_ERR_ARG; }
+  if (!c->b->used || !c->b->d_words) { set_err(c, "smr_sw16_prefix_batch: no reads uploaded into the selected batch"); return SMR_ERR_STATE; }
+  (void)hipSetDevice(c->device);
+  const uint32_t n_reads = c->b->n;
+  std::vector<uint32_t> len(n_reads);
+  if (n_reads) HIPCHK(c, hipMemcpyAsync(len.data(), c->b->d_len, (size_t)n_reads * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<WTask> tk(std::max<uint32_t>(n_tasks, 1));
+  std::vector<uint32_t> ic(std::max<uint32_t>(n_tasks, 1));
+  for (uint32_t i = 0; i < n_tasks; i++) {
+    const smr_sw16_prefix_task& t = tasks[i];
+    const char* why = nullptr;
+    if (t.read >= n_reads) why = "read index outside the batch";
+    else if (t.m == 0 || t.nref == 0) why = "empty span or window";
+    else if (t.m > WK_MAX_ROWS || (int)t.m > 8 * rows) why = "span longer than the kernel takes (8 x rows, at most WK_MAX_ROWS)";
+    else if ((uint64_t)t.aq + t.m > len[t.read]) why = "rows outside the read";
+    else if ((uint64_t)t.win_off + t.nref > ref_len) why = "window outside the reference letters";
+    else if (!sw_pk_fits((int)t.m, (int)t.nref, match, mismatch, score_N, gap_open)) why = "numbers outside the packed representation (sw_pk_fits)";
+    else if (t.reversed > 1) why = "reversed must be 0 or 1";
+    else if (t.cols == 0) why = "cols must not be 0";
+    else if (t.cols % 4u) why = "cols must be a multiple of 4 (the kernel's period)";
+    else if (t.cols >= t.nref) why = "cols must be less than nref";
+    if (why) { set_err(c, std::string("smr_sw16_prefix_batch: task ") + std::to_string(i) + ": " + why); return SMR_ERR_ARG; }
+    WTask o;
+    memset(&o, 0, sizeof o);
+    o.r = t.read; o.rf_start = t.win_off; o.aq = t.aq; o.m = t.m; o.nref = t.nref; o.flags = (uint16_t)((t.reversed ? 1u : 0u) | t.cols);
+    tk[i] = o; ic[i] = i;
+  }
+  if (n_tasks == 0) return SMR_OK;
+  DevPool pool;
+  IB_GET(d_ref, uint8_t, ref_len + 8); IB_GET(d_tk, WTask, n_tasks); IB_GET(d_ic, uint32_t, n_tasks);
+  IB_GET(d_wc, unsigned long long, WC_STRIDE); IB_GET(d_res, uint2, n_tasks);
+  HIPCHK(c, hipMemsetAsync(d_ref, 0, ref_len + 8, c->stream));
+  if (ref_len) HIPCHK(c, hipMemcpyAsync(d_ref, ref, ref_len, hipMemcpyHostToDevice, c->stream));
+  DIndex ix;
+  memset(&ix, 0, sizeof ix);
+  ix.ref_seq = d_ref;
+  ix.ref_any_n = (force_any_n || (ref_len && memchr(ref, 4, ref_len))) ? 1u : 0u;
+  DParams P;
+  memset(&P, 0, sizeof P);
+  P.match = match; P.mismatch = mismatch; P.score_N = score_N; P.gap_open = gap_open; P.gap_ext = gap_ext; P.sw_mode = c->sw_mode;
+  unsigned long long wc[WC_STRIDE] = {};
+  std::vector<uint2> res(n_tasks);
+  wc[WC_NTASK3] = n_tasks;
+  HIPCHK(c, hipMemcpyAsync(d_tk, tk.data(), (size_t)n_tasks * sizeof(WTask), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_ic, ic.data(), (size_t)n_tasks * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_wc, wc, sizeof wc, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(d_res, 0xEE, (size_t)n_tasks * sizeof(uint2), c->stream));
+  launch_sw16(c, rows, -1, blocks, dreads(c), ix, P, d_tk, d_ic, d_ic, d_ic, d_wc, d_res);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(res.data(), d_res, (size_t)n_tasks * sizeof(uint2), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (uint32_t i = 0; i < n_tasks; i++) {
+    if (res[i].y != WRES_PREFIX) { set_err(c, "smr_sw16_prefix_batch: a prefix task came back without an interval"); return SMR_ERR_DEVICE; }
+    out[2 * (size_t)i] = (int32_t)(res[i].x & 0xFFFFu); out[2 * (size_t)i + 1] = (int32_t)(res[i].x >> 16);
+  }
+  return SMR_OK;
+}
+
+// prefix tasks of the candidate walk since smr_prof_reset: out[0] left for k_sw16, [1] consumed decisively, [2] met undecided (left again in full),
+// [3] never looked at, [4] / [5] look-ahead tasks of reads expected to align under best N (whatever the mode) and their cells, [6] SMR_WALK_PREFIX as latched,
+// [7] 1 while the context leaves prefix tasks, 0 after a part whose intervals mostly stayed undecided (adapt_walk_prefix)
+extern "C" int smr_walk_prefix_stats(smr_ctx* c, uint64_t out[8]) {
+  if (!c || !out) return SMR_ERR_ARG;
+  unsigned long long h[WPS_N] = {};
+  if (c->d_wpstat) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(h, c->d_wpstat, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  out[0] = h[WPS_SCORED]; out[1] = h[WPS_DECIDED]; out[2] = h[WPS_REDONE]; out[3] = h[WPS_SCORED] - h[WPS_DECIDED] - h[WPS_REDONE];
+  out[4] = h[WPS_AHEAD]; out[5] = h[WPS_AHEAD_CELLS]; out[6] = c->tune.walk_prefix; out[7] = c->pfx_live ? 1 : 0;
   return SMR_OK;
 }
 

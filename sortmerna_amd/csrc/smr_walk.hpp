@@ -38,19 +38,27 @@ __host__ __device__ __forceinline__ uint32_t walk_tasks_per_read(uint32_t nlist,
 #define WK_CLAIM 24u                                      // list entries a wave claims at a time, at most (24 x WK_MAX task slots = 7 424 bytes of LDS for the kernel; with 32 it was 8 160 and the kernel 6 % slower, profiles/r5s33_*: fewer than the 20 waves per CU its registers allow)
 #endif
 // per-round counters (u64 words): every hot one on a 128-byte line of its own
-enum { WC_NLIST = 0, WC_CLAIM = 16, WC_NTASK = 32, WC_NTASK2 = 48, WC_STRIDE = 64 };
+enum { WC_NLIST = 0, WC_CLAIM = 16, WC_NTASK = 32, WC_NTASK2 = 48, WC_NTASK3 = 64, WC_STRIDE = 80 };
 
 struct WTask {                        // one Smith-Waterman task: read span x reference window (alignment.cpp:271-357)
   uint32_t r, max_ref;
   uint64_t rf_start;                  // where the window starts in ix.ref_seq
   uint32_t ars, head;                 // align_ref_start, head (what the walk needs besides the window when it resumes at this task)
   uint16_t aq, m, nref;               // align_que_start, read span, window length
-  uint16_t flags;                     // bit 0: the read is walked on its reverse-complement strand; bit 1: rows and columns run backwards from aq / rf_start (a begin-cell task)
+  uint16_t flags;                     // bit 0: the read is walked on its reverse-complement strand; bit 1: rows and columns run backwards from aq / rf_start (a begin-cell task);
+                                      // bits 2..15: a prefix task scores this many periods of four columns of its window (0 < 4 x that < nref)
 };
+#define WT_COLS(flags) (((uint32_t)(flags) >> 2) * 4u)
+#define WRES_PREFIX 0xFFFFFFFEu       // y of a prefix task's result: x = lo | hi << 16 (sw_quad16, SW16_PREFIX)
+// the columns a look-ahead task of a window of nref columns is scored over: `pct` per cent of them, rounded up to the kernel's period
+__host__ __device__ __forceinline__ uint32_t walk_prefix_cols(uint32_t nref, uint32_t pct) { return ((nref * pct + 99u) / 100u + 3u) & ~3u; }
+// what a context counts about prefix tasks since smr_prof_reset (smr_walk_prefix_stats): left for k_sw16, consumed decisively, met undecided (left
+// again in full); and -- whatever the mode -- the look-ahead tasks of reads expected to align under options that make them eligible, with their cells
+enum { WPS_SCORED = 0, WPS_DECIDED, WPS_REDONE, WPS_AHEAD, WPS_AHEAD_CELLS, WPS_N = 8 };
 struct WState {                       // the walk of a read standing AT the first task it had no result for (= task 0 of the tasks it left)
   uint32_t k, it, ms_lo, ms_hi, begin_ref, begin_read;
   int32_t best;                       // Walk::best there (also what the read ends with when nothing of its tasks aligns)
-  uint32_t bits;                      // 0 is_aligned, 1 go_on, 2 started, 3 pending_pop, 4 search, 5 look-ahead ended under "nothing aligns", 6 last result aligned, 8..11 tasks left
+  uint32_t bits;                      // 0 is_aligned, 1 go_on, 2 started, 3 pending_pop, 4 search, 5 look-ahead ended under "nothing aligns", 6 last result aligned, 7 no more prefix tasks for this read, 8..11 tasks left
   uint32_t cells;                     // DP cells of the tasks left
 };
 #define WS_NK(bits) (((bits) >> 8) & 15u)
@@ -108,15 +116,30 @@ struct __attribute__((aligned(4))) Sw16W2 { uint32_t a, b; };
 // KEYS = false: the score only (no running-maximum key per row: ten instead of thirteen instructions per cell pair, R registers less) -- for
 // the tasks of reads that are not expected to align (their result is "score <= minimal_score", nothing else is asked of it; when one aligns
 // after all, its end cell is found by k_begins)
-template <int R, bool HASN, bool KEYS>
+//
+// KEYS = SW16_PREFIX: a PREFIX task -- the caller passes n = cols, the first columns of a window of n + rem -- for a look-ahead task whose
+// exact score the walk does not need (k_walk, "decisive").  One packed running maximum per row pair, rmax[j] = max(rmax[j], h): eleven
+// instructions per cell pair, the R registers of the key variant.  With M_i = the maximum of H over row i of those columns and
+// s = max(match, mismatch, score_N, 0) the result is the interval
+//     lo = max_i M_i                        (the score of the prefix: what the score-only variant returns for n = cols)
+//     hi = max(lo, s min(m, rem), max_{i < m} (M_i + s min(m - 1 - i, rem)))
+// and lo <= score of the whole window <= hi.  lo: a prefix's cells are the window's own.  hi: an alignment that ends left of column cols
+// scores <= lo.  One that crosses into column cols leaves column cols - 1 at some row i with a prefix score <= H(i, cols - 1) <= M_i (an
+// open gap's E there is <= H), and each of the m - 1 - i rows below and of the rem columns to the right adds at most s: no cell gains more
+// than s, a gap gains nothing.  One that lies wholly in [cols, n + rem) has at most min(m, rem) scoring cells.
+// The steps past column cols - 1 (the wave runs to its longest problem) meet the selector NONE, and no value there exceeds its row's M_i:
+// H(i, c) <= M_i holds for a = H(i - 1, c - 1) - go because M_i >= M_{i-1} - go (the gap opened under M_{i-1}'s cell), for e because it
+// comes from row i, for f because M_i >= M_i' - go - (i - i' - 1) ge for every row i' above.  Rows >= m are left out of lo and hi.
+enum { SW16_SCORE = 0, SW16_KEYS = 1, SW16_PREFIX = 2 };
+template <int R, bool HASN, int KEYS>
 __device__ __forceinline__ SwRes sw_quad16(const uint32_t* __restrict__ rec, uint32_t len, uint32_t reversed, int m, int aq, const uint8_t* __restrict__ ref, int n,
-                                           int match, int mismatch, int scoreN, int go, int ge, int dir) {      // dir = 1, or -1: rows and columns run backwards from aq / ref (ssw_align's reverse pass)
+                                           int match, int mismatch, int scoreN, int go, int ge, int dir, int rem = 0) {      // rem: SW16_PREFIX only; dir = 1, or -1: rows and columns run backwards from aq / ref (ssw_align's reverse pass)
   const int gl = lane_id() & 3;
   const pk16 GE = pk_splat(ge), GO = pk_splat(go), ZERO = pk_splat(0);
   const uint32_t TN = (((uint32_t)(scoreN + go)) & 0xFFFFu) * 0x00010001u;
   uint32_t tlo[R], thi[R];
   pk16 Y[R], E[R];
-  uint32_t key[KEYS ? R : 1];
+  uint32_t key[KEYS ? R : 1];                               // (SW16_PREFIX: the rows' packed running maxima)
   pk16 hmax = ZERO;
   const uint32_t t_mm = ((uint32_t)(mismatch + go) & 0xFFu) * 0x01010101u, t_x = ((uint32_t)(mismatch + go) ^ (uint32_t)(match + go)) & 0xFFu,
                  t_n = ((uint32_t)(scoreN + go) & 0xFFu) * 0x01010101u;
@@ -144,9 +167,8 @@ __device__ __forceinline__ SwRes sw_quad16(const uint32_t* __restrict__ rec, uin
     uint32_t t2[2];
 #pragma unroll
     for (int hf = 0; hf < 2; hf++) {
-      const int row = (gl + 4 * hf) * R + j;
       uint32_t t = 0;
-      if (row < m) {
+      if (j < m - (gl + 4 * hf) * R) {                    // row (gl + 4 hf) R + j < m, asked of the task's number (a row index per j would be kept for the whole kernel)
         const int ph = pa[hf] + sgn * j;
         const int wi = (ph >> 4) - cw0[hf], ai = (ph >> 5) - aw0[hf];
         const uint32_t wd = wi == 0 ? cwd[hf][0] : wi == 1 ? cwd[hf][1] : cwd[hf][2];
@@ -193,7 +215,8 @@ __device__ __forceinline__ SwRes sw_quad16(const uint32_t* __restrict__ rec, uin
       diag = Y[j];                                                                                                          \
       const pk16 y = pk_sub(h, GO);                                                                                         \
       Y[j] = y; E[j] = e;                                                                                                   \
-      if (KEYS) { const uint32_t hu = pk_bits(h); key[j] = max(key[j], max((hu << 16) | xlo, (hu & 0xFFFF0000u) | xhi)); }  \
+      if (KEYS == SW16_KEYS) { const uint32_t hu = pk_bits(h); key[j] = max(key[j], max((hu << 16) | xlo, (hu & 0xFFFF0000u) | xhi)); } \
+      else if (KEYS == SW16_PREFIX) key[j] = pk_bits(pk_max(pk_from(key[j]), h));                                           \
       else hmax = pk_max(hmax, h);                                                                                          \
       uy = y; uf = f;                                                                                                       \
     }                                                                                                                       \
@@ -209,7 +232,26 @@ __device__ __forceinline__ SwRes sw_quad16(const uint32_t* __restrict__ rec, uin
     SW16_STEP(0) SW16_STEP(1) SW16_STEP(2) SW16_STEP(3)
   }
 #undef SW16_STEP
-  if (!KEYS) {
+  if (KEYS == SW16_PREFIX) {
+    // (32-bit arithmetic from here: h >= 0, so a half is its row's M_i as it stands)
+    const int sg = max(max(match, mismatch), max(scoreN, 0));
+    int lo = 0, hi = sg * min(m, rem);
+    const int below0 = m - 1 - gl * R;                      // rows of the span below the lane's first one (every row's count comes from this number of the task, not from
+                                                            // a row index: 2 R indices that are the same for every task get computed once per kernel and parked in scratch)
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+#pragma unroll
+      for (int hf = 0; hf < 2; hf++) {
+        const int below = below0 - 4 * R * hf - j;          // < 0: a row >= m
+        const int mi = below >= 0 ? (int)(hf ? key[j] >> 16 : key[j] & 0xFFFFu) : 0;
+        lo = max(lo, mi); hi = max(hi, mi + sg * max(min(below, rem), 0));
+      }
+    }
+    for (int d = 2; d > 0; d >>= 1) { lo = max(lo, __shfl_xor(lo, d, 64)); hi = max(hi, __shfl_xor(hi, d, 64)); }
+    SwRes rs; rs.score = lo; rs.end_ref = -3; rs.end_read = min(max(hi, lo), 0xFFFF);      // (wres_pack makes x = lo | hi << 16, y = WRES_PREFIX of it)
+    return rs;
+  }
+  if (KEYS == SW16_SCORE) {
     const uint32_t hb = pk_bits(hmax);
     int sc = max((int)(hb & 0xFFFFu), (int)(hb >> 16));
     for (int d = 2; d > 0; d >>= 1) sc = max(sc, __shfl_xor(sc, d, 64));
@@ -237,7 +279,10 @@ __device__ __forceinline__ SwRes sw_quad16(const uint32_t* __restrict__ rec, uin
 }
 
 // a result: x = score, y = (end_ref + 1) << 16 | end_read
-__device__ __forceinline__ uint2 wres_pack(const SwRes& s) { return make_uint2((uint32_t)s.score, s.end_ref < -1 ? 0xFFFFFFFFu : ((uint32_t)(s.end_ref + 1) << 16) | ((uint32_t)s.end_read & 0xFFFFu)); }
+__device__ __forceinline__ uint2 wres_pack(const SwRes& s) {
+  if (s.end_ref == -3) return make_uint2(((uint32_t)s.score & 0xFFFFu) | ((uint32_t)s.end_read << 16), WRES_PREFIX);      // a prefix task's interval
+  return make_uint2((uint32_t)s.score, s.end_ref < -1 ? 0xFFFFFFFFu : ((uint32_t)(s.end_ref + 1) << 16) | ((uint32_t)s.end_read & 0xFFFFu));
+}
 __device__ __forceinline__ SwRes wres_unpack(const uint2 v) {
   SwRes s; s.score = (int)v.x;
   if (v.y == 0xFFFFFFFFu) { s.end_ref = -2; s.end_read = 0; }
@@ -252,25 +297,30 @@ __device__ __forceinline__ SwRes wres_unpack(const uint2 v) {
 #endif
 template <int R>
 __global__ void __launch_bounds__(64, SW16_WAVES(R)) k_sw16(DReads rd, DIndex ix, DParams P, const WTask* __restrict__ tk, const uint32_t* __restrict__ tidx1,
-                                                           const uint32_t* __restrict__ tidx2, const unsigned long long* __restrict__ wc, uint2* __restrict__ res) {
+                                                           const uint32_t* __restrict__ tidx2, const uint32_t* __restrict__ tidx3, const unsigned long long* __restrict__ wc, uint2* __restrict__ res) {
   const int lane = lane_id(), g = lane >> 2, gl = lane & 3;
-  // two lists: tidx[0, ntA) = tasks scored with their end cells, tidx2[0, ntB) = tasks of which only the score is asked
-  const uint32_t ntA = (uint32_t)wc[WC_NTASK], ntB = (uint32_t)wc[WC_NTASK2];
-  const uint32_t npassA = (ntA + 15u) / 16u, npass = npassA + (ntB + 15u) / 16u;
+  // three lists: tidx[0, ntA) = tasks scored with their end cells, tidx2[0, ntB) = tasks of which only the score is asked, tidx3[0, ntC) = prefix
+  // tasks (an interval from the first columns; last, so that the sixteen problems of a wave run about the same number of steps)
+  const uint32_t ntA = (uint32_t)wc[WC_NTASK], ntB = (uint32_t)wc[WC_NTASK2], ntC = (uint32_t)wc[WC_NTASK3];
+  const uint32_t npassA = (ntA + 15u) / 16u, npassB = npassA + (ntB + 15u) / 16u, npass = npassB + (ntC + 15u) / 16u;
   // (the slot of a pass's task is asked for one pass ahead: the first of the four dependent loads -- slot, task, read, letters -- in front of a pass's work)
-  auto slot_of = [&](uint32_t p) -> uint32_t {
-    const bool keys = p < npassA;
-    const uint32_t ti = (keys ? p : p - npassA) * 16u + (uint32_t)g;
-    return (p < npass && ti < (keys ? ntA : ntB)) ? (keys ? tidx1 : tidx2)[ti] : NONE;
-  };
-  uint32_t slot_next = slot_of(blockIdx.x);
+  // (which list a pass belongs to: two overriding tests in straight-line code -- a three-way choice among the pointers, or a lambda that hands them
+  // out by reference, becomes a table of addresses in private memory and LDS)
+#define SW16_LIST_OF(p, lp, ln, p0)                              \
+  const uint32_t* lp = tidx1; uint32_t ln = ntA, p0 = 0u;        \
+  if ((p) >= npassA) { lp = tidx2; ln = ntB; p0 = npassA; }      \
+  if ((p) >= npassB) { lp = tidx3; ln = ntC; p0 = npassB; }
+  uint32_t slot_next = NONE;
+  { SW16_LIST_OF(blockIdx.x, lp, ln, p0)
+    const uint32_t ti = (blockIdx.x - p0) * 16u + (uint32_t)g;
+    if (blockIdx.x < npass && ti < ln) slot_next = lp[ti]; }
   for (uint32_t p = blockIdx.x; p < npass; p += gridDim.x) {
-    const bool keys = p < npassA;
-    const uint32_t ti = (keys ? p : p - npassA) * 16u + (uint32_t)g;
-    const uint32_t* const tidx = keys ? tidx1 : tidx2;
+    const bool keys = p < npassA, prefix = p >= npassB;
+    SW16_LIST_OF(p, tidx, ln_, p0_)
+    const uint32_t ti = (p - p0_) * 16u + (uint32_t)g;
     const uint32_t slot = slot_next;
     const bool have = slot != NONE;
-    int m = 0, n = 0, aq = 0, dir = 1;
+    int m = 0, n = 0, aq = 0, dir = 1, rem = 0;
     uint32_t len = 0, reversed = 0;
     const uint32_t* rec = rd.words;
     const uint8_t* ref = ix.ref_seq;
@@ -279,8 +329,13 @@ __global__ void __launch_bounds__(64, SW16_WAVES(R)) k_sw16(DReads rd, DIndex ix
       m = t.m; n = t.nref; aq = t.aq; reversed = t.flags & 1u; dir = (t.flags & 2u) ? -1 : 1;
       len = rd.len[t.r]; rec = rd.words + rd.rec_off[t.r];
       ref = ix.ref_seq + t.rf_start;
+      if (prefix) { const int cols = (int)WT_COLS(t.flags); rem = n - cols; n = cols; }      // (0 < cols < nref: k_walk and the seam see to it)
     }
-    slot_next = slot_of(p + gridDim.x);
+    slot_next = NONE;
+    { const uint32_t pn = p + gridDim.x;
+      SW16_LIST_OF(pn, lp, ln, p0)
+      const uint32_t tn = (pn - p0) * 16u + (uint32_t)g;
+      if (pn < npass && tn < ln) slot_next = lp[tn]; }
     int nn = n;
     for (int d = 32; d > 0; d >>= 1) nn = max(nn, __shfl_xor(nn, d, 64));
     // does the window hold an ambiguous letter?  Only asked of a reference DB that has one at all (DIndex::ref_any_n), eight letters per lane at a time
@@ -298,9 +353,11 @@ __global__ void __launch_bounds__(64, SW16_WAVES(R)) k_sw16(DReads rd, DIndex ix
     SwRes s;
     const bool hasn = __any(hn);
 #define SW16_ARGS rec, len, reversed, m, aq, ref, n, P.match, P.mismatch, P.score_N, P.gap_open, P.gap_ext, dir
-    if (keys) { if (hasn) s = sw_quad16<R, true, true>(SW16_ARGS); else s = sw_quad16<R, false, true>(SW16_ARGS); }
-    else { if (hasn) s = sw_quad16<R, true, false>(SW16_ARGS); else s = sw_quad16<R, false, false>(SW16_ARGS); }
+    if (keys) { if (hasn) s = sw_quad16<R, true, SW16_KEYS>(SW16_ARGS); else s = sw_quad16<R, false, SW16_KEYS>(SW16_ARGS); }
+    else if (prefix) { if (hasn) s = sw_quad16<R, true, SW16_PREFIX>(SW16_ARGS, rem); else s = sw_quad16<R, false, SW16_PREFIX>(SW16_ARGS, rem); }
+    else { if (hasn) s = sw_quad16<R, true, SW16_SCORE>(SW16_ARGS); else s = sw_quad16<R, false, SW16_SCORE>(SW16_ARGS); }
 #undef SW16_ARGS
+#undef SW16_LIST_OF
     // (the task's slot is asked for again rather than kept across the Smith-Waterman loop, whose rows take every register the occupancy allows)
     if (have && gl == 0) res[tidx[ti]] = wres_pack(s);
   }
@@ -317,8 +374,8 @@ __global__ void __launch_bounds__(64, FINAL ? 3 : SMR_WALK_WAVES_PER_SIMD)
 k_walk(DReads rd, DIndex ix, DParams P, int pass, int is_last_strand, RState* __restrict__ work, AlignRec* __restrict__ work_aln, RWork* __restrict__ rw,
        unsigned long long* __restrict__ ctr, const uint2* __restrict__ mrec, const uint32_t* __restrict__ mpool, const uint32_t* __restrict__ pool,
        const uint2* __restrict__ list, const WState* __restrict__ ws_prev, const WTask* __restrict__ tk_prev, const uint2* __restrict__ res_prev,
-       WState* __restrict__ ws_cur, WTask* __restrict__ tk_cur, uint32_t* __restrict__ tidx, uint32_t* __restrict__ tidx2, unsigned long long* __restrict__ wc,
-       uint32_t K0, unsigned long long task_cap, int round, uint32_t lds_ml, uint32_t lds_rf, uint32_t assume_min) {
+       WState* __restrict__ ws_cur, WTask* __restrict__ tk_cur, uint32_t* __restrict__ tidx, uint32_t* __restrict__ tidx2, uint32_t* __restrict__ tidx3, unsigned long long* __restrict__ wc,
+       uint32_t K0, unsigned long long task_cap, int round, uint32_t lds_ml, uint32_t lds_rf, uint32_t assume_min, uint32_t prefix_pct, unsigned long long* __restrict__ pstat) {
   SMR_DYN_LDS(unsigned char, lds_raw);                  // FINAL: read letters (lds_ml) | reference window (lds_rf)
   __shared__ unsigned long long l_pairs[WK_MAX_POS];    // (reference position << 32 | window position) of the sorted triples of the candidates
   __shared__ uint2 l_cand[64];                          // candidates in walk order: {reference, count | first triple << 8}
@@ -329,13 +386,20 @@ k_walk(DReads rd, DIndex ix, DParams P, int pass, int is_last_strand, RState* __
   __shared__ WTask s_ctk[WK_MAX];                       // the tasks the read left in the previous round ...
   __shared__ uint2 s_cres[WK_MAX];                      // ... and their results
   __shared__ uint32_t s_tix[WK_CLAIM * WK_MAX];         // task slots of the chunk being worked on (appended to tidx / tidx2 with one atomic per chunk):
-                                                        // the tasks to be scored with their end cells from the front, the score-only ones from the back
-  __shared__ uint32_t s_next, s_tbase;
+                                                        // the tasks to be scored with their end cells from the front (a prefix task among them: bit 31), the score-only ones from the back
+  __shared__ uint32_t s_next, s_tbase, s_tbase3;
   const int lane = lane_id();
   const uint32_t nlist = (uint32_t)wc[WC_NLIST];
   const uint32_t K = walk_tasks_per_read(nlist, task_cap, K0, round);                                                // tasks per read of this round ...
   const uint32_t Kp = round > 0 ? walk_tasks_per_read((uint32_t)(wc - WC_STRIDE)[WC_NLIST], task_cap, K0, round - 1) : K0;      // ... and of the previous one (where this round's reads left theirs)
   unsigned long long n_fwd = 0, n_cells = 0, n_spec = 0, n_spec_used = 0, n_newhit = 0;
+  // prefix tasks left / consumed decisively / met undecided; look-ahead tasks of `assume` reads that the options make eligible, their cells (WPS_*):
+  // counted in LDS by lane 0 -- as wave-uniform registers they took ten more scalar registers through the whole kernel, which already parks 170 of them
+  __shared__ unsigned long long s_wps[WPS_AHEAD_CELLS + 1];
+  if (lane < WPS_AHEAD_CELLS + 1) s_wps[lane] = 0;
+#define WPS_ADD(i, v) { if (lane == 0) s_wps[i] += (unsigned long long)(v); }
+  // a look-ahead task of a read that is expected to align is scored over its first columns only when a stored alignment can make its exact score irrelevant
+  const bool pfx_opts = P.is_best && P.num_alignments > 0;
 #ifdef SMR_WALK_PHASES                                    // where a wave's cycles go (build with -DSMR_WALK_PHASES, run with SMR_DEBUG_PHASES=1): claim + loads, sort + candidates, advance, results + bookkeeping, look-ahead + tasks, write-back, task list
   unsigned long long wph[7] = {0, 0, 0, 0, 0, 0, 0}, wlast = clock64();
 #define WPH(i) { const unsigned long long tn_ = clock64(); wph[i] += tn_ - wlast; wlast = tn_; }
@@ -350,7 +414,7 @@ k_walk(DReads rd, DIndex ix, DParams P, int pass, int is_last_strand, RState* __
     const uint32_t chunk_base = s_next;
     if (chunk_base >= nlist) break;
     const uint32_t chunk_n = min(claim, nlist - chunk_base);
-    uint32_t ntix = 0, ntix2 = 0;
+    uint32_t ntix = 0, ntix2 = 0, ntix3 = 0;              // (ntix3 of the ntix entries are prefix tasks)
     // the chunk's entries at once: lane i asks for entry chunk_base + i and its read's record and length (one round trip per chunk, not two per read)
     uint32_t c_r = 0, c_prev = NONE, c_len = 0;
     uint2 c_mr = make_uint2(NONE, 0u);
@@ -596,10 +660,10 @@ k_walk(DReads rd, DIndex ix, DParams P, int pass, int is_last_strand, RState* __
             wk.k++; wk.started = 0;
           }
         };
-        auto put_task = [&](uint32_t j, const SwTask& t) {
+        auto put_task = [&](uint32_t j, const SwTask& t, uint32_t cols = 0) {
           if (lane == 0) {
             WTask o; o.r = r; o.max_ref = t.max_ref; o.rf_start = t.rf_start; o.ars = (uint32_t)t.align_ref_start; o.head = (uint32_t)t.head; o.aq = (uint16_t)t.align_que_start;
-            o.m = (uint16_t)t.m; o.nref = (uint16_t)t.nref; o.flags = w.reversed ? 1 : 0;
+            o.m = (uint16_t)t.m; o.nref = (uint16_t)t.nref; o.flags = (uint16_t)((w.reversed ? 1u : 0u) | cols);      // (cols is a multiple of 4: WT_COLS)
             tk_cur[(size_t)e * K + j] = o;
           }
         };
@@ -624,6 +688,9 @@ k_walk(DReads rd, DIndex ix, DParams P, int pass, int is_last_strand, RState* __
         // from the DB meets a family of references, one accepted alignment each), "does not" otherwise (a spurious candidate of a background read);
         // later what the read's last result was.  Only which windows get scored ahead depends on it, never a result.
         const uint32_t max_SW_score = len * (uint32_t)P.match;
+        // (a read that met an undecided interval gets no more prefix tasks: its scores lie too close to what it has stored -- on real 16S data
+        // most reads are like that, and every undecided interval is a window scored twice)
+        bool pfx_off = prev != NONE && (ps.bits & 128u);
         bool live = false, rdq_staged = false, dirty = false;      // dirty: st / w changed by an accepted alignment (flip34 alone is redone where it matters)
         for (;;) {
           WPH(3)
@@ -639,15 +706,27 @@ k_walk(DReads rd, DIndex ix, DParams P, int pass, int is_last_strand, RState* __
             if (have_tk) ce = 0;
             else for (uint32_t q = 0; q < n_prev; q++)
               if (s_ctk[q].max_ref == tk.max_ref && s_ctk[q].rf_start == tk.rf_start && (uint32_t)s_ctk[q].aq == (uint32_t)tk.align_que_start && (int)s_ctk[q].m == m && (int)s_ctk[q].nref == nref) { ce = (int)q; break; }
-            if (ce >= 0) { fw = wres_unpack(s_cres[ce]); if (ce > 0) n_spec_used++; }
+            if (ce >= 0 && s_cres[ce].y == WRES_PREFIX) {
+              // An interval [lo, hi] that holds the score.  It is DECISIVE when every statement below does the same for each score in it: aligned
+              // (lo > minimal_score), not the highest possible score (hi < max_SW_score), and not stored -- the read's slots are full and the very
+              // comparison the replacement test makes (stale min_index included) fails for hi.  Then lo stands in for the score.  Otherwise the
+              // walk has no result for this task: it stands here, and the task is left again (scored here in the last round) as task 0, in full.
+              const uint32_t lo = s_cres[ce].x & 0xFFFFu, hi = s_cres[ce].x >> 16;
+              bool dec = lo > P.minimal_score && hi < max_SW_score && pfx_opts && st.n_align == (uint32_t)P.num_alignments;
+              // (the barrier under `if (dec)` is reached by all or none: the block is ONE wave and dec is the same in every lane -- as at the replacement test below)
+              if (dec) { __syncthreads(); dec = hi <= (uint32_t)(work_aln + (size_t)r * P.slots)[st.min_index].score1; }
+              if (dec) { fw.score = (int)lo; fw.end_ref = -2; fw.end_read = 0; WPS_ADD(WPS_DECIDED, 1) n_spec_used++; }
+              else { WPS_ADD(WPS_REDONE, 1) ce = -1; pfx_off = true; }
+            } else if (ce >= 0) { fw = wres_unpack(s_cres[ce]); if (ce > 0) n_spec_used++; }
+            if (ce >= 0) {}                                   // (a result)
             else if (!FINAL) {
               // the walk needs a result it does not have: this task and the ones the walk reaches next under the prediction become the read's
               // tasks of this round; the state the read resumes from (standing at this task) is written first, then the same walk runs on as the look-ahead
               const int assume = prev == NONE ? ((ncand > 0 && (l_cand[0].y & 0xFFu) >= assume_min) ? 1 : 0) : last_aligned;
               WState o; o.k = R.k; o.it = R.it; o.ms_lo = R.ms_lo; o.ms_hi = R.ms_hi; o.begin_ref = R.begin_ref; o.begin_read = R.begin_read; o.best = R.best;
               const uint32_t bits0 = (uint32_t)(R.is_aligned & 1) | ((uint32_t)(R.go_on & 1) << 1) | ((uint32_t)(R.started & 1) << 2) | ((uint32_t)(R.pending_pop & 1) << 3) | ((uint32_t)(search & 1) << 4) |
-                                     ((uint32_t)(last_aligned & 1) << 6);
-              uint32_t nk = 1, cells = (uint32_t)m * (uint32_t)nref;
+                                     ((uint32_t)(last_aligned & 1) << 6) | (pfx_off ? 128u : 0u);
+              uint32_t nk = 1, cells = (uint32_t)m * (uint32_t)nref, pfx_mask = 0;
               put_task(0, tk);
               R.is_aligned = assume;
               bool ended = false;
@@ -655,7 +734,13 @@ k_walk(DReads rd, DIndex ix, DParams P, int pass, int is_last_strand, RState* __
                 SwTask t2;
                 if (advance(R, t2) != 1) { ended = true; break; }
                 if (!task_ok(t2)) break;
-                put_task(nk, t2); nk++; cells += (uint32_t)t2.m * (uint32_t)t2.nref;
+                // (a look-ahead task of a read that is expected to align: a prefix task where the mode, the options and the window allow it)
+                uint32_t cols = 0;
+                if (assume && pfx_opts) {
+                  WPS_ADD(WPS_AHEAD, 1) WPS_ADD(WPS_AHEAD_CELLS, (uint32_t)t2.m * (uint32_t)t2.nref)
+                  if (prefix_pct && !pfx_off) { cols = walk_prefix_cols((uint32_t)t2.nref, prefix_pct); if (cols >= (uint32_t)t2.nref) cols = 0; }
+                }
+                put_task(nk, t2, cols); pfx_mask |= (cols ? 1u : 0u) << nk; nk++; cells += (uint32_t)t2.m * (uint32_t)t2.nref;
                 R.is_aligned = assume;
               }
               n_spec += nk - 1;
@@ -663,7 +748,7 @@ k_walk(DReads rd, DIndex ix, DParams P, int pass, int is_last_strand, RState* __
               if (lane == 0) ws_cur[e] = o;
               live_bits = nk << 8;
               // (a read that is expected to align gets its end cells with the scores; of the others only the score is asked)
-              if (assume) { for (uint32_t q = lane; q < nk; q += 64) s_tix[ntix + q] = e * K + q; ntix += nk; }
+              if (assume) { for (uint32_t q = lane; q < nk; q += 64) s_tix[ntix + q] = (e * K + q) | (((pfx_mask >> q) & 1u) << 31); ntix += nk; ntix3 += (uint32_t)__popc(pfx_mask); WPS_ADD(WPS_SCORED, __popc(pfx_mask)) }
               else { for (uint32_t q = lane; q < nk; q += 64) s_tix[WK_CLAIM * WK_MAX - 1u - (ntix2 + q)] = e * K + q; ntix2 += nk; }
               live = true;
               WPH(4)
@@ -747,10 +832,21 @@ k_walk(DReads rd, DIndex ix, DParams P, int pass, int is_last_strand, RState* __
     // the chunk's tasks go to the dense list with one atomic
     if (!FINAL && ntix) {
       __syncthreads();
-      if (lane == 0) s_tbase = (uint32_t)atomicAdd(&wc[WC_NTASK], (unsigned long long)ntix);
+      if (lane == 0) {
+        s_tbase = (uint32_t)atomicAdd(&wc[WC_NTASK], (unsigned long long)(ntix - ntix3));
+        if (ntix3) s_tbase3 = (uint32_t)atomicAdd(&wc[WC_NTASK3], (unsigned long long)ntix3);
+      }
       __syncthreads();
-      const uint32_t tb = s_tbase;
-      for (uint32_t q = lane; q < ntix; q += 64) tidx[tb + q] = s_tix[q];
+      uint32_t tb = s_tbase, tb3 = ntix3 ? s_tbase3 : 0u;
+      const unsigned long long below = (1ull << lane) - 1ull;
+      for (uint32_t q0 = 0; q0 < ntix; q0 += 64) {          // the prefix tasks (bit 31) go to their own list
+        const uint32_t q = q0 + (uint32_t)lane, v = q < ntix ? s_tix[q] : 0u;
+        const bool is3 = q < ntix && (v >> 31), is1 = q < ntix && !(v >> 31);
+        const unsigned long long m1 = __ballot(is1), m3 = __ballot(is3);
+        if (is1) tidx[tb + (uint32_t)__popcll(m1 & below)] = v;
+        if (is3) tidx3[tb3 + (uint32_t)__popcll(m3 & below)] = v & 0x7FFFFFFFu;
+        tb += (uint32_t)__popcll(m1); tb3 += (uint32_t)__popcll(m3);
+      }
     }
     if (!FINAL && ntix2) {
       __syncthreads();
@@ -767,11 +863,13 @@ k_walk(DReads rd, DIndex ix, DParams P, int pass, int is_last_strand, RState* __
     if (n_spec) atomicAdd(&ctr[C_SW_SPEC], n_spec);
     if (n_spec_used) atomicAdd(&ctr[C_SW_SPEC_USED], n_spec_used);
     if (n_newhit) { atomicAdd(&ctr[C_NUM_ALIGNED], n_newhit); atomicAdd(&ctr[C_PER_DB + P.index_num], n_newhit); }
+    for (int q = 0; q <= WPS_AHEAD_CELLS; q++) if (s_wps[q]) atomicAdd(&pstat[q], s_wps[q]);      // (lane 0 wrote them all)
 #ifdef SMR_WALK_PHASES
     for (int q = 0; q < 7; q++) if (wph[q]) atomicAdd(&ctr[C_SHARDS + (blockIdx.x & (C_NSHARD - 1)) * C_SHARD_W + C_SHARD_PH + q], wph[q]);
 #endif
   }
 #undef WPH
+#undef WPS_ADD
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -795,7 +893,7 @@ __global__ void __launch_bounds__(1024) k_wnext(DParams P, int is_last_strand, R
       if (nk > 0) {
         live = true;
         r = list[e].x;
-        if (s.bits & 32u) {
+        if (s.bits & 32u) {                                 // (bit 5 is only ever set without `assume`: no prefix task, so no interval, is read here)
           bool any = false;
           for (uint32_t j = 0; j < nk; j++) { const uint32_t sc = res[(size_t)e * K + j].x; any |= (sc > 65535u ? 65535u : sc) > P.minimal_score; }
           if (!any) {

@@ -325,6 +325,28 @@ class Engine:
                                         filters, rows, blocks, out.ctypes.data), "smr_sw16_batch")
         return out[:n]
 
+    SW16_PREFIX_TASK = np.dtype([("read", "<u4"), ("win_off", "<u4"), ("aq", "<u2"), ("m", "<u2"), ("nref", "<u2"), ("cols", "<u2"), ("reversed", "u1"), ("pad_", "V3")])
+
+    def sw16_prefix_batch(self, tasks, ref, rows, match=2, mismatch=-3, score_N=-3, gap_open=5, gap_ext=2, blocks=0, force_any_n=False, **_):
+        """the prefix tasks of k_sw16<rows> (smr_sw16_prefix_batch).  tasks: tuples (read, aq, m, reversed, win_off, nref, cols);
+        -> int32 array (n, 2): lo, hi -- the interval that holds the score of the span against the whole window, from its first cols columns"""
+        n = len(tasks)
+        t = np.zeros(max(n, 1), dtype=self.SW16_PREFIX_TASK)
+        for i, (r, aq, m, rev, wo, nref, cols) in enumerate(tasks):
+            t[i] = (r, wo, aq, m, nref, cols, rev, b"")
+        rf = np.frombuffer(bytes(ref) + b"\0", dtype=np.uint8).copy()
+        out = np.zeros((max(n, 1), 2), dtype=np.int32)
+        self._chk(self.L.smr_sw16_prefix_batch(self.h, n, t.ctypes.data, rf.ctypes.data, len(ref), int(bool(force_any_n)), match, mismatch, score_N, gap_open, gap_ext,
+                                               rows, blocks, out.ctypes.data), "smr_sw16_prefix_batch")
+        return out[:n]
+
+    def walk_prefix_stats(self):
+        """prefix tasks of the candidate walk since prof_reset (smr_walk_prefix_stats): scored, decided, redone, unused; the look-ahead tasks of reads
+        expected to align under best N and their cells; percent = SMR_WALK_PREFIX as latched"""
+        out = (C.c_uint64 * 8)()
+        self._chk(self.L.smr_walk_prefix_stats(self.h, out), "smr_walk_prefix_stats")
+        return dict(zip(("scored", "decided", "redone", "unused", "ahead", "ahead_cells", "percent", "live"), out[:8]))
+
     def sw16_launches(self):
         """launches of k_sw16<13 | 19 | 26 | 32> since the engine was created: ({rows: by the walk rounds}, {rows: by the begin-cell stage})"""
         out = (C.c_uint64 * 8)()
