@@ -584,6 +584,13 @@ int smr_walk_prefix_stats(smr_ctx*, uint64_t out[8]);
 /* Launches of k_sw16<13 | 19 | 26 | 32> since smr_create: out[0..3] by the rounds of the candidate walk, out[4..7] by the begin-cell stage
  * (which instantiation a batch gets follows from its longest read; a batch that never takes the walk path counts nothing). */
 int smr_sw16_launches(const smr_ctx*, uint64_t out[8]);
+/* k_sw16h<R>: k_sw16<R> in packed f16 (v_pk_add_f16, v_pk_maximum3_f16: the three-operand maximum gfx950 lacks for 16-bit integers), bit-exact
+ * because every value is an integer f16 holds.  Launched instead of k_sw16<R> (walk rounds, begin-cell stage, smr_sw16_batch,
+ * smr_sw16_prefix_batch; smr_sw16_launches counts both) where the scheme allows it: match, mismatch and score_N + gap_open each an integer of
+ * at most three significant bits (0..8, 10, 12, 14, 16, 20, ...: one table byte), and 8 R x match + gap_open + gap_ext + the largest of them <= 2048.
+ * smr_create compares the two kernels on the device and keeps k_sw16 alone if they differ; SMR_SW16_F16=0 does the same by hand.
+ * set_to: 0 / 1 = select, anything else = query only; returns the mode in use.  *launches (may be NULL): k_sw16h launches since smr_create. */
+int smr_sw16_f16(smr_ctx*, int set_to, uint64_t* launches);
 /* The traceback kernels at the same seam: for n independent triples (read window, reference window -- both exactly the aligned spans
  * [begin1, end1] -- and the alignment's score1) the CIGAR that banded_sw returns for them (ssw.c:577-773 as called from ssw_align,
  * ssw.c:919-926): BAM-style u32 operations (length << 4 | op, op 0/1/2 = M/I/D), pair i at cigar_out[cigar_off_out[i] .. cigar_off_out[i+1]).

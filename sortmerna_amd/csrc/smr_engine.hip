@@ -214,6 +214,8 @@ struct smr_ctx {
   DevBuf<uint2> d_wlist[2]; DevBuf<WState> d_wstate[2]; DevBuf<WTask> d_wtask[2]; DevBuf<uint2> d_wres[2];
   DevBuf<uint32_t> d_wtidx, d_wslow; DevBuf<unsigned long long> d_wctr; size_t walk_cap = 0; uint32_t walk_kcap = 0;      // walk_cap x walk_kcap: the layout of d_wtidx
   size_t walk_lds_attr = 0, pg_lds_attr = 0, search_lds_attr = 0;
+  int sw16_f16 = tune.sw16_f16;            // k_sw16h (packed f16, smr_walk.hpp) where sw_h16_fits allows it; 0 by SMR_SW16_F16=0, smr_sw16_f16 or a failed self-check of smr_create
+  uint64_t sw16h_launches = 0;             // launches of k_sw16h<R> since smr_create, the test seam's included (smr_sw16_f16)
   uint64_t sw16_launches[8] = {};          // k_sw16<13 | 19 | 26 | 32> launched by the walk rounds [0..3] and by the begin-cell stage [4..7] (smr_sw16_launches)
   // rounds per (strand, pass): without SMR_WALK_ROUNDS the number adapts to what the previous part needed (the last round with more than a few
   // reads listed + the closing one: an empty round still costs three launches, ~70 us of stream time; 8 -> 4 rounds = 3 % of the bench step)
@@ -444,6 +446,16 @@ extern "C" int smr_create(int device, smr_ctx** out, char* err, size_t errcap) {
       fprintf(stderr, "libsmr_hip: packed Smith-Waterman kernel disagrees with the 32-bit kernel on %llu self-check cases; using the 32-bit kernel\n", (unsigned long long)bad);
       c->sw_mode = 0;
     }
+  }
+  if (c->sw16_f16) {
+    // k_sw16h must agree with k_sw16 on this device (end cells, scores, prefix intervals), or the integer kernel does all the work
+    uint64_t bad = 0;
+    const uint32_t cases = c->tune.sw_selfcheck;
+    if (cases > 0 && (sw16h_selfcheck(c, cases, 20261019u, &bad) != SMR_OK || bad != 0)) {
+      say(c->tune, "k_sw16h (packed f16) disagrees with k_sw16 on %llu self-check results; using k_sw16\n", (unsigned long long)bad);
+      c->sw16_f16 = 0;
+    }
+    c->sw16h_launches = 0;                 // (the counter is about the work of the context's user)
   }
   *out = c;
   return SMR_OK;

@@ -58,14 +58,17 @@ begins_fn begins_kernel(bool lng, bool striped) {
   static const begins_fn K[4] = {k_begins<false, false>, k_begins<true, false>, k_begins<false, true>, k_begins<true, true>};
   return K[(lng ? 1 : 0) | (striped ? 2 : 0)];
 }
-// k_sw16<rows> over one task list (smr_walk.hpp).  counted: 0 = a walk round, 4 = the begin-cell stage (smr_sw16_launches), < 0 = not counted (the
+// k_sw16<rows> or k_sw16h<rows> over one task list (smr_walk.hpp).  counted: 0 = a walk round, 4 = the begin-cell stage (smr_sw16_launches), < 0 = not counted (the
 // test seam); blocks 0: what fills the device
 typedef decltype(&k_sw16<13>) sw16_fn;
 void launch_sw16(smr_ctx* c, int rows, int counted, uint32_t blocks, const DReads& rd, const DIndex& ix, const DParams& P, const WTask* tasks, const uint32_t* tix, const uint32_t* tix2,
-                 const uint32_t* tix3, const unsigned long long* wc, uint2* res) {
-  static const sw16_fn K[4] = {k_sw16<13>, k_sw16<19>, k_sw16<26>, k_sw16<32>};
+                 const uint32_t* tix3, const unsigned long long* wc, uint2* res, int flavour = -1) {      // flavour: -1 = the dispatcher's choice, 0 / 1 = k_sw16 / k_sw16h (the self-check of smr_create)
+  static const sw16_fn K[2][4] = {{k_sw16<13>, k_sw16<19>, k_sw16<26>, k_sw16<32>}, {k_sw16h<13>, k_sw16h<19>, k_sw16h<26>, k_sw16h<32>}};
   const int v = rows == 13 ? 0 : rows == 19 ? 1 : rows == 26 ? 2 : 3;
-  launch(c, K[v], dim3(blocks ? blocks : (uint32_t)c->n_cu * 4u * (uint32_t)SW16_WAVES(rows)), dim3(64), 0, rd, ix, P, tasks, tix, tix2, tix3, wc, res);
+  // the f16 flavour (three-operand maxima) where the scheme and the longest span of this instantiation stay within what f16 holds exactly
+  const int h = (flavour < 0 ? c->sw16_f16 != 0 : flavour == 1) && sw_h16_fits(std::min<int>(8 * rows, (int)WK_MAX_ROWS), P.match, P.mismatch, P.score_N, P.gap_open, P.gap_ext) ? 1 : 0;
+  c->sw16h_launches += (uint64_t)h;
+  launch(c, K[h][v], dim3(blocks ? blocks : (uint32_t)c->n_cu * 4u * (uint32_t)SW16_WAVES(rows)), dim3(64), 0, rd, ix, P, tasks, tix, tix2, tix3, wc, res);
   if (counted >= 0) c->sw16_launches[counted + v]++;
 }
 

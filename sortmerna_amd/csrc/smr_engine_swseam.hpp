@@ -427,6 +427,120 @@ extern "C" int smr_sw16_launches(const smr_ctx* c, uint64_t out[8]) {
   return SMR_OK;
 }
 
+// k_sw16h against k_sw16 on the device (smr_create): for each of the four instantiations, seeded pseudo-random reads (~1.5 % N) of 1 .. 8 R letters
+// against a mutated copy between random flanks (3 of 4) or an unrelated window, each as a task with end cells (every fourth one a begin-cell
+// task, rows and columns backwards), as a score-only task and, where the window has more than four columns, as a prefix task; the two
+// scoring schemes of smr_sw_selfcheck in turn.  *n_bad: results (8 bytes each) on which the kernels differ.
+int sw16h_selfcheck(smr_ctx* c, uint32_t cases, uint32_t seed, uint64_t* n_bad) {
+  *n_bad = 0;
+  const uint32_t n_reads = std::min<uint32_t>(cases, 64u);
+  if (n_reads == 0) return SMR_OK;
+  static const int ROWS[4] = {13, 19, 26, 32};
+  static const int SC[2][3] = {{2, -3, -3}, {5, -4, -4}};
+  uint32_t x = seed | 1u;
+  auto rnd = [&x]() { x ^= x << 13; x ^= x >> 17; x ^= x << 5; return x >> 8; };
+  DevPool pool;
+  for (int v = 0; v < 4; v++) {
+    const uint32_t max_m = std::min<uint32_t>(8u * (uint32_t)ROWS[v], WK_MAX_ROWS);
+    std::vector<uint32_t> words, len(n_reads);
+    std::vector<uint64_t> rec_off(n_reads);
+    std::vector<uint8_t> ref;
+    std::vector<WTask> tk;
+    std::vector<uint32_t> ia, ib, ic;
+    for (uint32_t r = 0; r < n_reads; r++) {
+      const uint32_t m = r == 0 ? max_m : 1u + rnd() % max_m;
+      std::vector<uint8_t> rd(m);
+      for (auto& ch : rd) { const uint32_t h = rnd(); ch = (h & 63u) == 0 ? 4 : (uint8_t)((h >> 8) & 3u); }
+      len[r] = m; rec_off[r] = words.size();
+      const size_t cw = (m + 15u) >> 4, aw = (m + 31u) >> 5, w0 = words.size();
+      words.resize(w0 + cw + aw, 0u);
+      for (uint32_t q = 0; q < m; q++) {
+        if (rd[q] == 4) words[w0 + cw + (q >> 5)] |= 1u << (q & 31);
+        else words[w0 + (q >> 4)] |= (uint32_t)rd[q] << ((q & 15) * 2);
+      }
+      const uint32_t hm = rnd();
+      const bool homolog = (hm & 3u) != 0, reversed = (hm >> 2) & 1u;
+      const uint64_t win_off = ref.size();
+      for (uint32_t q = 0, fl = (hm >> 4) & 15u; q < fl; q++) ref.push_back((uint8_t)(rnd() & 3u));
+      for (uint32_t q = 0; q < m; q++) {
+        // (a forward read's letters as they are; a reversed one is read complemented from its end, so its homolog is the reverse complement)
+        const uint8_t own = reversed ? (rd[m - 1 - q] == 4 ? 0 : (uint8_t)(3 - rd[m - 1 - q])) : (rd[q] == 4 ? 0 : rd[q]);
+        const uint32_t h = rnd(), ev = (h >> 4) & 63u;
+        if (!homolog) { ref.push_back((uint8_t)(h & 3u)); continue; }
+        if (ev == 0) continue;
+        if (ev == 1) ref.push_back((uint8_t)((h >> 12) & 3u));
+        if (ev == 2) { ref.push_back(4); continue; }
+        ref.push_back(ev < 6 ? (uint8_t)((h >> 16) & 3u) : own);
+      }
+      for (uint32_t q = 0, fl = (hm >> 8) & 15u; q < fl; q++) ref.push_back((uint8_t)(rnd() & 3u));
+      if (ref.size() == win_off) ref.push_back(0);
+      const uint32_t nref = (uint32_t)(ref.size() - win_off);
+      WTask t;
+      memset(&t, 0, sizeof t);
+      t.r = r; t.rf_start = win_off; t.aq = 0; t.m = (uint16_t)m; t.nref = (uint16_t)nref; t.flags = reversed ? 1 : 0;
+      WTask ta = t;
+      if ((r & 3u) == 3u) { ta.aq = (uint16_t)(m - 1); ta.rf_start = win_off + nref - 1; ta.flags |= 2u; }
+      ia.push_back((uint32_t)tk.size()); tk.push_back(ta);
+      ib.push_back((uint32_t)tk.size()); tk.push_back(t);
+      if (nref > 4) {
+        WTask tc = t;
+        tc.flags |= (uint16_t)(4u * (1u + rnd() % ((nref - 1u) / 4u)));      // cols: a multiple of 4 in [4, nref)
+        ic.push_back((uint32_t)tk.size()); tk.push_back(tc);
+      }
+    }
+    words.resize(words.size() + 4, 0u);          // (the kernel's 12-byte and 8-byte loads may begin in a record's last word)
+    const uint32_t n_tasks = (uint32_t)tk.size();
+    IB_GET(d_words, uint32_t, words.size()); IB_GET(d_off, uint64_t, n_reads); IB_GET(d_len, uint32_t, n_reads);
+    IB_GET(d_ref, uint8_t, ref.size() + 8); IB_GET(d_tk, WTask, n_tasks);
+    IB_GET(d_ia, uint32_t, n_tasks); IB_GET(d_ib, uint32_t, n_tasks); IB_GET(d_ic, uint32_t, n_tasks);
+    IB_GET(d_wc, unsigned long long, WC_STRIDE); IB_GET(d_res, uint2, (size_t)2 * n_tasks);
+    HIPCHK(c, hipMemcpyAsync(d_words, words.data(), words.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_off, rec_off.data(), (size_t)n_reads * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_len, len.data(), (size_t)n_reads * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_ref, 0, ref.size() + 8, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_ref, ref.data(), ref.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tk, tk.data(), (size_t)n_tasks * sizeof(WTask), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_ia, ia.data(), ia.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_ib, ib.data(), ib.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (!ic.empty()) HIPCHK(c, hipMemcpyAsync(d_ic, ic.data(), ic.size() * 4, hipMemcpyHostToDevice, c->stream));
+    unsigned long long wc[WC_STRIDE] = {};
+    wc[WC_NTASK] = ia.size(); wc[WC_NTASK2] = ib.size(); wc[WC_NTASK3] = ic.size();
+    HIPCHK(c, hipMemcpyAsync(d_wc, wc, sizeof wc, hipMemcpyHostToDevice, c->stream));
+    DReads rd;
+    rd.words = d_words; rd.rec_off = d_off; rd.len = d_len; rd.n = n_reads; rd.max_len = max_m;
+    DIndex ix;
+    memset(&ix, 0, sizeof ix);
+    ix.ref_seq = d_ref; ix.ref_any_n = 1u;
+    std::vector<uint2> res((size_t)2 * n_tasks);
+    for (int k = 0; k < 2; k++) {
+      DParams P;
+      memset(&P, 0, sizeof P);
+      P.match = SC[k][0]; P.mismatch = SC[k][1]; P.score_N = SC[k][2]; P.gap_open = 5; P.gap_ext = 2; P.sw_mode = c->sw_mode;
+      if (!sw_h16_fits((int)max_m, P.match, P.mismatch, P.score_N, P.gap_open, P.gap_ext)) continue;
+      HIPCHK(c, hipMemsetAsync(d_res, 0xEE, (size_t)2 * n_tasks * sizeof(uint2), c->stream));
+      launch_sw16(c, ROWS[v], -1, 0, rd, ix, P, d_tk, d_ia, d_ib, d_ic, d_wc, d_res, 0);
+      launch_sw16(c, ROWS[v], -1, 0, rd, ix, P, d_tk, d_ia, d_ib, d_ic, d_wc, d_res + n_tasks, 1);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipMemcpyAsync(res.data(), d_res, (size_t)2 * n_tasks * sizeof(uint2), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      for (uint32_t i = 0; i < n_tasks; i++) {
+        const uint2 a = res[i], b = res[(size_t)n_tasks + i];
+        if (a.x != b.x || a.y != b.y || (a.x == 0xEEEEEEEEu && a.y == 0xEEEEEEEEu)) (*n_bad)++;
+      }
+    }
+  }
+  return SMR_OK;
+}
+
+// k_sw16h, the packed-f16 flavour of k_sw16: set_to 0 / 1 = select, anything else = query only; returns the mode in use (0 too after a failed self-check
+// of smr_create or under SMR_SW16_F16=0).  launches (may be null): k_sw16h<R> launched since smr_create, whoever asked for them.
+extern "C" int smr_sw16_f16(smr_ctx* c, int set_to, uint64_t* launches) {
+  if (!c) return SMR_ERR_ARG;
+  if (set_to == 0 || set_to == 1) c->sw16_f16 = set_to;
+  if (launches) *launches = c->sw16h_launches;
+  return c->sw16_f16;
+}
+
 extern "C" int smr_sw_mode(smr_ctx* c, int set_to) {      // set_to: 0 / 1 = select, anything else = query only; returns the mode in use
   if (!c) return SMR_ERR_ARG;
   if (set_to >= 0 && set_to <= 2) c->sw_mode = set_to;

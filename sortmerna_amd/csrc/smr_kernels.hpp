@@ -26,6 +26,7 @@
 #include "smr_host.hpp"
 
 #include <smr_device_ops.hpp>      // SMR_DYN_LDS, packed 16-bit ops, v_perm_b32, v_rcp_f32 (the test suite's kernel emulator supplies its own)
+#include <smr_h16_ops.hpp>         // packed f16 add / max3 of k_sw16h (likewise)
 
 namespace smr {
 

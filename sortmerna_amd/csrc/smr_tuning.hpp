@@ -34,6 +34,8 @@ struct Tuning {
   uint32_t walk_assume = 3;               // SMR_WALK_ASSUME: round 0 predicts "aligns" from this many seeds of the best candidate
   uint32_t walk_prefix = 44;              // SMR_WALK_PREFIX: per cent of a window's columns that a look-ahead task of a read expected to align is scored over (a prefix task, smr_walk.hpp); 0 = off   [0..100]
                                           //   (not in the table below, whose names tests/test_emu_tuning.py pins: smr_walk_prefix_stats hands out what was latched)
+  int sw16_f16 = 1;                       // SMR_SW16_F16: 0 = k_sw16 (packed 16-bit integers) scores every task list, 1 = k_sw16h (packed f16, three-operand maxima) where sw_h16_fits holds
+                                          //   (not in the table below either: smr_sw16_f16 hands out the mode in use)
   bool begins_x4 = false;                 // SMR_BEGINS_X4 (set): begin cells four per wave (k_begins) instead of sixteen (k_sw16)
   bool pg_host = false;                   // SMR_PG_HOST: the host transform of the pigeonhole layout instead of the device build at upload
   bool trace_global_rows = false;         // SMR_TRACE_GLOBAL_ROWS (set): the wide-band variant of k_trace_wide, rows in global memory
@@ -78,6 +80,7 @@ inline Tuning read_tuning(const TuningLimits& L) {
   if ((e = getenv("SMR_WALK_GATHER"))) t.walk_gather = atoi(e);
   if ((e = getenv("SMR_WALK_ASSUME"))) t.walk_assume = (uint32_t)atoi(e);
   if ((e = getenv("SMR_WALK_PREFIX"))) t.walk_prefix = (uint32_t)std::max(0, std::min(100, atoi(e)));
+  if ((e = getenv("SMR_SW16_F16"))) t.sw16_f16 = atoi(e) != 0 ? 1 : 0;
   t.begins_x4 = getenv("SMR_BEGINS_X4") != nullptr;
   if ((e = getenv("SMR_PG_HOST"))) t.pg_host = atoi(e) != 0;
   t.trace_global_rows = getenv("SMR_TRACE_GLOBAL_ROWS") != nullptr;

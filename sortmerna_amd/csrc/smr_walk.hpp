@@ -131,18 +131,83 @@ struct __attribute__((aligned(4))) Sw16W2 { uint32_t a, b; };
 // H(i, c) <= M_i holds for a = H(i - 1, c - 1) - go because M_i >= M_{i-1} - go (the gap opened under M_{i-1}'s cell), for e because it
 // comes from row i, for f because M_i >= M_i' - go - (i - i' - 1) ge for every row i' above.  Rows >= m are left out of lo and hi.
 enum { SW16_SCORE = 0, SW16_KEYS = 1, SW16_PREFIX = 2 };
-template <int R, bool HASN, int KEYS>
+
+// The FLAVOUR of the arithmetic: what a 16-bit half holds and the instructions that work on it.
+//   Sw16Ops<false>  signed 16-bit integers (v_pk_add_i16 / v_pk_sub_i16 / v_pk_max_i16): k_sw16, every scheme sw_pk_fits takes.
+//   Sw16Ops<true>   f16 (v_pk_add_f16 / v_pk_maximum3_f16): k_sw16h.  gfx950 has a packed three-operand maximum for f16 and none for 16-bit
+//                   integers, so e = max(E - ge, Y, 0) and h = max(a, e, f) are one instruction each instead of two, and the score-only
+//                   variant's running maximum takes two rows at a time.  Every value of the recurrence is an integer: H <= m x match,
+//                   Y = H - go >= -go, E - ge >= -ge, F - ge >= -go - ge, a = Y + T <= H + match; f16 holds the integers of magnitude
+//                   <= 2048 exactly, so under sw_h16_fits sums and maxima are the integer flavour's, bit for bit after the conversion.
+//                   Non-negative f16 patterns order like unsigned integers: the keys (h << 16 | column | half) and the 32-bit maxima over
+//                   them work on the patterns as they are, and the epilogue converts the winner (to_int).
+// Score tables: one v_perm_b32 picks ONE byte per half, the other is the constant 0.  Integer: the low byte of T = s + go (<= 255), selector
+// half 0x0C00 | letter.  f16: the HIGH byte of T's encoding, selector half letter << 8 | 0x0C -- T must be an integer whose encoding has a
+// zero low byte, i. e. one of at most three significant bits (0..8, 10, 12, 14, 16, 20, 24, 28, 32, 40, ...: sw_h16_encodable).  The
+// marker of the reference letter N (HASN: the looked-up value is replaced by T_N) sits in the byte that selects the constant: 0x0D
+// instead of 0x0C, bit 8 of the integer flavour's half, bit 0 of the f16 flavour's.  "+ 4" in the table byte moves a selector from the low
+// half's table to the high half's and leaves 0x0C what it is.
+template <bool F16> struct Sw16Ops;
+template <> struct Sw16Ops<false> {
+  typedef pk16 V;
+  static __device__ __forceinline__ V from(uint32_t v) { return pk_from(v); }
+  static __device__ __forceinline__ uint32_t bits(V v) { return pk_bits(v); }
+  static __device__ __forceinline__ V splat(int v) { return pk_splat(v); }
+  static __device__ __forceinline__ V add(V a, V b) { return pk_add(a, b); }
+  static __device__ __forceinline__ V sub(V a, V b) { return pk_sub(a, b); }
+  static __device__ __forceinline__ V max2(V a, V b) { return pk_max(a, b); }
+  static __device__ __forceinline__ V max3(V a, V b, V c) { return pk_max(pk_max(a, b), c); }
+  static __device__ __forceinline__ V e_of(V E, V GE, V Y) { return pk_max(pk_subs_u(E, GE), Y); }      // E is kept clamped at 0 (saturating subtract): e >= 0
+  static __device__ __forceinline__ uint32_t half_of(int v) { return (uint32_t)v & 0xFFFFu; }           // a half's pattern for an integer
+  static __device__ __forceinline__ uint32_t table_byte(int v) { return (uint32_t)v & 0xFFu; }
+  static __device__ __forceinline__ int to_int(uint32_t half) { return (int)half; }                     // (of a non-negative half)
+  static __device__ __forceinline__ uint32_t sel_of(int c) { return pk_sel_of(c); }
+  static constexpr uint32_t SEL_NONE = PK_SEL_NONE, SEL_TO_HI = 0x00040000u, N_SHIFT = 8;
+};
+template <> struct Sw16Ops<true> {
+  typedef h16x2 V;
+  static __device__ __forceinline__ V from(uint32_t v) { return h2_from(v); }
+  static __device__ __forceinline__ uint32_t bits(V v) { return h2_bits(v); }
+  static __device__ __forceinline__ V splat(int v) { return h2_splat(v); }
+  static __device__ __forceinline__ V add(V a, V b) { return h2_add(a, b); }
+  static __device__ __forceinline__ V sub(V a, V b) { return h2_sub(a, b); }
+  static __device__ __forceinline__ V max2(V a, V b) { return h2_max(a, b); }
+  static __device__ __forceinline__ V max3(V a, V b, V c) { return h2_max3(a, b, c); }
+  static __device__ __forceinline__ V e_of(V E, V GE, V Y) { return h2_max3(h2_sub(E, GE), Y, h2_from(0u)); }
+  static __device__ __forceinline__ uint32_t half_of(int v) { return h16_of_int(v); }
+  static __device__ __forceinline__ uint32_t table_byte(int v) { return h16_of_int(v) >> 8; }
+  static __device__ __forceinline__ int to_int(uint32_t half) { return h16_to_int(half); }
+  static __device__ __forceinline__ uint32_t sel_of(int c) { return c < 4 ? (((uint32_t)c << 8) | 0x0Cu) : 0x0C0Du; }
+  static constexpr uint32_t SEL_NONE = 0x0C0Cu, SEL_TO_HI = 0x04000000u, N_SHIFT = 0;
+};
+// may a table value T = score + gap_open go through the f16 flavour's one-byte lookup?
+__host__ __device__ __forceinline__ bool sw_h16_encodable(int v) {
+  if (v < 0 || v > 2048) return false;
+  while (v > 7) { if (v & 1) return false; v >>= 1; }
+  return true;
+}
+// k_sw16h takes spans of m rows under this scheme: the three table values encodable, and the largest magnitude the recurrence forms
+// (H + the largest T on the way up, -go - ge on the way down) within the integers f16 holds exactly
+__host__ __device__ __forceinline__ bool sw_h16_fits(int m, int match, int mismatch, int scoreN, int go, int ge) {
+  const int tmax = (match > mismatch ? (match > scoreN ? match : scoreN) : (mismatch > scoreN ? mismatch : scoreN)) + go;
+  return m >= 0 && go >= 0 && ge >= 0 && sw_h16_encodable(match + go) && sw_h16_encodable(mismatch + go) && sw_h16_encodable(scoreN + go) &&
+         (long long)m * match + go + ge + tmax <= 2048;
+}
+
+template <int R, bool HASN, int KEYS, bool F16 = false>
 __device__ __forceinline__ SwRes sw_quad16(const uint32_t* __restrict__ rec, uint32_t len, uint32_t reversed, int m, int aq, const uint8_t* __restrict__ ref, int n,
                                            int match, int mismatch, int scoreN, int go, int ge, int dir, int rem = 0) {      // rem: SW16_PREFIX only; dir = 1, or -1: rows and columns run backwards from aq / ref (ssw_align's reverse pass)
+  typedef Sw16Ops<F16> O;
+  typedef typename O::V V;
   const int gl = lane_id() & 3;
-  const pk16 GE = pk_splat(ge), GO = pk_splat(go), ZERO = pk_splat(0);
-  const uint32_t TN = (((uint32_t)(scoreN + go)) & 0xFFFFu) * 0x00010001u;
+  const V GE = O::splat(ge), GO = O::splat(go), ZERO = O::splat(0);
+  const uint32_t TN = O::half_of(scoreN + go) * 0x00010001u;
   uint32_t tlo[R], thi[R];
-  pk16 Y[R], E[R];
+  V Y[R], E[R];
   uint32_t key[KEYS ? R : 1];                               // (SW16_PREFIX: the rows' packed running maxima)
-  pk16 hmax = ZERO;
-  const uint32_t t_mm = ((uint32_t)(mismatch + go) & 0xFFu) * 0x01010101u, t_x = ((uint32_t)(mismatch + go) ^ (uint32_t)(match + go)) & 0xFFu,
-                 t_n = ((uint32_t)(scoreN + go) & 0xFFu) * 0x01010101u;
+  V hmax = ZERO;
+  const uint32_t t_mm = O::table_byte(mismatch + go) * 0x01010101u, t_x = O::table_byte(mismatch + go) ^ O::table_byte(match + go),
+                 t_n = O::table_byte(scoreN + go) * 0x01010101u;
   // The letters of a lane's rows are two runs of R consecutive read positions (low half: rows gl R .., high half: rows (gl + 4) R ..): at most three
   // words of 2-bit codes and two of ambiguity bits per run (R <= 32), and all ten are asked for before the first is looked at -- read_nt per row
   // was two loads under `if (row < m)` each, which the compiler turned into 2 R waits for memory one after the other.
@@ -181,59 +246,62 @@ __device__ __forceinline__ SwRes sw_quad16(const uint32_t* __restrict__ rec, uin
       t2[hf] = t;
     }
     tlo[j] = t2[0]; thi[j] = t2[1];
-    Y[j] = pk_splat(-go); E[j] = ZERO; if (KEYS) key[j] = 0;
+    Y[j] = O::splat(-go); E[j] = ZERO; if (KEYS) key[j] = 0;
   }
   int steps = m > 0 ? n + (m + R - 1) / R - 1 : 0;
   for (int d = 32; d > 0; d >>= 1) steps = max(steps, __shfl_xor(steps, d, 64));
 #ifdef SMR_SW16_NOSTEPS                                   // what-if build: set-up and result only (how much of the kernel is not the step loop)
   steps = min(steps, 4);
 #endif
-  uint32_t lastY = pk_bits(pk_splat(-go)), lastF = 0, selcur = PK_SEL_NONE * 0x00010001u;
-  pk16 diag0 = pk_splat(-go);
-  const uint32_t in_y = (uint32_t)(-go) & 0xFFFFu;
+  uint32_t lastY = O::bits(O::splat(-go)), lastF = 0, selcur = O::SEL_NONE * 0x00010001u;
+  V diag0 = O::splat(-go);
+  const uint32_t in_y = O::half_of(-go);
   uint32_t xlo = ((uint32_t)(0x3FFF + gl) << 1) | 1u;
   const bool first = gl == 0;
-  uint32_t wnext = gl < n ? pk_sel_of(ref[dir * gl]) : PK_SEL_NONE;
+  uint32_t wnext = gl < n ? O::sel_of(ref[dir * gl]) : O::SEL_NONE;
 #define SW16_STEP(U)                                                                                                        \
   {                                                                                                                         \
     const uint32_t win = (uint32_t)dpp_quad_bcast<U>((int)wcur);                                                            \
     const uint32_t rY = (uint32_t)dpp_quad_ror1((int)lastY), rF = (uint32_t)dpp_quad_ror1((int)lastF), rS = (uint32_t)dpp_quad_ror1((int)selcur); \
-    const pk16 upY = pk_from(first ? ((rY << 16) | in_y) : rY);                                                             \
-    const pk16 upF = pk_from(first ? (rF << 16) : rF);                                                                      \
-    selcur = first ? ((rS << 16) | win | 0x00040000u) : rS;                                                                 \
+    const V upY = O::from(first ? ((rY << 16) | in_y) : rY);                                                             \
+    const V upF = O::from(first ? (rF << 16) : rF);                                                                      \
+    selcur = first ? ((rS << 16) | win | O::SEL_TO_HI) : rS;                                                                 \
     uint32_t nmask = 0;                                                                                                     \
-    if (HASN) nmask = ((selcur >> 8) & 0x00010001u) * 0xFFFFu;                                                              \
+    if (HASN) nmask = ((selcur >> O::N_SHIFT) & 0x00010001u) * 0xFFFFu;                                                              \
     const uint32_t xhi = xlo + 7u;                                                                                          \
-    pk16 diag = diag0, uy = upY, uf = upF;                                                                                  \
+    V diag = diag0, uy = upY, uf = upF, hprev = ZERO;                                                                                \
     _Pragma("unroll") for (int j = 0; j < R; j++) {                                                                         \
       uint32_t T = perm_b32(thi[j], tlo[j], selcur);                                                                        \
       if (HASN) T = (T & ~nmask) | (TN & nmask);                                                                            \
-      const pk16 a = pk_add(diag, pk_from(T));                                                                              \
-      const pk16 e = pk_max(pk_subs_u(E[j], GE), Y[j]);   /* E is kept clamped at 0 (saturating subtract): e >= 0, so */    \
-      const pk16 f = pk_max(pk_sub(uf, GE), uy);                                                                            \
-      const pk16 h = pk_max(pk_max(a, e), f);             /* h = max(a, e, f, 0) without the fourth operand */               \
+      const V a = O::add(diag, O::from(T));                                                                                  \
+      const V e = O::e_of(E[j], GE, Y[j]);                /* e = max(E - ge, Y, 0): e >= 0, so */                           \
+      const V f = O::max2(O::sub(uf, GE), uy);                                                                              \
+      const V h = O::max3(a, e, f);                       /* h = max(a, e, f, 0) without the fourth operand */               \
       diag = Y[j];                                                                                                          \
-      const pk16 y = pk_sub(h, GO);                                                                                         \
+      const V y = O::sub(h, GO);                                                                                             \
       Y[j] = y; E[j] = e;                                                                                                   \
-      if (KEYS == SW16_KEYS) { const uint32_t hu = pk_bits(h); key[j] = max(key[j], max((hu << 16) | xlo, (hu & 0xFFFF0000u) | xhi)); } \
-      else if (KEYS == SW16_PREFIX) key[j] = pk_bits(pk_max(pk_from(key[j]), h));                                           \
-      else hmax = pk_max(hmax, h);                                                                                          \
+      if (KEYS == SW16_KEYS) { const uint32_t hu = O::bits(h); key[j] = max(key[j], max((hu << 16) | xlo, (hu & 0xFFFF0000u) | xhi)); } \
+      else if (KEYS == SW16_PREFIX) key[j] = O::bits(O::max2(O::from(key[j]), h));                                         \
+      else if (!F16) hmax = O::max2(hmax, h);                                                                               \
+      else if (j & 1) hmax = O::max3(hmax, hprev, h);     /* (the three-operand maximum takes the rows two at a time) */    \
+      else if (j == R - 1) hmax = O::max2(hmax, h);                                                                         \
+      else hprev = h;                                                                                                       \
       uy = y; uf = f;                                                                                                       \
     }                                                                                                                       \
     diag0 = upY;                                                                                                            \
-    lastY = pk_bits(uy); lastF = pk_bits(uf);                                                                               \
+    lastY = O::bits(uy); lastF = O::bits(uf);                                                                               \
     xlo -= 2u;                                                                                                              \
   }
   // (steps beyond a problem's own n + lanes - 1, up to the wave's maximum rounded to a period, meet the selector NONE: values that never reach a maximum)
   for (int t = 0; t < steps; t += 4) {
     const uint32_t wcur = wnext;
     const int cq = t + 4 + gl;
-    wnext = cq < n ? pk_sel_of(ref[dir * cq]) : PK_SEL_NONE;
+    wnext = cq < n ? O::sel_of(ref[dir * cq]) : O::SEL_NONE;
     SW16_STEP(0) SW16_STEP(1) SW16_STEP(2) SW16_STEP(3)
   }
 #undef SW16_STEP
   if (KEYS == SW16_PREFIX) {
-    // (32-bit arithmetic from here: h >= 0, so a half is its row's M_i as it stands)
+    // (32-bit arithmetic from here: h >= 0, so a half is its row's M_i as it stands -- the f16 flavour's after the conversion)
     const int sg = max(max(match, mismatch), max(scoreN, 0));
     int lo = 0, hi = sg * min(m, rem);
     const int below0 = m - 1 - gl * R;                      // rows of the span below the lane's first one (every row's count comes from this number of the task, not from
@@ -243,7 +311,7 @@ __device__ __forceinline__ SwRes sw_quad16(const uint32_t* __restrict__ rec, uin
 #pragma unroll
       for (int hf = 0; hf < 2; hf++) {
         const int below = below0 - 4 * R * hf - j;          // < 0: a row >= m
-        const int mi = below >= 0 ? (int)(hf ? key[j] >> 16 : key[j] & 0xFFFFu) : 0;
+        const int mi = below >= 0 ? O::to_int(hf ? key[j] >> 16 : key[j] & 0xFFFFu) : 0;
         lo = max(lo, mi); hi = max(hi, mi + sg * max(min(below, rem), 0));
       }
     }
@@ -252,8 +320,8 @@ __device__ __forceinline__ SwRes sw_quad16(const uint32_t* __restrict__ rec, uin
     return rs;
   }
   if (KEYS == SW16_SCORE) {
-    const uint32_t hb = pk_bits(hmax);
-    int sc = max((int)(hb & 0xFFFFu), (int)(hb >> 16));
+    const uint32_t hb = O::bits(hmax);
+    int sc = max(O::to_int(hb & 0xFFFFu), O::to_int(hb >> 16));
     for (int d = 2; d > 0; d >>= 1) sc = max(sc, __shfl_xor(sc, d, 64));
     SwRes rs; rs.score = sc; rs.end_ref = -2; rs.end_read = 0xFFFF;       // (end cell not computed: wres_pack makes y = 0xFFFFFFFF of it)
     return rs;
@@ -261,7 +329,7 @@ __device__ __forceinline__ SwRes sw_quad16(const uint32_t* __restrict__ rec, uin
   int bestH = 0, bestcol = 0x1FFFFF, bestrow = 0x1FFFFF;
 #pragma unroll
   for (int j = 0; j < R; j++) {
-    const int h = (int)(key[j] >> 16);
+    const int h = O::to_int(key[j] >> 16);
     const int hf = (key[j] & 1u) ? 0 : 1;
     const int col = 0x3FFF - (int)((key[j] >> 1) & 0x7FFFu);
     const int row = (gl + 4 * hf) * R + j;
@@ -295,9 +363,10 @@ __device__ __forceinline__ SwRes wres_unpack(const uint2 v) {
 #ifndef SW16_WAVES
 #define SW16_WAVES(R) ((R) <= 13 ? 4 : (R) <= 19 ? 3 : 2)
 #endif
-template <int R>
-__global__ void __launch_bounds__(64, SW16_WAVES(R)) k_sw16(DReads rd, DIndex ix, DParams P, const WTask* __restrict__ tk, const uint32_t* __restrict__ tidx1,
-                                                           const uint32_t* __restrict__ tidx2, const uint32_t* __restrict__ tidx3, const unsigned long long* __restrict__ wc, uint2* __restrict__ res) {
+// (the body of k_sw16<R> and k_sw16h<R>: the same passes over the three lists, the arithmetic of the flavour)
+template <int R, bool F16>
+__device__ __forceinline__ void sw16_lists(const DReads& rd, const DIndex& ix, const DParams& P, const WTask* __restrict__ tk, const uint32_t* __restrict__ tidx1,
+                                           const uint32_t* __restrict__ tidx2, const uint32_t* __restrict__ tidx3, const unsigned long long* __restrict__ wc, uint2* __restrict__ res) {
   const int lane = lane_id(), g = lane >> 2, gl = lane & 3;
   // three lists: tidx[0, ntA) = tasks scored with their end cells, tidx2[0, ntB) = tasks of which only the score is asked, tidx3[0, ntC) = prefix
   // tasks (an interval from the first columns; last, so that the sixteen problems of a wave run about the same number of steps)
@@ -353,14 +422,25 @@ __global__ void __launch_bounds__(64, SW16_WAVES(R)) k_sw16(DReads rd, DIndex ix
     SwRes s;
     const bool hasn = __any(hn);
 #define SW16_ARGS rec, len, reversed, m, aq, ref, n, P.match, P.mismatch, P.score_N, P.gap_open, P.gap_ext, dir
-    if (keys) { if (hasn) s = sw_quad16<R, true, SW16_KEYS>(SW16_ARGS); else s = sw_quad16<R, false, SW16_KEYS>(SW16_ARGS); }
-    else if (prefix) { if (hasn) s = sw_quad16<R, true, SW16_PREFIX>(SW16_ARGS, rem); else s = sw_quad16<R, false, SW16_PREFIX>(SW16_ARGS, rem); }
-    else { if (hasn) s = sw_quad16<R, true, SW16_SCORE>(SW16_ARGS); else s = sw_quad16<R, false, SW16_SCORE>(SW16_ARGS); }
+    if (keys) { if (hasn) s = sw_quad16<R, true, SW16_KEYS, F16>(SW16_ARGS); else s = sw_quad16<R, false, SW16_KEYS, F16>(SW16_ARGS); }
+    else if (prefix) { if (hasn) s = sw_quad16<R, true, SW16_PREFIX, F16>(SW16_ARGS, rem); else s = sw_quad16<R, false, SW16_PREFIX, F16>(SW16_ARGS, rem); }
+    else { if (hasn) s = sw_quad16<R, true, SW16_SCORE, F16>(SW16_ARGS); else s = sw_quad16<R, false, SW16_SCORE, F16>(SW16_ARGS); }
 #undef SW16_ARGS
 #undef SW16_LIST_OF
     // (the task's slot is asked for again rather than kept across the Smith-Waterman loop, whose rows take every register the occupancy allows)
     if (have && gl == 0) res[tidx[ti]] = wres_pack(s);
   }
+}
+template <int R>
+__global__ void __launch_bounds__(64, SW16_WAVES(R)) k_sw16(DReads rd, DIndex ix, DParams P, const WTask* __restrict__ tk, const uint32_t* __restrict__ tidx1,
+                                                           const uint32_t* __restrict__ tidx2, const uint32_t* __restrict__ tidx3, const unsigned long long* __restrict__ wc, uint2* __restrict__ res) {
+  sw16_lists<R, false>(rd, ix, P, tk, tidx1, tidx2, tidx3, wc, res);
+}
+// the f16 flavour (Sw16Ops<true>): the host launches it instead of k_sw16<R> where sw_h16_fits holds for the scheme and 8 R rows
+template <int R>
+__global__ void __launch_bounds__(64, SW16_WAVES(R)) k_sw16h(DReads rd, DIndex ix, DParams P, const WTask* __restrict__ tk, const uint32_t* __restrict__ tidx1,
+                                                            const uint32_t* __restrict__ tidx2, const uint32_t* __restrict__ tidx3, const unsigned long long* __restrict__ wc, uint2* __restrict__ res) {
+  sw16_lists<R, true>(rd, ix, P, tk, tidx1, tidx2, tidx3, wc, res);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -353,6 +353,15 @@ class Engine:
         self._chk(self.L.smr_sw16_launches(self.h, out), "smr_sw16_launches")
         return dict(zip((13, 19, 26, 32), out[:4])), dict(zip((13, 19, 26, 32), out[4:]))
 
+    def sw16_f16(self, set_to=-1):
+        """k_sw16h, the packed-f16 flavour of k_sw16, where the scoring scheme allows it (smr_sw16_f16): set_to 0 / 1 selects, anything else only
+        queries; -> (the mode in use, launches of k_sw16h since the engine was created)"""
+        n = C.c_uint64(0)
+        mode = self.L.smr_sw16_f16(self.h, int(set_to), C.byref(n))
+        if mode < 0:
+            self._chk(mode, "smr_sw16_f16")
+        return mode, int(n.value)
+
     def sw_long_rows(self, m):
         """the strip height (8, 10 ... 24) the long-read Smith-Waterman scores a span of m rows with (smr_sw_long_rows)"""
         return self.L.smr_sw_long_rows(int(m))
