@@ -21,6 +21,9 @@
 // --otu device (needs --pack device): the members of otu_map.txt come from one smr_otu_part call per (index, part) (smr_report_add_otu) and
 // aligned_denovo.* from one smr_fastx_denovo call (smr_report_add_denovo) instead of read by read; the default, --otu host, is smr_report_add.
 // Single reads and interleaved mates; refused with two reads files.  Every output file is the same.
+// --zip device (needs --split device and gzipped reports): aligned.* / other.*, and with --otu device aligned_denovo.*, are deflated by the
+// DEFLATE kernels where the split leaves them (smr_fastx_split_gz / smr_fastx_denovo_gz) and appended to the .gz files as gzip members
+// (smr_report_add_fastx_gz / _add_denovo_gz); every file inflates to what --zip host writes.
 // Build:  g++ -std=c++17 -O2 examples/smr_align.cpp -Iinclude -Lsortmerna_amd/lib -lsmr_hip -Wl,-rpath,$PWD/sortmerna_amd/lib -o smr_align
 // There is no CPU fallback: without a HIP device smr_create fails and the program exits like the reference does (ERR + exit 1).
 #include <cstdint>
@@ -45,7 +48,7 @@ int main(int argc, char** argv) {
   smr_params base; smr_params_default(&base);
   double evalue = 1.0;
   int device = 0;
-  bool pack_device = false, split_device = false, rows_device = false, pair_device = false, otu_device = false;
+  bool pack_device = false, split_device = false, rows_device = false, pair_device = false, otu_device = false, zip_device = false;
   bool id_given = false, cov_given = false;
   smr_report_opts ro; memset(&ro, 0, sizeof ro);
   for (int i = 1; i < argc; i++) {
@@ -74,6 +77,7 @@ int main(int argc, char** argv) {
     else if (a == "-split" || a == "--split") { const std::string v = val(); if (v != "host" && v != "device") die("--split: host or device"); split_device = v == "device"; }
     else if (a == "-rows" || a == "--rows") { const std::string v = val(); if (v != "host" && v != "device") die("--rows: host or device"); rows_device = v == "device"; }
     else if (a == "-pairwise" || a == "--pairwise") { const std::string v = val(); if (v != "host" && v != "device") die("--pairwise: host or device"); pair_device = v == "device"; }
+    else if (a == "-zip" || a == "--zip") { const std::string v = val(); if (v != "host" && v != "device") die("--zip: host or device"); zip_device = v == "device"; }
     else if (a == "-otu" || a == "--otu") { const std::string v = val(); if (v != "host" && v != "device") die("--otu: host or device"); otu_device = v == "device"; }
     else if (a == "-otu_map" || a == "--otu_map") ro.otu_map = 1;
     else if (a == "-de_novo_otu" || a == "--de_novo_otu") ro.denovo = 1;
@@ -101,7 +105,7 @@ int main(int argc, char** argv) {
       printf("usage: smr_align --ref DB.fasta --gumbel LAMBDA K [--idx PREFIX] [--ref ...] --reads READS.fa|fq[.gz] [--reads MATES] [--out DIR]\n"
              "       [-e EVALUE] [-num_alignments N] [-no-best] [-min_lis N] [-num_seeds N] [-edges N] [-full_search] [-F|-R]\n"
              "       [-match N -mismatch N -gap_open N -gap_ext N] [-device K] [--fastx] [--other] [--blast '0' | '1 cigar qcov qstrand'] [--sam [-SQ]]\n"
-             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [--rows host|device] [--pairwise host|device] [-otu_map [-id X] [-coverage X]] [-de_novo_otu] [--otu host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
+             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [--zip host|device] [--rows host|device] [--pairwise host|device] [-otu_map [-id X] [-coverage X]] [-de_novo_otu] [--otu host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
       return 0;
     } else die("unknown option " + a);
   }
@@ -127,6 +131,14 @@ int main(int argc, char** argv) {
   // which is outside this library: they must be given -- from the reference's log ("Gumbel lambda = ..", "Gumbel K = ..") for the same DB
   // and the same -match/-mismatch/-gap_open/-gap_ext.  No default is assumed: a silent guess would classify a different set of reads.
   for (auto& d : dbs) if (!d.has_gumbel) die("--gumbel LAMBDA K is required after every --ref (see --help): the values of the reference's log for this DB and scoring scheme");
+  if (zip_out == -1) {                                      // gzip reports for a gzip reads file
+    unsigned char mg[2] = {0, 0};
+    if (FILE* fz = fopen(reads_paths[0].c_str(), "rb")) { if (fread(mg, 1, 2, fz) != 2) mg[0] = 0; fclose(fz); }
+    zip_out = (mg[0] == 0x1f && mg[1] == 0x8b) ? 1 : 0;
+  }
+  ro.zip_out = zip_out;
+  if (zip_device && !split_device) die("--zip device compresses the aligned.* / other.* streams where --split device leaves them: it needs --split device");
+  if (zip_device && !zip_out) die("--zip device writes gzip members: the reports of this run are not gzipped (a plain reads file without -zip-out 1, or -zip-out 0)");
   char err[512] = "";
   // reads (Readfeed::next -> Read::init, readfeed.hpp:124 / read.cpp:264-347)
   // (all cores parse and 2-bit pack the FASTA / FASTQ / .gz file; the text stays mapped for the report writers)
@@ -147,12 +159,6 @@ int main(int argc, char** argv) {
   }
   if (n == 0) min_len = 0;
   const bool is_fastq = smr_reads_is_fastq(rf[0]) != 0;
-  if (zip_out == -1) {                                      // gzip reports for a gzip reads file
-    unsigned char mg[2] = {0, 0};
-    if (FILE* fz = fopen(reads_paths[0].c_str(), "rb")) { if (fread(mg, 1, 2, fz) != 2) mg[0] = 0; fclose(fz); }
-    zip_out = (mg[0] == 0x1f && mg[1] == 0x8b) ? 1 : 0;
-  }
-  ro.zip_out = zip_out;
   const bool paired = rf.size() == 2 || ro.paired_in || ro.paired_out;
   if (rf.size() == 2 && smr_reads_count(rf[0]) != smr_reads_count(rf[1])) die("the two --reads files hold different numbers of reads");
   if (rf.size() == 1 && paired && (smr_reads_count(rf[0]) & 1)) die("-paired_in / -paired_out with one file: odd number of reads");
@@ -251,9 +257,16 @@ int main(int argc, char** argv) {
     so.paired_in = ro.paired_in; so.paired_out = ro.paired_out; so.out2 = ro.out2; so.sout = ro.sout; so.want_aligned = ro.fastx; so.want_other = ro.other;
     uint64_t off[9], need = 0;
     if (smr_batch_select(gpu, 0) != SMR_OK || smr_fastx_split(gpu, so.layout == 2 ? 1 : -1, &so, nullptr, nullptr, 0, off, &need) != SMR_OK) die(smr_last_error(gpu));
+    if (zip_device) {                                        // the streams are deflated where they are; only gzip members cross the bus
+      uint64_t gz_off[9];
+      std::vector<uint8_t> gz((size_t)smr_gzip_bound(need, need / smr_gzip_chunk() + 8) + 1);      // (at most one short chunk per stream)
+      if (smr_fastx_split_gz(gpu, so.layout == 2 ? 1 : -1, &so, nullptr, gz.data(), gz.size(), gz_off, off, &need) != SMR_OK) die(smr_last_error(gpu));
+      if (smr_report_add_fastx_gz(rep, gz.data(), gz_off) != SMR_OK) die(smr_report_last_error(rep));
+    } else {
     std::vector<uint8_t> fx((size_t)need + 1);
     if (smr_fastx_split(gpu, so.layout == 2 ? 1 : -1, &so, nullptr, fx.data(), need, off, &need) != SMR_OK) die(smr_last_error(gpu));
     if (smr_report_add_fastx(rep, fx.data(), off) != SMR_OK) die(smr_report_last_error(rep));
+    }
     smr_report_skip_fastx(rep, 1);
   }
   // --rows device: the SAM / BLAST rows of every (index, part) in one call each, after all alignment (the call order of smr_idcov_part); a run of
@@ -312,9 +325,16 @@ int main(int argc, char** argv) {
     so.paired_in = ro.paired_in; so.paired_out = ro.paired_out; so.out2 = ro.out2; so.sout = ro.sout;
     uint64_t off[5], need = 0;
     if (smr_batch_select(gpu, 0) != SMR_OK || smr_fastx_denovo(gpu, -1, &so, nullptr, nullptr, 0, off, &need) != SMR_OK) die(smr_last_error(gpu));
+    if (zip_device) {
+      uint64_t gz_off[5];
+      std::vector<uint8_t> gz((size_t)smr_gzip_bound(need, need / smr_gzip_chunk() + 4) + 1);
+      if (smr_fastx_denovo_gz(gpu, -1, &so, nullptr, gz.data(), gz.size(), gz_off, off, &need) != SMR_OK) die(smr_last_error(gpu));
+      if (smr_report_add_denovo_gz(rep, gz.data(), gz_off) != SMR_OK) die(smr_report_last_error(rep));
+    } else {
     std::vector<uint8_t> fx((size_t)need + 1);
     if (need && smr_fastx_denovo(gpu, -1, &so, nullptr, fx.data(), need, off, &need) != SMR_OK) die(smr_last_error(gpu));
     if (smr_report_add_denovo(rep, fx.data(), off) != SMR_OK) die(smr_report_last_error(rep));
+    }
     smr_report_skip_denovo(rep, 1);
   }
   // does the report take the reads one by one at all: for aligned.* / other.*, for rows / pairwise text, for the map or aligned_denovo.* that no

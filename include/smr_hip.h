@@ -400,6 +400,35 @@ int smr_otu_sort_batch(smr_ctx*, uint32_t n, const uint32_t* keys, uint32_t key_
  * unless both mates are de novo reads, and otherwise BOTH mates written, the one that is no de novo read to file 0. */
 int smr_fastx_denovo(smr_ctx*, int mates, const smr_fxsplit_opts*, const uint8_t* dn /* NULL: the batches' own counters */,
                      uint8_t* bytes, uint64_t cap, uint64_t off[5], uint64_t* need);
+
+/* ---- gzip on the device ----------------------------------------------------------------------------------------------------------------
+ * A DEFLATE compressor in HIP kernels.  A byte range (a "stream") is cut into chunks of smr_gzip_chunk() plain bytes, the last one may be
+ * shorter, and every chunk becomes one complete gzip member: a 10-byte header (mtime 0, no name), dynamic-Huffman DEFLATE data whose
+ * back-references stay inside the chunk (or stored blocks where coding would not make the member smaller), CRC-32 and ISIZE, both computed
+ * on the device.  The members of a stream lie back to back -- a multi-member gzip file, as the reference's merged per-thread outputs are;
+ * an empty stream gives no byte.  The same bytes in give the same bytes out, whatever else is in the call.
+ * smr_gzip_bound: no output for plain_bytes in n_chunks members is larger -- per member 18 + its plain bytes + 5 per stored block of at most
+ * 65 535 bytes; for the ceil(len / chunk) members of one stream of len bytes the value is exactly that sum. */
+uint32_t smr_gzip_chunk(void);
+uint64_t smr_gzip_bound(uint64_t plain_bytes, uint64_t n_chunks);
+/* A building block and the test seam: stream k is plain[off[k], off[k + 1]) of a HOST buffer (off ascending, n_streams + 1 entries); its
+ * members are gz[gz_off[k], gz_off[k + 1]), gz_off[n_streams] = *need.  gz == NULL: the sizes only (this costs the matching and the code
+ * building, i.e. most of a compression: with smr_gzip_bound one call is enough).  cap < *need: SMR_ERR_CAPACITY, gz_off and *need valid,
+ * nothing written.  Otherwise exactly *need bytes are written.  gz may be pinned memory. */
+int smr_gzip_batch(smr_ctx*, const uint8_t* plain, const uint64_t* off /* n_streams + 1 */, uint32_t n_streams,
+                   uint8_t* gz, uint64_t cap, uint64_t* gz_off /* n_streams + 1 */, uint64_t* need);
+/* smr_fastx_split / smr_fastx_denovo whose streams stay on the device and cross the bus as gzip members: the same measure, scan and copy
+ * kernels, then the compressor on the engine's stream.  Routing, layouts, `hit` / `dn`, refusals and the state contract are the plain
+ * calls'; plain_off is what the plain call returns in `off`; stream k is gz[gz_off[k], gz_off[k + 1]), the last offset = *need, an empty
+ * stream has no byte.  gz == NULL: sizes only (a full compression but for the bit packing); cap < *need: SMR_ERR_CAPACITY with the offsets and
+ * *need valid and nothing written; otherwise exactly *need bytes.  The calls change no stored state and may be repeated: the same bytes. */
+int smr_fastx_split_gz(smr_ctx*, int mates, const smr_fxsplit_opts*, const uint8_t* hit,
+                       uint8_t* gz, uint64_t cap, uint64_t gz_off[9], uint64_t plain_off[9], uint64_t* need);
+int smr_fastx_denovo_gz(smr_ctx*, int mates, const smr_fxsplit_opts*, const uint8_t* dn,
+                        uint8_t* gz, uint64_t cap, uint64_t gz_off[5], uint64_t plain_off[5], uint64_t* need);
+/* HIP-event milliseconds of the last of the three calls above: {matching + CRC, code building, bit packing, scan + compaction, bytes D2H}
+ * (the last three 0 for a sizes-only call) */
+int smr_gzip_times(const smr_ctx*, double ms[5]);
 /* Forget all per-read results/counters of the resident batch (reads stay resident). */
 int smr_state_reset(smr_ctx*);
 
@@ -689,6 +718,13 @@ int smr_report_skip_otu(smr_report*, int on);
 int smr_report_add_denovo(smr_report*, const uint8_t* bytes, const uint64_t off[5]);
 /* on != 0: smr_report_add / smr_report_add_pair leave aligned_denovo.* alone (smr_report_add_denovo writes them); everything else is unaffected */
 int smr_report_skip_denovo(smr_report*, int on);
+/* The gzip members of smr_fastx_split_gz / smr_fastx_denovo_gz: stream k is appended AS IT IS to the open .gz file that smr_report_add_fastx /
+ * smr_report_add_denovo would deflate stream k into.  What the file holds from plain calls is closed as a gzip member first and a later plain
+ * call begins a new one, so any mix of calls leaves a valid multi-member gzip file that inflates to the streams in call order.  SMR_ERR_ARG,
+ * and nothing is appended, when the report was not opened with zip_out, when a stream that is not empty has no open file, or when the offsets
+ * decrease.  A report that never sees one of these calls writes the bytes it always wrote. */
+int smr_report_add_fastx_gz(smr_report*, const uint8_t* gz, const uint64_t gz_off[9]);
+int smr_report_add_denovo_gz(smr_report*, const uint8_t* gz, const uint64_t gz_off[5]);
 /* *total_otu = lines of otu_map.txt (Readstats::total_otu, for smr_summary), stored when smr_report_close runs: the pointer must live until then */
 int smr_report_otu_count(smr_report*, uint64_t* total_otu);
 /* One otu_map.txt for a run whose reads went through several report objects (one per device, each fed a contiguous shard of the reads in input

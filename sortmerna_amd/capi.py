@@ -71,6 +71,7 @@ class Kprof(C.Structure):
 
 
 EXPORTS = [
+    "smr_gzip_chunk", "smr_gzip_bound", "smr_gzip_batch", "smr_fastx_split_gz", "smr_fastx_denovo_gz", "smr_gzip_times", "smr_report_add_fastx_gz", "smr_report_add_denovo_gz",
     "smr_otu_part", "smr_otu_times", "smr_otu_sort_batch", "smr_fastx_denovo", "smr_report_add_otu", "smr_report_skip_otu", "smr_report_add_denovo", "smr_report_skip_denovo",
     "smr_params_default", "smr_params_refused", "smr_index_load_files", "smr_index_build", "smr_index_build_gpu", "smr_index_write_files", "smr_index_save", "smr_index_load_flat", "smr_index_selfcheck", "smr_index_free",
     "smr_index_get_info", "smr_minimal_score", "smr_minimal_score_split", "smr_refstats_corrected_split", "smr_reads_pack", "smr_reads_load_fastx", "smr_reads_load_fastx_mt", "smr_reads_load_fastx_text", "smr_reads_is_fastq", "smr_reads_record_text", "smr_reads_free", "smr_reads_slice",
@@ -268,6 +269,22 @@ def bind(L):
     L.smr_otu_sort_batch.argtypes = [vp, u32, vp, u32, vp]
     L.smr_fastx_denovo.restype = i32
     L.smr_fastx_denovo.argtypes = [vp, i32, C.POINTER(FxSplitOpts), vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.smr_gzip_chunk.restype = u32
+    L.smr_gzip_chunk.argtypes = []
+    L.smr_gzip_bound.restype = u64
+    L.smr_gzip_bound.argtypes = [u64, u64]
+    L.smr_gzip_batch.restype = i32
+    L.smr_gzip_batch.argtypes = [vp, vp, C.POINTER(u64), u32, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.smr_fastx_split_gz.restype = i32
+    L.smr_fastx_split_gz.argtypes = [vp, i32, C.POINTER(FxSplitOpts), vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.smr_fastx_denovo_gz.restype = i32
+    L.smr_fastx_denovo_gz.argtypes = [vp, i32, C.POINTER(FxSplitOpts), vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.smr_gzip_times.restype = i32
+    L.smr_gzip_times.argtypes = [vp, C.POINTER(C.c_double)]
+    L.smr_report_add_fastx_gz.restype = i32
+    L.smr_report_add_fastx_gz.argtypes = [vp, vp, C.POINTER(u64)]
+    L.smr_report_add_denovo_gz.restype = i32
+    L.smr_report_add_denovo_gz.argtypes = [vp, vp, C.POINTER(u64)]
     L.smr_report_add_otu.restype = i32
     L.smr_report_add_otu.argtypes = [vp, u32, u32, vp, u64, vp, u64, i32]
     L.smr_report_skip_otu.restype = i32

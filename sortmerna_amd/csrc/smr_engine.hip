@@ -20,6 +20,7 @@
 #include "smr_rows.hpp"
 #include "smr_pairwise.hpp"
 #include "smr_otu.hpp"
+#include "smr_gzip.hpp"
 #include "smr_ibuild.hpp"
 #include "smr_pgbuild.hpp"
 #include "smr_hostmem.hpp"
@@ -164,6 +165,18 @@ struct OtuScratch {
   ~OtuScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
+// scratch and staging of the DEFLATE kernels (smr_gzip.hpp), grow-only
+struct GzScratch {
+  DevBuf<uint8_t> in, slots, out; DevBuf<GzChunk> chunks; DevBuf<GzCode> codes; DevBuf<unsigned long long> slot_off, sizes;
+  DevBuf<uint32_t> crc_tab, crc, tok, freq, ntok;
+  hipEvent_t ev[4] = {};
+  double ms[5] = {0, 0, 0, 0, 0};         // of the last call: match, code build, encode, scan + compact, D2H
+  GzScratch() = default;
+  GzScratch(const GzScratch&) = delete;
+  GzScratch& operator=(const GzScratch&) = delete;
+  ~GzScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
 struct smr_ctx {
   const Tuning tune;                      // the environment switches as smr_create found them (smr_tuning.hpp)
   explicit smr_ctx(const Tuning& t) : tune(t) {}
@@ -242,6 +255,7 @@ struct smr_ctx {
   RowsScratch rows;
   PairScratch pair;
   OtuScratch otu;
+  GzScratch gz;
 };
 struct KpSave { double ms[KP_COUNT]; uint64_t l[KP_COUNT]; };
 
@@ -890,6 +904,7 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
 #include "smr_engine_import.hpp"
 #include "smr_engine_export.hpp"
 #include "smr_engine_fastx.hpp"
+#include "smr_engine_gzip.hpp"
 #include "smr_engine_fxsplit.hpp"
 #include "smr_engine_rows.hpp"
 #include "smr_engine_pairwise.hpp"

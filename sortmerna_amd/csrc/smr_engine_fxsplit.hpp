@@ -11,28 +11,34 @@ FxsSrc fxs_src(const Batch& B) {
 }
 }  // namespace
 
-extern "C" int smr_fastx_split(smr_ctx* c, int mates, const smr_fxsplit_opts* o, const uint8_t* hit, uint8_t* bytes, uint64_t cap, uint64_t off[9], uint64_t* need) {
-  if (!c || !o || !off) return SMR_ERR_ARG;
+namespace {
+// smr_fastx_split (zip = false: `bytes` takes the streams, `off` their offsets) and smr_fastx_split_gz (zip = true: the streams stay on the
+// device and go through gz_run, `bytes` takes the gzip members, gz_off their offsets, `off` what the plain call would have returned)
+int fxs_split_impl(smr_ctx* c, const char* who, bool zip, int mates, const smr_fxsplit_opts* o, const uint8_t* hit, uint8_t* bytes, uint64_t cap, uint64_t off[9],
+                   uint64_t gz_off[9], uint64_t* need) {
+  if (!c || !o || !off || (zip && (!gz_off || !need))) return SMR_ERR_ARG;
+  const std::string W(who);
   for (int k = 0; k < 9; k++) off[k] = 0;
+  if (zip) for (int k = 0; k < 9; k++) gz_off[k] = 0;
   if (need) *need = 0;
-  if (o->layout < 0 || o->layout > 2) { set_err(c, "smr_fastx_split: layout must be 0 (single reads), 1 (mates interleaved) or 2 (mates in batch `mates`)"); return SMR_ERR_ARG; }
+  if (o->layout < 0 || o->layout > 2) { set_err(c, W + ": layout must be 0 (single reads), 1 (mates interleaved) or 2 (mates in batch `mates`)"); return SMR_ERR_ARG; }
   Batch& A = *c->b;
   const Batch* M = nullptr;
   if (o->layout == 2) {
-    if (mates < 0 || mates >= SMR_MAX_BATCHES || &c->bt[mates] == &A) { set_err(c, "smr_fastx_split: layout 2 takes the mates from another batch than the selected one"); return SMR_ERR_ARG; }
+    if (mates < 0 || mates >= SMR_MAX_BATCHES || &c->bt[mates] == &A) { set_err(c, W + ": layout 2 takes the mates from another batch than the selected one"); return SMR_ERR_ARG; }
     M = &c->bt[mates];
   }
   if (o->layout != 0 && ((o->paired_in && o->paired_out) || (o->sout && (o->paired_in || o->paired_out)))) {      // what smr_report_open refuses
-    set_err(c, "smr_fastx_split: invalid combination of paired_in / paired_out / sout"); return SMR_ERR_ARG;
+    set_err(c, W + ": invalid combination of paired_in / paired_out / sout"); return SMR_ERR_ARG;
   }
   if (!A.fx_kept || (M && !M->fx_kept)) {
-    set_err(c, "smr_fastx_split: the batch does not hold its text (upload it with smr_reads_upload_fastx* and SMR_FASTX_KEEP)"); return SMR_ERR_STATE;
+    set_err(c, W + ": the batch does not hold its text (upload it with smr_reads_upload_fastx* and SMR_FASTX_KEEP)"); return SMR_ERR_STATE;
   }
-  if (o->layout == 1 && (A.n & 1u)) { set_err(c, "smr_fastx_split: layout 1 with an odd number of reads (" + std::to_string(A.n) + ")"); return SMR_ERR_ARG; }
-  if (M && M->n != A.n) { set_err(c, "smr_fastx_split: " + std::to_string(A.n) + " reads, " + std::to_string(M->n) + " mates"); return SMR_ERR_ARG; }
-  if (M && M->fx_fastq != A.fx_fastq) { set_err(c, "smr_fastx_split: FASTA reads with FASTQ mates (or the other way round)"); return SMR_ERR_ARG; }
+  if (o->layout == 1 && (A.n & 1u)) { set_err(c, W + ": layout 1 with an odd number of reads (" + std::to_string(A.n) + ")"); return SMR_ERR_ARG; }
+  if (M && M->n != A.n) { set_err(c, W + ": " + std::to_string(A.n) + " reads, " + std::to_string(M->n) + " mates"); return SMR_ERR_ARG; }
+  if (M && M->fx_fastq != A.fx_fastq) { set_err(c, W + ": FASTA reads with FASTQ mates (or the other way round)"); return SMR_ERR_ARG; }
   const uint64_t n64 = (uint64_t)A.n * (M ? 2u : 1u);
-  if (n64 >= 0xFFFFFFFFull) { set_err(c, "smr_fastx_split: 2^32 - 1 records or more"); return SMR_ERR_CAPACITY; }
+  if (n64 >= 0xFFFFFFFFull) { set_err(c, W + ": 2^32 - 1 records or more"); return SMR_ERR_CAPACITY; }
   if (n64 == 0) return SMR_OK;
   HIPCHK(c, hipSetDevice(c->device));
   FxSplitScratch& S = c->fxs;
@@ -64,8 +70,18 @@ extern "C" int smr_fastx_split(smr_ctx* c, int mates, const smr_fxsplit_opts* o,
   float f = 0;
   if (hipEventElapsedTime(&f, S.ev[0], S.ev[1]) == hipSuccess) S.ms[0] = f;
   if (hipEventElapsedTime(&f, S.ev[1], S.ev[2]) == hipSuccess) S.ms[1] = f;
+  if (zip) {                                           // the streams are written where the plain call stages them, and compressed from there
+    *need = 0;
+    if (total == 0) return SMR_OK;
+    if (S.out.cap() < total + 4u && (rc = S.out.alloc(c, (size_t)((total + (total >> 3) + 4095u) & ~4095ull)))) return rc;
+    const uint32_t quads = (n + 3u) / 4u, blocks = std::max(1u, std::min<uint32_t>((quads + 3u) / 4u, (uint32_t)c->n_cu * 16u));
+    launch(c, k_fxs_copy, dim3(blocks), dim3(256), 0, n, D, a, b, (const uint4*)S.rec, (const unsigned long long*)S.woff, (const unsigned long long*)S.part,
+           (const unsigned long long*)S.tot, S.out);
+    HIPCHK(c, hipGetLastError());
+    return gz_run(c, who, S.out, off, 8, bytes, cap, gz_off, need);
+  }
   if (!bytes) return SMR_OK;
-  if (cap < total) { set_err(c, "smr_fastx_split: the streams take " + std::to_string(total) + " bytes, the buffer has " + std::to_string(cap)); return SMR_ERR_CAPACITY; }
+  if (cap < total) { set_err(c, W + ": the streams take " + std::to_string(total) + " bytes, the buffer has " + std::to_string(cap)); return SMR_ERR_CAPACITY; }
   if (total == 0) return SMR_OK;
   if (S.out.cap() < total + 4u && (rc = S.out.alloc(c, (size_t)((total + (total >> 3) + 4095u) & ~4095ull)))) return rc;      // (the next, slightly larger call fits as well)
   const uint32_t quads = (n + 3u) / 4u, blocks = std::max(1u, std::min<uint32_t>((quads + 3u) / 4u, (uint32_t)c->n_cu * 16u));
@@ -80,6 +96,14 @@ extern "C" int smr_fastx_split(smr_ctx* c, int mates, const smr_fxsplit_opts* o,
   if (hipEventElapsedTime(&f, S.ev[3], S.ev[4]) == hipSuccess) S.ms[2] = f;
   if (hipEventElapsedTime(&f, S.ev[4], S.ev[5]) == hipSuccess) S.ms[3] = f;
   return SMR_OK;
+}
+}  // namespace
+extern "C" int smr_fastx_split(smr_ctx* c, int mates, const smr_fxsplit_opts* o, const uint8_t* hit, uint8_t* bytes, uint64_t cap, uint64_t off[9], uint64_t* need) {
+  return fxs_split_impl(c, "smr_fastx_split", false, mates, o, hit, bytes, cap, off, nullptr, need);
+}
+extern "C" int smr_fastx_split_gz(smr_ctx* c, int mates, const smr_fxsplit_opts* o, const uint8_t* hit, uint8_t* gz, uint64_t cap, uint64_t gz_off[9], uint64_t plain_off[9],
+                                  uint64_t* need) {
+  return fxs_split_impl(c, "smr_fastx_split_gz", true, mates, o, hit, gz, cap, plain_off, gz_off, need);
 }
 extern "C" int smr_fastx_split_times(const smr_ctx* c, double ms[4]) {
   if (!c || !ms) return SMR_ERR_ARG;

@@ -1,0 +1,137 @@
+// smr_engine_gzip.hpp -- host side of the DEFLATE kernels (smr_gzip.hpp; included by smr_engine.hip): gz_run, the dispatcher that turns byte
+// ranges of a device buffer into gzip members and copies only those to the host, and smr_gzip_batch, the same over a host buffer (a building
+// block and the tests' seam).  smr_fastx_split_gz / smr_fastx_denovo_gz (smr_engine_fxsplit.hpp, smr_engine_otu.hpp) hand it the streams
+// their plain siblings would have copied back.
+//
+// The tokens of a chunk take four bytes per plain byte, so the chunks are worked on in rounds of GZ_ROUND; the members wait in worst-case
+// slots (the stored form's size) until all sizes are known, then one scan and one compaction put them back to back.
+
+namespace {
+#define GZ_ROUND 1024u           // chunks per round: 256 MiB of tokens
+
+// the CRC-32 byte table (reflected, 0xEDB88320) and, for k = 0 .. 7, the GF(2) operator "the register after 2^k slices of zero bytes"
+void gz_crc_words(uint32_t* w) {
+  for (uint32_t i = 0; i < 256u; i++) {
+    uint32_t x = i;
+    for (int k = 0; k < 8; k++) x = (x & 1u) ? 0xEDB88320u ^ (x >> 1) : x >> 1;
+    w[i] = x;
+  }
+  uint32_t m[32], q[32];
+  for (uint32_t k = 0; k < 32u; k++) m[k] = w[(1u << k) & 0xFFu] ^ ((1u << k) >> 8);      // one zero byte
+  auto square = [&]() {
+    for (uint32_t k = 0; k < 32u; k++) { uint32_t y = 0; for (uint32_t b = 0; b < 32u; b++) if ((m[k] >> b) & 1u) y ^= m[b]; q[k] = y; }
+    memcpy(m, q, sizeof m);
+  };
+  uint32_t bytes = 1;
+  while (bytes < GZ_SLICE) { square(); bytes *= 2u; }
+  for (uint32_t k = 0; k < 8u; k++) { memcpy(w + 256u + 32u * k, m, sizeof m); square(); }
+}
+
+// n_streams ranges [off[k], off[k + 1]) of d_in -> their gzip members, back to back, in gz (may be null: sizes only); gz_off[n_streams + 1]
+int gz_run(smr_ctx* c, const char* who, const uint8_t* d_in, const uint64_t* off, uint32_t n_streams, uint8_t* gz, uint64_t cap, uint64_t* gz_off, uint64_t* need) {
+  GzScratch& S = c->gz;
+  for (double& m : S.ms) m = 0.0;
+  for (uint32_t k = 0; k <= n_streams; k++) gz_off[k] = 0;
+  if (need) *need = 0;
+  std::vector<GzChunk> chunks;
+  std::vector<unsigned long long> slot_off;
+  std::vector<uint64_t> first(n_streams + 1u);
+  unsigned long long slots_bytes = 0;
+  for (uint32_t k = 0; k < n_streams; k++) {
+    first[k] = chunks.size();
+    for (uint64_t at = off[k]; at < off[k + 1]; at += GZ_CHUNK) {
+      GzChunk ck; ck.src = at; ck.len = (uint32_t)std::min<uint64_t>(GZ_CHUNK, off[k + 1] - at); ck.pad = 0;
+      chunks.push_back(ck); slot_off.push_back(slots_bytes);
+      slots_bytes += gz_slot_size(ck.len);
+    }
+  }
+  first[n_streams] = chunks.size();
+  if (chunks.empty()) return SMR_OK;
+  if (chunks.size() >= 0x7FFFFFFFull) { set_err(c, std::string(who) + ": 2^31 - 1 chunks or more"); return SMR_ERR_CAPACITY; }
+  const uint32_t nc = (uint32_t)chunks.size(), round = std::min(nc, GZ_ROUND);
+  for (auto& e : S.ev) if (!e) HIPCHK(c, hipEventCreate(&e));
+  int rc;
+  if (!S.crc_tab) {
+    uint32_t w[GZ_CRC_WORDS];
+    gz_crc_words(w);
+    if ((rc = S.crc_tab.alloc(c, GZ_CRC_WORDS))) return rc;
+    HIPCHK(c, hipMemcpyAsync(S.crc_tab, w, sizeof w, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));        // (w leaves the scope)
+  }
+  if ((rc = S.chunks.reserve(c, nc)) || (rc = S.slot_off.reserve(c, nc)) || (rc = S.sizes.reserve(c, (size_t)nc + 1u)) || (rc = S.codes.reserve(c, nc)) ||
+      (rc = S.crc.reserve(c, nc)) || (rc = S.tok.reserve(c, (size_t)round * GZ_TOK_STRIDE)) || (rc = S.freq.reserve(c, (size_t)round * GZ_FREQ_STRIDE)) ||
+      (rc = S.ntok.reserve(c, round))) return rc;
+  if (gz && (rc = S.slots.reserve(c, (size_t)slots_bytes))) return rc;
+  HIPCHK(c, hipMemcpyAsync(S.chunks, chunks.data(), (size_t)nc * sizeof(GzChunk), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(S.slot_off, slot_off.data(), (size_t)nc * 8u, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(S.sizes + nc, 0, 8, c->stream));
+  float f = 0;
+  for (uint32_t b = 0; b < nc; b += round) {
+    const uint32_t m = std::min(round, nc - b);
+    HIPCHK(c, hipEventRecord(S.ev[0], c->stream));
+    launch(c, k_gz_match, dim3(m), dim3(GZ_WIN), 0, d_in, (const GzChunk*)(S.chunks + b), (const uint32_t*)S.crc_tab, S.tok, S.freq, S.ntok, S.crc + b);
+    HIPCHK(c, hipEventRecord(S.ev[1], c->stream));
+    launch(c, k_gz_codes, dim3(m), dim3(64), 0, (const GzChunk*)(S.chunks + b), (const uint32_t*)S.freq, S.codes + b, S.sizes + b);
+    HIPCHK(c, hipEventRecord(S.ev[2], c->stream));
+    // (sizes only: the sizes are known once the codes are; the members themselves are not made)
+    if (gz) launch(c, k_gz_encode, dim3(m), dim3(256), 0, d_in, (const GzChunk*)(S.chunks + b), (const uint32_t*)S.tok, (const uint32_t*)S.ntok, (const uint32_t*)(S.crc + b),
+                   (const GzCode*)(S.codes + b), (const unsigned long long*)(S.slot_off + b), S.slots);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(S.ev[3], c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));        // the next round takes the token arrays (and the events)
+    if (hipEventElapsedTime(&f, S.ev[0], S.ev[1]) == hipSuccess) S.ms[0] += f;
+    if (hipEventElapsedTime(&f, S.ev[1], S.ev[2]) == hipSuccess) S.ms[1] += f;
+    if (hipEventElapsedTime(&f, S.ev[2], S.ev[3]) == hipSuccess) S.ms[2] += f;
+  }
+  HIPCHK(c, hipEventRecord(S.ev[0], c->stream));
+  launch(c, k_export_scan, dim3(1), dim3(EXP_SIZE_BLOCK), 0, S.sizes, nc + 1u);
+  HIPCHK(c, hipGetLastError());
+  std::vector<unsigned long long> excl((size_t)nc + 1u);
+  HIPCHK(c, hipMemcpyAsync(excl.data(), S.sizes, ((size_t)nc + 1u) * 8u, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (uint32_t k = 0; k <= n_streams; k++) gz_off[k] = excl[first[k]];
+  const uint64_t total = excl[nc];
+  if (need) *need = total;
+  if (!gz) return SMR_OK;
+  if (cap < total) { set_err(c, std::string(who) + ": the members take " + std::to_string(total) + " bytes, the buffer has " + std::to_string(cap)); return SMR_ERR_CAPACITY; }
+  if ((rc = S.out.reserve(c, (size_t)((total + 4095u) & ~4095ull)))) return rc;
+  launch(c, k_gz_compact, dim3(nc), dim3(256), 0, (const GzCode*)S.codes, (const unsigned long long*)S.slot_off, (const uint8_t*)S.slots, (const unsigned long long*)S.sizes, S.out);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(S.ev[1], c->stream));
+  HIPCHK(c, hipMemcpyAsync(gz, S.out, (size_t)total, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipEventRecord(S.ev[2], c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (hipEventElapsedTime(&f, S.ev[0], S.ev[1]) == hipSuccess) S.ms[3] = f;
+  if (hipEventElapsedTime(&f, S.ev[1], S.ev[2]) == hipSuccess) S.ms[4] = f;
+  return SMR_OK;
+}
+}  // namespace
+
+extern "C" uint32_t smr_gzip_chunk(void) { return GZ_CHUNK; }
+extern "C" uint64_t smr_gzip_bound(uint64_t plain_bytes, uint64_t n_chunks) {
+  // per member 18 + its plain bytes + 5 per stored block of at most 65 535 bytes: one block per member, and a further one in every member that
+  // is a whole chunk -- of which plain_bytes allow plain_bytes / GZ_CHUNK.  For the chunks of one stream this is the sum over its members.
+  const uint64_t per_full = (GZ_CHUNK + 65534u) / 65535u;
+  return 18u * n_chunks + plain_bytes + 5u * (n_chunks + (per_full - 1u) * std::min<uint64_t>(n_chunks, plain_bytes / GZ_CHUNK));
+}
+extern "C" int smr_gzip_batch(smr_ctx* c, const uint8_t* plain, const uint64_t* off, uint32_t n_streams, uint8_t* gz, uint64_t cap, uint64_t* gz_off, uint64_t* need) {
+  if (!c || !off || !gz_off || !need) return SMR_ERR_ARG;
+  for (uint32_t k = 0; k <= n_streams; k++) gz_off[k] = 0;
+  *need = 0;
+  for (uint32_t k = 0; k < n_streams; k++) if (off[k + 1] < off[k]) { set_err(c, "smr_gzip_batch: the offsets decrease"); return SMR_ERR_ARG; }
+  const uint64_t n = off[n_streams] - off[0];
+  if (n == 0) return SMR_OK;
+  if (!plain) return SMR_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = c->gz.in.reserve(c, (size_t)n))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->gz.in, plain + off[0], (size_t)n, hipMemcpyHostToDevice, c->stream));
+  std::vector<uint64_t> rel(n_streams + 1u);
+  for (uint32_t k = 0; k <= n_streams; k++) rel[k] = off[k] - off[0];
+  return gz_run(c, "smr_gzip_batch", c->gz.in, rel.data(), n_streams, gz, cap, gz_off, need);
+}
+extern "C" int smr_gzip_times(const smr_ctx* c, double ms[5]) {
+  if (!c || !ms) return SMR_ERR_ARG;
+  for (int k = 0; k < 5; k++) ms[k] = c->gz.ms[k];
+  return SMR_OK;
+}

@@ -26,6 +26,8 @@
 #include <string>
 #include <vector>
 
+#include <fcntl.h>
+#include <unistd.h>
 #include <zlib.h>
 
 #include "smr_host.hpp"
@@ -33,16 +35,37 @@
 
 namespace {
 // one report file, plain or gzip (the reference deflates its reports when the reads file is gzip, or with -zip-out; the names get ".gz")
+// The gzip file is opened by descriptor (gzdopen: the same bytes as gzopen, which stores no name either), so that put_raw can append gzip
+// members made elsewhere: what zlib holds is finished as a member first (gzflush(Z_FINISH); a later gzwrite begins a new one), then the bytes
+// follow on the descriptor.
 struct Out {
   FILE* f = nullptr; gzFile g = nullptr;
+  int fd = -1; bool pending = false;                   // pending: deflated bytes since the last finished member
   bool open(const std::string& path, bool zip) {
-    if (zip) { g = gzopen((path + ".gz").c_str(), "wb"); return g != nullptr; }
+    if (zip) {
+      fd = ::open((path + ".gz").c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+      if (fd < 0) return false;
+      g = gzdopen(fd, "wb");
+      if (!g) { ::close(fd); fd = -1; }
+      return g != nullptr;
+    }
     f = fopen(path.c_str(), "wb"); return f != nullptr;
   }
   bool is_open() const { return f || g; }
-  void put(const void* p, size_t n) { if (!n) return; if (g) gzwrite(g, p, (unsigned)n); else if (f) fwrite(p, 1, n, f); }
+  void put(const void* p, size_t n) { if (!n) return; if (g) { gzwrite(g, p, (unsigned)n); pending = true; } else if (f) fwrite(p, 1, n, f); }
   void put(const std::string& t) { put(t.data(), t.size()); }
-  void close() { if (g) gzclose(g); if (f) fclose(f); g = nullptr; f = nullptr; }
+  bool put_raw(const uint8_t* p, uint64_t n) {
+    if (!n) return true;
+    if (!g) return false;
+    if (pending) { if (gzflush(g, Z_FINISH) != Z_OK) return false; pending = false; }
+    while (n) {
+      const ssize_t k = ::write(fd, p, (size_t)std::min<uint64_t>(n, 1u << 30));
+      if (k <= 0) return false;
+      p += k; n -= (uint64_t)k;
+    }
+    return true;
+  }
+  void close() { if (g) gzclose(g); if (f) fclose(f); g = nullptr; f = nullptr; fd = -1; }
 };
 struct Aln {
   std::vector<uint32_t> cigar;
@@ -343,6 +366,26 @@ extern "C" int smr_report_add_denovo(smr_report* r, const uint8_t* bytes, const 
     }
   }
   return SMR_OK;
+}
+namespace {
+int add_gz(smr_report* r, const char* who, const uint8_t* gz, const uint64_t* off, int n, const std::function<Out&(int)>& file) {
+  if (!r || !off) return SMR_ERR_ARG;
+  const std::string W(who);
+  if (!r->o.zip_out) { r->err = W + ": the report was not opened with zip_out"; return SMR_ERR_ARG; }
+  for (int k = 0; k < n; k++) {
+    if (off[k + 1] < off[k]) { r->err = W + ": the offsets decrease"; return SMR_ERR_ARG; }
+    if (off[k + 1] > off[k] && (!gz || !file(k).g)) { r->err = W + ": stream " + std::to_string(k) + " is not empty and has no open file"; return SMR_ERR_ARG; }
+  }
+  for (int k = 0; k < n; k++)
+    if (!file(k).put_raw(gz + off[k], off[k + 1] - off[k])) { r->err = W + ": cannot write stream " + std::to_string(k); return SMR_ERR_IO; }
+  return SMR_OK;
+}
+}  // namespace
+extern "C" int smr_report_add_fastx_gz(smr_report* r, const uint8_t* gz, const uint64_t gz_off[9]) {
+  return add_gz(r, "smr_report_add_fastx_gz", gz, gz_off, 8, [r](int k) -> Out& { return k < 4 ? r->f_aligned[k] : r->f_other[k - 4]; });
+}
+extern "C" int smr_report_add_denovo_gz(smr_report* r, const uint8_t* gz, const uint64_t gz_off[5]) {
+  return add_gz(r, "smr_report_add_denovo_gz", gz, gz_off, 4, [r](int k) -> Out& { return r->f_denovo[k]; });
 }
 extern "C" int smr_report_skip_denovo(smr_report* r, int on) {
   if (!r) return SMR_ERR_ARG;

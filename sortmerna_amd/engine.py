@@ -543,6 +543,64 @@ class Engine:
         raw = bytes(buf)
         return [raw[off[k]:off[k + 1]] for k in range(4)]
 
+    def gzip_chunk(self):
+        """smr_gzip_chunk: plain bytes per gzip member of the device compressor"""
+        return int(self.L.smr_gzip_chunk())
+
+    def gzip_bound(self, plain_bytes, n_chunks):
+        """smr_gzip_bound: no output of the device compressor for plain_bytes in n_chunks members is larger"""
+        return int(self.L.smr_gzip_bound(int(plain_bytes), int(n_chunks)))
+
+    def gzip_batch(self, streams):
+        """smr_gzip_batch: every bytes object of `streams` cut into chunks of gzip_chunk() bytes and each chunk made a gzip member by the
+        DEFLATE kernels -> a list of bytes objects, the members of each stream back to back (b"" for an empty one)"""
+        n = len(streams)
+        off = (C.c_uint64 * (n + 1))()
+        for k in range(n):
+            off[k + 1] = off[k] + len(streams[k])
+        plain = np.frombuffer(b"".join(streams) or b"\0", dtype=np.uint8)
+        gz_off = (C.c_uint64 * (n + 1))()
+        need = C.c_uint64(0)
+        cap = self.gzip_bound(off[n], sum((len(x) + self.gzip_chunk() - 1) // self.gzip_chunk() for x in streams))
+        buf = np.zeros(max(cap, 1), dtype=np.uint8)
+        self._chk(self.L.smr_gzip_batch(self.h, plain.ctypes.data, off, n, buf.ctypes.data, cap, gz_off, C.byref(need)), "smr_gzip_batch")
+        raw = buf[:need.value].tobytes()
+        return [raw[gz_off[k]:gz_off[k + 1]] for k in range(n)]
+
+    def gzip_times(self):
+        """HIP-event ms of the last gzip_batch / fastx_split_gz / fastx_denovo_gz: dict(match, codes, encode, compact, d2h)"""
+        ms = (C.c_double * 5)()
+        self._chk(self.L.smr_gzip_times(self.h, ms), "smr_gzip_times")
+        return dict(zip(("match", "codes", "encode", "compact", "d2h"), (float(x) for x in ms)))
+
+    def _fx_gz(self, fn, n, o, flags, mates):
+        fb = None if flags is None else (C.c_uint8 * max(len(flags), 1))(*[1 if x else 0 for x in flags])
+        m = -1 if mates is None else int(mates)
+        gz_off, plain_off = (C.c_uint64 * (n + 1))(), (C.c_uint64 * (n + 1))()
+        need = C.c_uint64(0)
+        call = getattr(self.L, fn)
+        self._chk(call(self.h, m, C.byref(o), fb, None, 0, gz_off, plain_off, C.byref(need)), fn)
+        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
+        if need.value:
+            self._chk(call(self.h, m, C.byref(o), fb, buf.ctypes.data, need.value, gz_off, plain_off, C.byref(need)), fn)
+        raw = buf.tobytes()
+        return [raw[gz_off[k]:gz_off[k + 1]] for k in range(n)], [int(x) for x in plain_off]
+
+    def fastx_split_gz(self, layout=0, mates=None, paired_in=False, paired_out=False, out2=False, sout=False, aligned=True, other=True, hit=None):
+        """smr_fastx_split_gz: the eight streams of fastx_split, compressed on the device -> (a list of eight bytes objects, each the gzip
+        members of its stream or b"", and the nine offsets fastx_split's streams would have)"""
+        o = capi.FxSplitOpts(int(layout), int(bool(paired_in)), int(bool(paired_out)), int(bool(out2)), int(bool(sout)), int(bool(aligned)), int(bool(other)))
+        return self._fx_gz("smr_fastx_split_gz", 8, o, hit, mates)
+
+    def fastx_denovo_gz(self, opts=None, mates=-1, dn=None, **kw):
+        """smr_fastx_denovo_gz: the four streams of fastx_denovo, compressed on the device -> (four bytes objects, the five plain offsets)"""
+        if isinstance(opts, capi.FxSplitOpts):
+            o = opts
+        else:
+            d = dict(opts or {}, **kw)
+            o = capi.FxSplitOpts(int(d.get("layout", 0)), int(bool(d.get("paired_in"))), int(bool(d.get("paired_out"))), int(bool(d.get("out2"))), int(bool(d.get("sout"))), 1, 0)
+        return self._fx_gz("smr_fastx_denovo_gz", 4, o, dn, mates)
+
     def rows_fmt_batch(self, num, den):
         """smr_rows_fmt_batch (a test seam): the device's `%.3g` of 100 * num[i] / den[i] -> list of str"""
         num = np.ascontiguousarray(num, dtype=np.uint32)

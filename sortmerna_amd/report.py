@@ -114,6 +114,22 @@ class Report:
         blob = b"".join(streams)
         self._chk(self.L.smr_report_add_denovo(self.h, blob if blob else None, off), "smr_report_add_denovo")
 
+    def _add_gz(self, fn, streams, n):
+        off = (C.c_uint64 * (n + 1))()
+        for k in range(n):
+            off[k + 1] = off[k] + len(streams[k])
+        blob = b"".join(streams)
+        self._chk(getattr(self.L, fn)(self.h, blob if blob else None, off), fn)
+
+    def add_fastx_gz(self, streams):
+        """the eight streams of Engine.fastx_split_gz -- gzip members -- appended as they are to the open aligned.* / other.* .gz files
+        (smr_report_add_fastx_gz); the report must have been opened with zip_out"""
+        self._add_gz("smr_report_add_fastx_gz", streams, 8)
+
+    def add_denovo_gz(self, streams):
+        """the four streams of Engine.fastx_denovo_gz appended as they are to the open aligned_denovo.* .gz files (smr_report_add_denovo_gz)"""
+        self._add_gz("smr_report_add_denovo_gz", streams, 4)
+
     def skip_denovo(self, on=True):
         """add / add_pair leave aligned_denovo.* alone: add_denovo writes them (smr_report_skip_denovo)"""
         self._chk(self.L.smr_report_skip_denovo(self.h, int(bool(on))), "smr_report_skip_denovo")
