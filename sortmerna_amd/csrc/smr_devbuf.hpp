@@ -43,6 +43,11 @@ template <class T> class DevBuf {
   }
   // grow-only: a new array when this one holds fewer than `need` elements
   int reserve(smr_ctx* c, size_t need) { return (p_ && cap_ >= need) ? 0 : alloc(c, need); }
+  // a staging buffer for `total` elements of which a kernel may touch `slack` more: when it is too small, a new one with an eighth to spare,
+  // rounded up to 4 Ki elements (the next, slightly larger call fits as well)
+  int reserve_headroom(smr_ctx* c, size_t total, size_t slack) {
+    return cap_ >= total + slack ? 0 : alloc(c, (size_t)((total + (total >> 3) + 4095u) & ~4095ull));
+  }
 };
 
 struct DevStream {

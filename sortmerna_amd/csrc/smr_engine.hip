@@ -25,6 +25,7 @@
 #include "smr_pgbuild.hpp"
 #include "smr_hostmem.hpp"
 #include "smr_devbuf.hpp"
+#include "smr_stage.hpp"
 #include "smr_score_text.hpp"
 #include "smr_tuning.hpp"
 
@@ -113,68 +114,34 @@ struct FxScratch {
   DevBuf<uint8_t> text;
   DevBuf<uint32_t> tot, part_t, part_l, line_start, lrec, lcum, hdr_line, rcum, rlen, rwi;      // part_l: three arrays of one entry per block of lines
   DevBuf<unsigned long long> hoff, soff;
-  hipEvent_t ev[6] = {};
-  FxScratch() = default;
-  FxScratch(const FxScratch&) = delete;
-  FxScratch& operator=(const FxScratch&) = delete;
-  ~FxScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+  StageClock<6, 0> clk;                   // (events only: the times of the last call go to smr_ctx::fx_ms under err_m)
 };
 
 // scratch and staging of smr_fastx_split (smr_fxsplit.hpp), grow-only
 struct FxSplitScratch {
   DevBuf<uint4> rec; DevBuf<unsigned long long> woff, part, tot; DevBuf<uint8_t> hit, out;
-  hipEvent_t ev[6] = {};
-  double ms[4] = {0, 0, 0, 0};            // of the last call: measure, scans, copy, D2H
-  FxSplitScratch() = default;
-  FxSplitScratch(const FxSplitScratch&) = delete;
-  FxSplitScratch& operator=(const FxSplitScratch&) = delete;
-  ~FxSplitScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+  StageClock<6, 4> clk;                   // of the last smr_fastx_split*: measure, scans, copy, D2H
 };
 
 // scratch and staging of smr_rows_part (smr_rows.hpp), grow-only; the e-value / bit-score table with the database it was made for
 struct RowsScratch {
   DevBuf<uint4> stat, meta; DevBuf<unsigned long long> excl_s, excl_b, part_s, part_b; DevBuf<uint32_t> err; DevBuf<uint8_t> tab, out;
   uint32_t tab_n = 0; double tab_lambda = 0, tab_K = 0; uint64_t tab_ref = 0, tab_read = 0;
-  hipEvent_t ev[7] = {};
-  double ms[4] = {0, 0, 0, 0};            // of the last call: stats, sizes and scans, write, D2H
-  RowsScratch() = default;
-  RowsScratch(const RowsScratch&) = delete;
-  RowsScratch& operator=(const RowsScratch&) = delete;
-  ~RowsScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
-};
-
-// the events and times of smr_pairwise_part (smr_pairwise.hpp); its device buffers are those of RowsScratch
-struct PairScratch {
-  hipEvent_t ev[7] = {};
-  double ms[4] = {0, 0, 0, 0};            // of the last call: guards / statistics, sizes and scans, write, D2H
-  PairScratch() = default;
-  PairScratch(const PairScratch&) = delete;
-  PairScratch& operator=(const PairScratch&) = delete;
-  ~PairScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+  StageClock<7, 4> clk;                   // of the last call: stats, sizes and scans, write, D2H
 };
 
 // scratch and staging of smr_otu_part (smr_otu.hpp), grow-only
 struct OtuScratch {
   DevBuf<uint8_t> pass, out; DevBuf<uint2> meta; DevBuf<uint4> pairs; DevBuf<uint32_t> key[2], val[2], gstart, err;
   DevBuf<unsigned long long> excl, part, hist, wexcl, wpart, gexcl, gpart; DevBuf<OtuGroup> groups;
-  hipEvent_t ev[10] = {};
-  double ms[5] = {0, 0, 0, 0, 0};         // of the last call: classify, size + scans, sort, write, D2H
-  OtuScratch() = default;
-  OtuScratch(const OtuScratch&) = delete;
-  OtuScratch& operator=(const OtuScratch&) = delete;
-  ~OtuScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+  StageClock<10, 5> clk;                  // of the last call: classify, size + scans, sort, write, D2H
 };
 
 // scratch and staging of the DEFLATE kernels (smr_gzip.hpp), grow-only
 struct GzScratch {
   DevBuf<uint8_t> in, slots, out; DevBuf<GzChunk> chunks; DevBuf<GzCode> codes; DevBuf<unsigned long long> slot_off, sizes;
   DevBuf<uint32_t> crc_tab, crc, tok, freq, ntok;
-  hipEvent_t ev[4] = {};
-  double ms[5] = {0, 0, 0, 0, 0};         // of the last call: match, code build, encode, scan + compact, D2H
-  GzScratch() = default;
-  GzScratch(const GzScratch&) = delete;
-  GzScratch& operator=(const GzScratch&) = delete;
-  ~GzScratch() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+  StageClock<4, 5> clk;                   // of the last call: match, code build, encode, scan + compact, D2H
 };
 
 struct smr_ctx {
@@ -253,7 +220,7 @@ struct smr_ctx {
   uint64_t fx_info[4] = {0, 0, 0, 0}; double fx_ms[5] = {0, 0, 0, 0, 0};
   FxSplitScratch fxs;
   RowsScratch rows;
-  PairScratch pair;
+  StageClock<7, 4> pair_clk;              // of the last smr_pairwise_part (its device buffers are those of `rows`): guards / statistics, sizes and scans, write, D2H
   OtuScratch otu;
   GzScratch gz;
 };
@@ -346,6 +313,15 @@ int check_params(smr_ctx* c, const smr_params* p, bool sw = true) {
   // unsigned compare, alignment.cpp:320,345 -- the whole rest of the reference becomes the window; larger values: more reads whose window length wraps)
   if (sw && (p->edges < 1 || p->edges > 10)) { set_err(c, "edges must be 1..10 (nucleotides or percent), like the reference's --edges"); return SMR_ERR_ARG; }
   if (p->num_alignments > 0 && p->num_alignments > c->b->slots) { set_err(c, "num_alignments exceeds max_alignments_per_read given to smr_reads_upload"); return SMR_ERR_ARG; }
+  return SMR_OK;
+}
+
+// stored alignments a call cannot work on, as the guards of smr_idcov_part, k_rows_stat and k_otu_classify count them: SMR_OK when all three are 0
+int part_refuse_state(smr_ctx* c, const char* who, uint32_t no_cigar, uint32_t bad_ref, uint32_t past) {
+  const std::string W = std::string(who) + ": ";
+  if (no_cigar) { set_err(c, W + std::to_string(no_cigar) + " alignments of this (index, part) have no CIGAR yet (call smr_traceback first)"); return SMR_ERR_STATE; }
+  if (bad_ref) { set_err(c, W + std::to_string(bad_ref) + " alignments with ref_num out of range"); return SMR_ERR_ARG; }
+  if (past) { set_err(c, W + std::to_string(past) + " alignments whose CIGAR runs past its read or its reference"); return SMR_ERR_ARG; }
   return SMR_OK;
 }
 

@@ -29,7 +29,7 @@ extern "C" int smr_state_export(smr_ctx* c, uint8_t* bytes, uint64_t cap, uint64
   if (!bytes) return SMR_OK;
   if (cap < total) { set_err(c, "smr_state_export: the records take " + std::to_string(total) + " bytes, the buffer has " + std::to_string(cap)); return SMR_ERR_CAPACITY; }
   if (total == 0) return SMR_OK;
-  if (c->d_xbytes.cap() < total && (rc = c->d_xbytes.alloc(c, (size_t)((total + (total >> 3) + 4095u) & ~4095ull)))) return rc;      // (the next, slightly larger batch fits as well)
+  if ((rc = c->d_xbytes.reserve_headroom(c, (size_t)total, 0))) return rc;
   const uint32_t chunks = (n + 63u) / 64u, blocks = std::min<uint32_t>((chunks + 3u) / 4u, (uint32_t)c->n_cu * 8u);
   launch(c, k_export_state, dim3(blocks), dim3(256), 0, n, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar,
                      (unsigned long long)(B.d_cigar ? B.cigar_words : 0), (const uint32_t*)B.d_idcov, B.last_num_alignments, (const unsigned long long*)c->d_xoff, c->d_xbytes);

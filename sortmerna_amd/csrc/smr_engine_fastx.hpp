@@ -54,18 +54,18 @@ int fastx_upload(smr_ctx* c, Batch& B, FxScratch& S, hipStream_t st, const char*
   if (first >= n || (text[first] != '@' && text[first] != '>')) return fx_host_path(c, B, st, name, text, n, owner, max_aln, flags, out, 0, 0);
   const uint32_t fastq = text[first] == '@';
   int rc;
-  for (auto& e : S.ev) if (!e) HIPCHK(c, hipEventCreate(&e));
+  if ((rc = S.clk.begin(c))) return rc;
   // ---- the text, padded for the aligned loads of the kernels
   const size_t cap = (((size_t)n + 15u) & ~(size_t)15u) + 64u;
   const uint32_t nt = (uint32_t)(((uint64_t)n + FX_TILE - 1u) / FX_TILE);
   if ((rc = S.text.reserve(c, cap)) || (rc = S.tot.reserve(c, FXT_COUNT)) || (rc = S.part_t.reserve(c, nt))) return rc;
   uint32_t h_tot[FXT_COUNT] = {};
   h_tot[FXT_FIRST_BLANK_HDR] = ~0u; h_tot[FXT_MIN_LEN] = ~0u;
-  HIPCHK(c, hipEventRecord(S.ev[0], st));
+  if ((rc = S.clk.mark(c, 0, st))) return rc;
   HIPCHK(c, hipMemcpyAsync(S.text, text, n, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemsetAsync(S.text + n, '\n', cap - n, st));
   HIPCHK(c, hipMemcpyAsync(S.tot, h_tot, sizeof h_tot, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipEventRecord(S.ev[1], st));
+  if ((rc = S.clk.mark(c, 1, st))) return rc;
   // ---- lines
   launch_on(st, k_fx_count, dim3(nt), dim3(FX_BLOCK), 0, (const uint8_t*)S.text, n, first, (uint32_t*)S.part_t);
   launch_on(st, k_fx_scan, dim3(1), dim3(FX_LBLOCK), 0, (uint32_t*)S.part_t, (uint32_t*)nullptr, nt, (uint32_t*)S.tot, (uint32_t)FXT_NEWLINES, 0u);
@@ -82,7 +82,7 @@ int fastx_upload(smr_ctx* c, Batch& B, FxScratch& S, hipStream_t st, const char*
       (rc = S.hoff.reserve(c, max_rec)) || (rc = S.soff.reserve(c, max_rec))) return rc;
   uint32_t* const part_h = S.part_l; uint32_t* const part_c = part_h + npart; uint32_t* const part_w = part_c + npart;
   launch_on(st, k_fx_lines, dim3(nt), dim3(FX_BLOCK), 0, (const uint8_t*)S.text, n, first, (const uint32_t*)S.part_t, (const uint32_t*)S.tot, (uint32_t*)S.line_start);
-  HIPCHK(c, hipEventRecord(S.ev[2], st));
+  if ((rc = S.clk.mark(c, 2, st))) return rc;
   // ---- records
   launch_on(st, k_fx_classify, dim3(nlb), dim3(FX_LBLOCK), 0, (const uint8_t*)S.text, fastq, nl, (const uint32_t*)S.line_start, (uint32_t*)S.lrec, (uint32_t*)S.lcum, part_h, part_c,
                      (uint32_t*)S.tot);
@@ -94,7 +94,7 @@ int fastx_upload(smr_ctx* c, Batch& B, FxScratch& S, hipStream_t st, const char*
                      (uint32_t*)S.rlen, (uint32_t*)S.rwi, part_w, (unsigned long long*)S.hoff, (unsigned long long*)S.soff);
   launch_on(st, k_fx_scan, dim3(1), dim3(FX_LBLOCK), 0, part_w, (uint32_t*)nullptr, nrb, (uint32_t*)S.tot, (uint32_t)FXT_WORDS, 0u);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(S.ev[3], st));
+  if ((rc = S.clk.mark(c, 3, st))) return rc;
   HIPCHK(c, hipMemcpyAsync(h_tot, S.tot, sizeof h_tot, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   if (h_tot[FXT_FLAG]) return fx_host_path(c, B, st, name, text, n, owner, max_aln, flags, out, nl, n);
@@ -106,7 +106,7 @@ int fastx_upload(smr_ctx* c, Batch& B, FxScratch& S, hipStream_t st, const char*
                      (const uint32_t*)S.rcum, (const uint32_t*)S.rlen, (const uint32_t*)S.rwi, (const uint32_t*)part_w, (uint32_t*)B.d_len, reinterpret_cast<unsigned long long*>(B.d_rec_off.get()),
                      (uint32_t*)B.d_words);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(S.ev[4], st));
+  if ((rc = S.clk.mark(c, 4, st))) return rc;
   if ((rc = batch_fresh_state(c, B, st))) return rc;
   // ---- what the caller asked to see of it
   smr_reads* r = nullptr;
@@ -131,11 +131,11 @@ int fastx_upload(smr_ctx* c, Batch& B, FxScratch& S, hipStream_t st, const char*
     }
     if (e != hipSuccess) { delete r; return dev_fail(c, "hipMemcpyAsync", e); }
   }
-  hipError_t e = hipEventRecord(S.ev[5], st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if ((rc = S.clk.mark(c, 5, st))) { delete r; return rc; }
+  const hipError_t e = hipStreamSynchronize(st);
   if (e != hipSuccess) { delete r; return dev_fail(c, "hipStreamSynchronize", e); }
   double ms[5] = {0, 0, 0, 0, 0};
-  for (int k = 0; k < 5; k++) { float f = 0; if (hipEventElapsedTime(&f, S.ev[k], S.ev[k + 1]) == hipSuccess) ms[k] = f; }
+  for (int k = 0; k < 5; k++) (void)S.clk.elapsed(k, k + 1, ms[k]);
   fx_report(c, 0, nl, R, n, ms);
   if (flags & SMR_FASTX_KEEP) {                                 // (handed over, not copied: the stream's scratch allocates again on its next use)
     B.fx_text = std::move(S.text); B.fx_hoff = std::move(S.hoff); B.fx_soff = std::move(S.soff);

@@ -1,6 +1,6 @@
 // smr_engine_gzip.hpp -- host side of the DEFLATE kernels (smr_gzip.hpp; included by smr_engine.hip): gz_run, the dispatcher that turns byte
 // ranges of a device buffer into gzip members and copies only those to the host, and smr_gzip_batch, the same over a host buffer (a building
-// block and the tests' seam).  smr_fastx_split_gz / smr_fastx_denovo_gz (smr_engine_fxsplit.hpp, smr_engine_otu.hpp) hand it the streams
+// block and the tests' seam).  smr_fastx_split_gz / smr_fastx_denovo_gz (smr_engine_fxsplit.hpp) hand it the streams
 // their plain siblings would have copied back.
 //
 // The tokens of a chunk take four bytes per plain byte, so the chunks are worked on in rounds of GZ_ROUND; the members wait in worst-case
@@ -30,7 +30,8 @@ void gz_crc_words(uint32_t* w) {
 // n_streams ranges [off[k], off[k + 1]) of d_in -> their gzip members, back to back, in gz (may be null: sizes only); gz_off[n_streams + 1]
 int gz_run(smr_ctx* c, const char* who, const uint8_t* d_in, const uint64_t* off, uint32_t n_streams, uint8_t* gz, uint64_t cap, uint64_t* gz_off, uint64_t* need) {
   GzScratch& S = c->gz;
-  for (double& m : S.ms) m = 0.0;
+  int rc;
+  if ((rc = S.clk.begin(c))) return rc;
   for (uint32_t k = 0; k <= n_streams; k++) gz_off[k] = 0;
   if (need) *need = 0;
   std::vector<GzChunk> chunks;
@@ -49,8 +50,6 @@ int gz_run(smr_ctx* c, const char* who, const uint8_t* d_in, const uint64_t* off
   if (chunks.empty()) return SMR_OK;
   if (chunks.size() >= 0x7FFFFFFFull) { set_err(c, std::string(who) + ": 2^31 - 1 chunks or more"); return SMR_ERR_CAPACITY; }
   const uint32_t nc = (uint32_t)chunks.size(), round = std::min(nc, GZ_ROUND);
-  for (auto& e : S.ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-  int rc;
   if (!S.crc_tab) {
     uint32_t w[GZ_CRC_WORDS];
     gz_crc_words(w);
@@ -65,25 +64,24 @@ int gz_run(smr_ctx* c, const char* who, const uint8_t* d_in, const uint64_t* off
   HIPCHK(c, hipMemcpyAsync(S.chunks, chunks.data(), (size_t)nc * sizeof(GzChunk), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(S.slot_off, slot_off.data(), (size_t)nc * 8u, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(S.sizes + nc, 0, 8, c->stream));
-  float f = 0;
   for (uint32_t b = 0; b < nc; b += round) {
     const uint32_t m = std::min(round, nc - b);
-    HIPCHK(c, hipEventRecord(S.ev[0], c->stream));
+    if ((rc = S.clk.mark(c, 0, c->stream))) return rc;
     launch(c, k_gz_match, dim3(m), dim3(GZ_WIN), 0, d_in, (const GzChunk*)(S.chunks + b), (const uint32_t*)S.crc_tab, S.tok, S.freq, S.ntok, S.crc + b);
-    HIPCHK(c, hipEventRecord(S.ev[1], c->stream));
+    if ((rc = S.clk.mark(c, 1, c->stream))) return rc;
     launch(c, k_gz_codes, dim3(m), dim3(64), 0, (const GzChunk*)(S.chunks + b), (const uint32_t*)S.freq, S.codes + b, S.sizes + b);
-    HIPCHK(c, hipEventRecord(S.ev[2], c->stream));
+    if ((rc = S.clk.mark(c, 2, c->stream))) return rc;
     // (sizes only: the sizes are known once the codes are; the members themselves are not made)
     if (gz) launch(c, k_gz_encode, dim3(m), dim3(256), 0, d_in, (const GzChunk*)(S.chunks + b), (const uint32_t*)S.tok, (const uint32_t*)S.ntok, (const uint32_t*)(S.crc + b),
                    (const GzCode*)(S.codes + b), (const unsigned long long*)(S.slot_off + b), S.slots);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(S.ev[3], c->stream));
+    if ((rc = S.clk.mark(c, 3, c->stream))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));        // the next round takes the token arrays (and the events)
-    if (hipEventElapsedTime(&f, S.ev[0], S.ev[1]) == hipSuccess) S.ms[0] += f;
-    if (hipEventElapsedTime(&f, S.ev[1], S.ev[2]) == hipSuccess) S.ms[1] += f;
-    if (hipEventElapsedTime(&f, S.ev[2], S.ev[3]) == hipSuccess) S.ms[2] += f;
+    S.clk.add(0, 0, 1);
+    S.clk.add(1, 1, 2);
+    S.clk.add(2, 2, 3);
   }
-  HIPCHK(c, hipEventRecord(S.ev[0], c->stream));
+  if ((rc = S.clk.mark(c, 0, c->stream))) return rc;
   launch(c, k_export_scan, dim3(1), dim3(EXP_SIZE_BLOCK), 0, S.sizes, nc + 1u);
   HIPCHK(c, hipGetLastError());
   std::vector<unsigned long long> excl((size_t)nc + 1u);
@@ -97,12 +95,12 @@ int gz_run(smr_ctx* c, const char* who, const uint8_t* d_in, const uint64_t* off
   if ((rc = S.out.reserve(c, (size_t)((total + 4095u) & ~4095ull)))) return rc;
   launch(c, k_gz_compact, dim3(nc), dim3(256), 0, (const GzCode*)S.codes, (const unsigned long long*)S.slot_off, (const uint8_t*)S.slots, (const unsigned long long*)S.sizes, S.out);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(S.ev[1], c->stream));
+  if ((rc = S.clk.mark(c, 1, c->stream))) return rc;
   HIPCHK(c, hipMemcpyAsync(gz, S.out, (size_t)total, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipEventRecord(S.ev[2], c->stream));
+  if ((rc = S.clk.mark(c, 2, c->stream))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (hipEventElapsedTime(&f, S.ev[0], S.ev[1]) == hipSuccess) S.ms[3] = f;
-  if (hipEventElapsedTime(&f, S.ev[1], S.ev[2]) == hipSuccess) S.ms[4] = f;
+  S.clk.set(3, 0, 1);
+  S.clk.set(4, 1, 2);
   return SMR_OK;
 }
 }  // namespace
@@ -132,6 +130,6 @@ extern "C" int smr_gzip_batch(smr_ctx* c, const uint8_t* plain, const uint64_t* 
 }
 extern "C" int smr_gzip_times(const smr_ctx* c, double ms[5]) {
   if (!c || !ms) return SMR_ERR_ARG;
-  for (int k = 0; k < 5; k++) ms[k] = c->gz.ms[k];
+  c->gz.clk.copy_to(ms);
   return SMR_OK;
 }

@@ -20,10 +20,7 @@ static int idcov_core(smr_ctx* c, const DevIndex& di, uint32_t index_num, uint32
   HIPCHK(c, hipGetLastError());
   std::vector<unsigned long long> h;
   if ((rc = read_ctr(c, h))) return rc;
-  if (h[C_IDCOV_NOCIG]) {
-    set_err(c, "smr_idcov_part: " + std::to_string(h[C_IDCOV_NOCIG]) + " alignments of this (index, part) have no CIGAR yet (call smr_traceback first)");
-    return SMR_ERR_STATE;
-  }
+  if ((rc = part_refuse_state(c, "smr_idcov_part", (uint32_t)h[C_IDCOV_NOCIG], 0, 0))) return rc;      // (a count of slots: below ntot)
   const uint32_t n_few = (uint32_t)h[C_IDCOV_FEW], n_many = (uint32_t)h[C_IDCOV_MANY];
   if (n_few + n_many == 0) return SMR_OK;
   B.fetched = false;

@@ -2,7 +2,8 @@
 // BLAST tabular report of one (index, part) over the selected batch, counted, sized and written on the device -- what smr_results_fetch +
 // smr_reads_record_text + smr_result_record + smr_report_add do on the host one read at a time.  The host's share: the names of the part's
 // references (uploaded once per slot), the e-value / bit-score texts per score (smr::score_texts, the report writer's own), three small
-// copies back (the error counts, the two totals) and the bytes.
+// copies back (the error counts, the two totals) and the bytes.  Also here, for smr_pairwise_part and smr_otu_part behind it: the preamble of a
+// call on one (index, part) (PartCall, part_call_open, part_call_views) and the guard loop of k_rows_stat (rows_guard).
 
 namespace {
 // blast_cols -> ROWS_COL_*; false for an unknown word
@@ -23,7 +24,7 @@ bool rows_parse_cols(const char* text, RowsOpts& D) {
 }
 
 // the names of the references of part `part` as the rows print them: sq_header[first_seq + ref_num].first, "*" beyond the table
-int rows_names(smr_ctx* c, DevIndex& d, const smr_index* ix, uint32_t part, const char* who = "smr_rows_part") {
+int rows_names(smr_ctx* c, DevIndex& d, const smr_index* ix, uint32_t part, const char* who) {
   if (d.rows_names && d.rows_part == (int64_t)part) return SMR_OK;
   size_t first_seq = 0;
   for (uint32_t q = 0; q < part && q < ix->parts.size(); q++) first_seq += ix->parts[q].numseq_part;
@@ -47,7 +48,7 @@ int rows_names(smr_ctx* c, DevIndex& d, const smr_index* ix, uint32_t part, cons
 }
 
 // the texts of e-value and bit score for score1 = 0 .. n_tab - 1 under the database of `o`; kept until another database or a higher score asks
-int rows_table(smr_ctx* c, const smr_rows_opts* o, uint32_t n_tab, const char* who = "smr_rows_part") {
+int rows_table(smr_ctx* c, const smr_rows_opts* o, uint32_t n_tab, const char* who) {
   RowsScratch& S = c->rows;
   if (S.tab && S.tab_n >= n_tab && S.tab_lambda == o->lambda && S.tab_K == o->K && S.tab_ref == o->full_ref_corr && S.tab_read == o->full_read_corr) return SMR_OK;
   std::vector<uint8_t> h((size_t)n_tab * ROWS_TAB_ENTRY, 0);
@@ -67,10 +68,69 @@ int rows_table(smr_ctx* c, const smr_rows_opts* o, uint32_t n_tab, const char* w
   S.tab_n = n_tab; S.tab_lambda = o->lambda; S.tab_K = o->K; S.tab_ref = o->full_ref_corr; S.tab_read = o->full_read_corr;
   return SMR_OK;
 }
+
+// ---- what smr_rows_part, smr_pairwise_part and smr_otu_part share: the checks of a call on (the part in `slot`, the selected batch) and what its
+// kernels are handed of the two
+struct PartCall {
+  DevIndex& di; Batch& B;
+  uint64_t ntot; uint32_t n; unsigned long long pool_words;      // reads x alignment slots, reads, words of the CIGAR pool
+  RowsSrc src; DReads rd; DIndex dx;
+};
+// the refusals, in the order in which they take precedence, of a call made as {c->idx[slot], *c->b}; the caller has checked its own arguments
+// (slot within 0..63 among them)
+int part_call_open(smr_ctx* c, const char* who, const smr_params* p, const smr_index* ix, const PartCall& pc) {
+  const std::string W = std::string(who) + ": ";
+  if (!pc.di.used || !pc.B.d_saved) { set_err(c, W + "index slot empty or no reads uploaded"); return SMR_ERR_STATE; }
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = check_params(c, p, false); if (rc) return rc;
+  if (pc.di.n_refs != ix->n_refs() || pc.di.ref_bytes != ix->ref_seq.size() || pc.di.lnwin != ix->lnwin) { set_err(c, W + "`ix` is not the index part that is resident in the slot"); return SMR_ERR_ARG; }
+  if (!pc.B.fx_kept) { set_err(c, W + "the batch does not hold its text (upload it with smr_reads_upload_fastx* and SMR_FASTX_KEEP)"); return SMR_ERR_STATE; }
+  return SMR_OK;
+}
+// behind the caller's early return (a batch with reads): the size limit, then the views
+int part_call_views(smr_ctx* c, const char* who, PartCall& pc) {
+  const Batch& B = pc.B;
+  pc.n = B.n; pc.ntot = (uint64_t)B.n * B.slots;
+  if (pc.ntot >= 0xFFFFFC00ull) { set_err(c, std::string(who) + ": reads x alignment slots of the batch must stay below 2^32"); return SMR_ERR_CAPACITY; }
+  pc.pool_words = B.d_cigar ? B.cigar_words : 0ull;
+  pc.src.text = B.fx_text; pc.src.n_text = B.fx_n; pc.src.fastq = B.fx_fastq; pc.src.hoff = B.fx_hoff; pc.src.soff = B.fx_soff;
+  pc.rd = dreads(c); pc.dx = dindex(pc.di);
+  return SMR_OK;
+}
+// k_rows_stat over the batch (events 0 and 1 of `clk`, time 0): the statistics of every alignment, and the refusal of state the writers would
+// read out of bounds for.  A score above the table of D.n_tab entries makes the table for every 16-bit score under `db`, once
+int rows_guard(smr_ctx* c, const char* who, StageClock<7, 4>& clk, const PartCall& pc, RowsOpts& D, RowsRef& ref, const smr_rows_opts* db) {
+  RowsScratch& S = c->rows;
+  const Batch& B = pc.B;
+  const std::string W = std::string(who) + ": ";
+  uint32_t h_err[ROWS_E_COUNT];
+  int rc;
+  for (int attempt = 0;; attempt++) {
+    HIPCHK(c, hipMemsetAsync(S.err, 0, sizeof h_err, c->stream));
+    if ((rc = clk.mark(c, 0, c->stream))) return rc;
+    launch(c, k_rows_stat, dim3((uint32_t)std::min<uint64_t>((pc.ntot + 15u) / 16u, (uint64_t)c->n_cu * 32u)), dim3(256), 0, pc.rd, pc.dx, B.slots, (const RState*)B.d_saved,
+           (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar, pc.pool_words, D, S.stat, S.err);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = clk.mark(c, 1, c->stream))) return rc;
+    HIPCHK(c, hipMemcpyAsync(h_err, S.err, sizeof h_err, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = part_refuse_state(c, who, h_err[ROWS_E_NOCIG], h_err[ROWS_E_BADREF], h_err[ROWS_E_PAST]))) return rc;
+    if (h_err[ROWS_E_NOCOLS]) { set_err(c, W + std::to_string(h_err[ROWS_E_NOCOLS]) + " alignments with a CIGAR without columns"); return SMR_ERR_ARG; }
+    if (!h_err[ROWS_E_SCORE]) break;
+    // a score above match x the longest read (imported state can hold one): the table for every 16-bit score, once
+    if (attempt || D.n_tab >= 65536u) { set_err(c, W + "a score beyond the e-value table"); return SMR_ERR_ARG; }
+    D.n_tab = 65536u;
+    if ((rc = rows_table(c, db, D.n_tab, who))) return rc;
+    ref.tab = S.tab;
+  }
+  clk.set(0, 0, 1);
+  return SMR_OK;
+}
 }  // namespace
 
 extern "C" int smr_rows_part(smr_ctx* c, int slot, const smr_params* p, const smr_index* ix, const smr_rows_opts* o,
                              uint8_t* bytes, uint64_t cap, uint64_t off[3], uint64_t* need) {
+  static const char* const who = "smr_rows_part";
   if (!c || !off) return SMR_ERR_ARG;
   off[0] = off[1] = off[2] = 0;
   if (need) *need = 0;
@@ -79,96 +139,63 @@ extern "C" int smr_rows_part(smr_ctx* c, int slot, const smr_params* p, const sm
   RowsOpts D;
   memset(&D, 0, sizeof D);
   if (!rows_parse_cols(o->blast_cols, D)) { set_err(c, "smr_rows_part: blast_cols takes \"cigar\", \"qcov\" and \"qstrand\", space separated"); return SMR_ERR_ARG; }
-  if (!c->idx[slot].used || !c->b->d_saved) { set_err(c, "smr_rows_part: index slot empty or no reads uploaded"); return SMR_ERR_STATE; }
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc = check_params(c, p, false); if (rc) return rc;
-  DevIndex& di = c->idx[slot];
-  if (di.n_refs != ix->n_refs() || di.ref_bytes != ix->ref_seq.size() || di.lnwin != ix->lnwin) { set_err(c, "smr_rows_part: `ix` is not the index part that is resident in the slot"); return SMR_ERR_ARG; }
-  Batch& B = *c->b;
-  if (!B.fx_kept) { set_err(c, "smr_rows_part: the batch does not hold its text (upload it with smr_reads_upload_fastx* and SMR_FASTX_KEEP)"); return SMR_ERR_STATE; }
+  PartCall pc = {c->idx[slot], *c->b};
+  int rc = part_call_open(c, who, p, ix, pc); if (rc) return rc;
+  const Batch& B = pc.B;
   if (B.n == 0) return SMR_OK;
-  const uint64_t ntot = (uint64_t)B.n * B.slots;
-  if (ntot >= 0xFFFFFC00ull) { set_err(c, "smr_rows_part: reads x alignment slots of the batch must stay below 2^32"); return SMR_ERR_CAPACITY; }
+  if ((rc = part_call_views(c, who, pc))) return rc;
   D.want_sam = o->want_sam != 0; D.want_blast = o->want_blast != 0; D.index_num = p->index_num; D.part = p->part;
   RowsScratch& S = c->rows;
-  for (auto& e : S.ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-  for (double& m : S.ms) m = 0.0;
-  const uint32_t n = B.n, np = (n + ROWS_BLOCK - 1u) / ROWS_BLOCK;
-  if ((rc = rows_names(c, di, ix, p->part))) return rc;
+  StageClock<7, 4>& T = S.clk;
+  if ((rc = T.begin(c))) return rc;
+  const uint32_t n = pc.n, np = (n + ROWS_BLOCK - 1u) / ROWS_BLOCK;
+  if ((rc = rows_names(c, pc.di, ix, p->part, who))) return rc;
   if (D.want_blast) {
     D.n_tab = (uint32_t)std::min<uint64_t>(65536u, (uint64_t)p->match * B.max_len + 1u);
-    if ((rc = rows_table(c, o, D.n_tab))) return rc;
+    if ((rc = rows_table(c, o, D.n_tab, who))) return rc;
   }
-  if ((rc = S.stat.reserve(c, ntot)) || (rc = S.meta.reserve(c, n)) || (rc = S.excl_s.reserve(c, n)) || (rc = S.excl_b.reserve(c, n)) ||
+  if ((rc = S.stat.reserve(c, pc.ntot)) || (rc = S.meta.reserve(c, n)) || (rc = S.excl_s.reserve(c, n)) || (rc = S.excl_b.reserve(c, n)) ||
       (rc = S.part_s.reserve(c, (size_t)np + 1)) || (rc = S.part_b.reserve(c, (size_t)np + 1)) || (rc = S.err.reserve(c, ROWS_E_COUNT))) return rc;
-  const unsigned long long pool_words = B.d_cigar ? B.cigar_words : 0ull;
-  RowsSrc src; src.text = B.fx_text; src.n_text = B.fx_n; src.fastq = B.fx_fastq; src.hoff = B.fx_hoff; src.soff = B.fx_soff;
-  RowsRef ref; ref.names = di.rows_names; ref.name_off = di.rows_name_off; ref.tab = S.tab;
-  const DReads rd = dreads(c);
-  uint32_t h_err[ROWS_E_COUNT];
-  for (int attempt = 0;; attempt++) {
-    HIPCHK(c, hipMemsetAsync(S.err, 0, sizeof h_err, c->stream));
-    HIPCHK(c, hipEventRecord(S.ev[0], c->stream));
-    launch(c, k_rows_stat, dim3((uint32_t)std::min<uint64_t>((ntot + 15u) / 16u, (uint64_t)c->n_cu * 32u)), dim3(256), 0, rd, dindex(di), B.slots, (const RState*)B.d_saved,
-           (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar, pool_words, D, S.stat, S.err);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(S.ev[1], c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_err, S.err, sizeof h_err, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (h_err[ROWS_E_NOCIG]) {
-      set_err(c, "smr_rows_part: " + std::to_string(h_err[ROWS_E_NOCIG]) + " alignments of this (index, part) have no CIGAR yet (call smr_traceback first)");
-      return SMR_ERR_STATE;
-    }
-    if (h_err[ROWS_E_BADREF]) { set_err(c, "smr_rows_part: " + std::to_string(h_err[ROWS_E_BADREF]) + " alignments with ref_num out of range"); return SMR_ERR_ARG; }
-    if (h_err[ROWS_E_PAST]) { set_err(c, "smr_rows_part: " + std::to_string(h_err[ROWS_E_PAST]) + " alignments whose CIGAR runs past its read or its reference"); return SMR_ERR_ARG; }
-    if (h_err[ROWS_E_NOCOLS]) { set_err(c, "smr_rows_part: " + std::to_string(h_err[ROWS_E_NOCOLS]) + " alignments with a CIGAR without columns"); return SMR_ERR_ARG; }
-    if (!h_err[ROWS_E_SCORE]) break;
-    // a score above match x the longest read (imported state can hold one): the table for every 16-bit score, once
-    if (attempt || D.n_tab >= 65536u) { set_err(c, "smr_rows_part: a score beyond the e-value table"); return SMR_ERR_ARG; }
-    D.n_tab = 65536u;
-    if ((rc = rows_table(c, o, D.n_tab))) return rc;
-    ref.tab = S.tab;
-  }
-  float f = 0;
-  if (hipEventElapsedTime(&f, S.ev[0], S.ev[1]) == hipSuccess) S.ms[0] = f;
-  HIPCHK(c, hipEventRecord(S.ev[2], c->stream));
-  launch(c, k_rows_size, dim3(np), dim3(ROWS_BLOCK), 0, rd, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar, pool_words,
-         (const uint4*)S.stat, src, ref, D, S.meta, S.excl_s, S.excl_b, S.part_s, S.part_b);
+  RowsRef ref; ref.names = pc.di.rows_names; ref.name_off = pc.di.rows_name_off; ref.tab = S.tab;
+  if ((rc = rows_guard(c, who, T, pc, D, ref, o))) return rc;
+  if ((rc = T.mark(c, 2, c->stream))) return rc;
+  launch(c, k_rows_size, dim3(np), dim3(ROWS_BLOCK), 0, pc.rd, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar, pc.pool_words,
+         (const uint4*)S.stat, pc.src, ref, D, S.meta, S.excl_s, S.excl_b, S.part_s, S.part_b);
   launch(c, k_export_scan, dim3(1), dim3(EXP_SIZE_BLOCK), 0, S.part_s, np + 1u);
   launch(c, k_export_scan, dim3(1), dim3(EXP_SIZE_BLOCK), 0, S.part_b, np + 1u);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(S.ev[3], c->stream));
+  if ((rc = T.mark(c, 3, c->stream))) return rc;
   unsigned long long tot[2] = {0, 0};
   HIPCHK(c, hipMemcpyAsync(&tot[0], S.part_s + np, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(&tot[1], S.part_b + np, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (hipEventElapsedTime(&f, S.ev[2], S.ev[3]) == hipSuccess) S.ms[1] = f;
+  T.set(1, 2, 3);
   const uint64_t total = tot[0] + tot[1];
   off[1] = tot[0]; off[2] = total;
   if (need) *need = total;
   if (!bytes) return SMR_OK;
   if (cap < total) { set_err(c, "smr_rows_part: the rows take " + std::to_string(total) + " bytes, the buffer has " + std::to_string(cap)); return SMR_ERR_CAPACITY; }
   if (total == 0) return SMR_OK;
-  if (S.out.cap() < total + 8u && (rc = S.out.alloc(c, (size_t)((total + (total >> 3) + 4095u) & ~4095ull)))) return rc;      // (the next, slightly larger call fits as well)
+  if ((rc = S.out.reserve_headroom(c, (size_t)total, 8))) return rc;
   const uint32_t chunks = (n + 63u) / 64u, blocks = std::max(1u, std::min<uint32_t>((chunks + 3u) / 4u, (uint32_t)c->n_cu * 8u));
-  HIPCHK(c, hipEventRecord(S.ev[4], c->stream));
-  if (tot[0]) launch(c, k_rows_write<0u>, dim3(blocks), dim3(256), 0, rd, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar, pool_words,
-                     (const uint4*)S.stat, src, ref, D, (const uint4*)S.meta, (const unsigned long long*)S.excl_s, (const unsigned long long*)S.part_s, 0ull, S.out);
-  if (tot[1]) launch(c, k_rows_write<1u>, dim3(blocks), dim3(256), 0, rd, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar, pool_words,
-                     (const uint4*)S.stat, src, ref, D, (const uint4*)S.meta, (const unsigned long long*)S.excl_b, (const unsigned long long*)S.part_b, tot[0], S.out);
+  if ((rc = T.mark(c, 4, c->stream))) return rc;
+  if (tot[0]) launch(c, k_rows_write<0u>, dim3(blocks), dim3(256), 0, pc.rd, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar, pc.pool_words,
+                     (const uint4*)S.stat, pc.src, ref, D, (const uint4*)S.meta, (const unsigned long long*)S.excl_s, (const unsigned long long*)S.part_s, 0ull, S.out);
+  if (tot[1]) launch(c, k_rows_write<1u>, dim3(blocks), dim3(256), 0, pc.rd, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar, pc.pool_words,
+                     (const uint4*)S.stat, pc.src, ref, D, (const uint4*)S.meta, (const unsigned long long*)S.excl_b, (const unsigned long long*)S.part_b, tot[0], S.out);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(S.ev[5], c->stream));
+  if ((rc = T.mark(c, 5, c->stream))) return rc;
   HIPCHK(c, hipMemcpyAsync(bytes, S.out, (size_t)total, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipEventRecord(S.ev[6], c->stream));
+  if ((rc = T.mark(c, 6, c->stream))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (hipEventElapsedTime(&f, S.ev[4], S.ev[5]) == hipSuccess) S.ms[2] = f;
-  if (hipEventElapsedTime(&f, S.ev[5], S.ev[6]) == hipSuccess) S.ms[3] = f;
+  T.set(2, 4, 5);
+  T.set(3, 5, 6);
   return SMR_OK;
 }
 
 extern "C" int smr_rows_times(const smr_ctx* c, double ms[4]) {
   if (!c || !ms) return SMR_ERR_ARG;
-  for (int k = 0; k < 4; k++) ms[k] = c->rows.ms[k];
+  c->rows.clk.copy_to(ms);
   return SMR_OK;
 }
 

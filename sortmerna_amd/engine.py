@@ -425,11 +425,15 @@ class Engine:
         self._chk(self.L.smr_fastx_info(self.h, info), "smr_fastx_info")
         return tuple(int(x) for x in info)
 
+    def _times(self, fn, names):
+        """the HIP-event ms that the smr_*_times call `fn` reports, one per name -> dict"""
+        ms = (C.c_double * len(names))()
+        self._chk(getattr(self.L, fn)(self.h, ms), fn)
+        return dict(zip(names, (float(x) for x in ms)))
+
     def fastx_times(self):
         """HIP-event ms of the last upload_fastx on the device path: dict(h2d, lines, records, pack, d2h)"""
-        ms = (C.c_double * 5)()
-        self._chk(self.L.smr_fastx_times(self.h, ms), "smr_fastx_times")
-        return dict(zip(("h2d", "lines", "records", "pack", "d2h"), (float(x) for x in ms)))
+        return self._times("smr_fastx_times", ("h2d", "lines", "records", "pack", "d2h"))
 
     def fastx_split(self, layout=0, mates=None, paired_in=False, paired_out=False, out2=False, sout=False, aligned=True, other=True, hit=None):
         """smr_fastx_split: the aligned.* / other.* FASTX streams of the selected batch (uploaded with keep=True), written on the device -> a list
@@ -449,9 +453,7 @@ class Engine:
 
     def fastx_split_times(self):
         """HIP-event ms of the last fastx_split: dict(measure, scans, copy, d2h)"""
-        ms = (C.c_double * 4)()
-        self._chk(self.L.smr_fastx_split_times(self.h, ms), "smr_fastx_split_times")
-        return dict(zip(("measure", "scans", "copy", "d2h"), (float(x) for x in ms)))
+        return self._times("smr_fastx_split_times", ("measure", "scans", "copy", "d2h"))
 
     def rows_part(self, slot, params, index, sam=True, blast=False, cols="", lam=0.0, K=0.0, full_ref=0, full_read=0):
         """smr_rows_part: the rows of aligned.sam and of the BLAST tabular report of the selected batch (uploaded with keep=True) for the
@@ -472,9 +474,7 @@ class Engine:
 
     def rows_times(self):
         """HIP-event ms of the last rows_part: dict(stats, sizes, write, d2h)"""
-        ms = (C.c_double * 4)()
-        self._chk(self.L.smr_rows_times(self.h, ms), "smr_rows_times")
-        return dict(zip(("stats", "sizes", "write", "d2h"), (float(x) for x in ms)))
+        return self._times("smr_rows_times", ("stats", "sizes", "write", "d2h"))
 
     def pairwise_part(self, slot, params, index, lam=0.0, K=0.0, full_ref=0, full_read=0):
         """smr_pairwise_part: the BLAST-like pairwise text (-blast 0) of the selected batch (uploaded with keep=True) for the (index, part) of
@@ -489,9 +489,7 @@ class Engine:
 
     def pairwise_times(self):
         """HIP-event ms of the last pairwise_part: dict(stats, sizes, write, d2h)"""
-        ms = (C.c_double * 4)()
-        self._chk(self.L.smr_pairwise_times(self.h, ms), "smr_pairwise_times")
-        return dict(zip(("stats", "sizes", "write", "d2h"), (float(x) for x in ms)))
+        return self._times("smr_pairwise_times", ("stats", "sizes", "write", "d2h"))
 
     def otu_part(self, slot, params, index, min_id, min_cov):
         """smr_otu_part: the members of otu_map.txt of the selected batch (uploaded with keep=True, after idcov_part of every part) for the
@@ -510,9 +508,7 @@ class Engine:
 
     def otu_times(self):
         """HIP-event ms of the last otu_part: dict(classify, sizes, sort, write, d2h)"""
-        ms = (C.c_double * 5)()
-        self._chk(self.L.smr_otu_times(self.h, ms), "smr_otu_times")
-        return dict(zip(("classify", "sizes", "sort", "write", "d2h"), (float(x) for x in ms)))
+        return self._times("smr_otu_times", ("classify", "sizes", "sort", "write", "d2h"))
 
     def otu_sort_batch(self, keys, key_bits):
         """smr_otu_sort_batch (a test seam): the stable permutation that sorts keys (each below 2 ** key_bits) ascending, found by the radix
@@ -522,16 +518,20 @@ class Engine:
         self._chk(self.L.smr_otu_sort_batch(self.h, len(keys), keys.ctypes.data if len(keys) else None, int(key_bits), perm.ctypes.data), "smr_otu_sort_batch")
         return perm[:len(keys)]
 
+    @staticmethod
+    def _denovo_opts(opts, kw):
+        """a capi.FxSplitOpts as it is, or one made of a dict / keywords out of layout, paired_in, paired_out, out2, sout"""
+        if isinstance(opts, capi.FxSplitOpts):
+            return opts
+        d = dict(opts or {}, **kw)
+        return capi.FxSplitOpts(int(d.get("layout", 0)), int(bool(d.get("paired_in"))), int(bool(d.get("paired_out"))), int(bool(d.get("out2"))), int(bool(d.get("sout"))), 1, 0)
+
     def fastx_denovo(self, opts=None, mates=-1, dn=None, **kw):
         """smr_fastx_denovo: the aligned_denovo.* FASTX streams of the selected batch (uploaded with keep=True), written on the device -> a list
         of four bytes objects.  opts: a capi.FxSplitOpts, or a dict / keywords out of layout, paired_in, paired_out, out2, sout as fastx_split
         takes them (want_aligned / want_other are ignored); mates: the batch of the mates under layout 2, else -1.  dn: one truth value per
         read (the selected batch's, then the mates') used instead of the counters idcov_part left"""
-        if isinstance(opts, capi.FxSplitOpts):
-            o = opts
-        else:
-            d = dict(opts or {}, **kw)
-            o = capi.FxSplitOpts(int(d.get("layout", 0)), int(bool(d.get("paired_in"))), int(bool(d.get("paired_out"))), int(bool(d.get("out2"))), int(bool(d.get("sout"))), 1, 0)
+        o = self._denovo_opts(opts, kw)
         db = None if dn is None else (C.c_uint8 * max(len(dn), 1))(*[1 if x else 0 for x in dn])
         m = -1 if mates is None else int(mates)
         off = (C.c_uint64 * 5)()
@@ -569,9 +569,7 @@ class Engine:
 
     def gzip_times(self):
         """HIP-event ms of the last gzip_batch / fastx_split_gz / fastx_denovo_gz: dict(match, codes, encode, compact, d2h)"""
-        ms = (C.c_double * 5)()
-        self._chk(self.L.smr_gzip_times(self.h, ms), "smr_gzip_times")
-        return dict(zip(("match", "codes", "encode", "compact", "d2h"), (float(x) for x in ms)))
+        return self._times("smr_gzip_times", ("match", "codes", "encode", "compact", "d2h"))
 
     def _fx_gz(self, fn, n, o, flags, mates):
         fb = None if flags is None else (C.c_uint8 * max(len(flags), 1))(*[1 if x else 0 for x in flags])
@@ -594,11 +592,7 @@ class Engine:
 
     def fastx_denovo_gz(self, opts=None, mates=-1, dn=None, **kw):
         """smr_fastx_denovo_gz: the four streams of fastx_denovo, compressed on the device -> (four bytes objects, the five plain offsets)"""
-        if isinstance(opts, capi.FxSplitOpts):
-            o = opts
-        else:
-            d = dict(opts or {}, **kw)
-            o = capi.FxSplitOpts(int(d.get("layout", 0)), int(bool(d.get("paired_in"))), int(bool(d.get("paired_out"))), int(bool(d.get("out2"))), int(bool(d.get("sout"))), 1, 0)
+        o = self._denovo_opts(opts, kw)
         return self._fx_gz("smr_fastx_denovo_gz", 4, o, dn, mates)
 
     def rows_fmt_batch(self, num, den):
