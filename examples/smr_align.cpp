@@ -24,6 +24,8 @@
 // --zip device (needs --split device and gzipped reports): aligned.* / other.*, and with --otu device aligned_denovo.*, are deflated by the
 // DEFLATE kernels where the split leaves them (smr_fastx_split_gz / smr_fastx_denovo_gz) and appended to the .gz files as gzip members
 // (smr_report_add_fastx_gz / _add_denovo_gz); every file inflates to what --zip host writes.
+// --unzip device (needs --pack device): a gzip reads file goes to the device as it is and is inflated there by the DEFLATE decoder kernels
+// (SMR_FASTX_INFLATE) instead of by zlib on one host thread; the default, --unzip host, and every output file stay as they are.
 // Build:  g++ -std=c++17 -O2 examples/smr_align.cpp -Iinclude -Lsortmerna_amd/lib -lsmr_hip -Wl,-rpath,$PWD/sortmerna_amd/lib -o smr_align
 // There is no CPU fallback: without a HIP device smr_create fails and the program exits like the reference does (ERR + exit 1).
 #include <cstdint>
@@ -48,7 +50,7 @@ int main(int argc, char** argv) {
   smr_params base; smr_params_default(&base);
   double evalue = 1.0;
   int device = 0;
-  bool pack_device = false, split_device = false, rows_device = false, pair_device = false, otu_device = false, zip_device = false;
+  bool pack_device = false, split_device = false, rows_device = false, pair_device = false, otu_device = false, zip_device = false, unzip_device = false;
   bool id_given = false, cov_given = false;
   smr_report_opts ro; memset(&ro, 0, sizeof ro);
   for (int i = 1; i < argc; i++) {
@@ -77,6 +79,7 @@ int main(int argc, char** argv) {
     else if (a == "-split" || a == "--split") { const std::string v = val(); if (v != "host" && v != "device") die("--split: host or device"); split_device = v == "device"; }
     else if (a == "-rows" || a == "--rows") { const std::string v = val(); if (v != "host" && v != "device") die("--rows: host or device"); rows_device = v == "device"; }
     else if (a == "-pairwise" || a == "--pairwise") { const std::string v = val(); if (v != "host" && v != "device") die("--pairwise: host or device"); pair_device = v == "device"; }
+    else if (a == "-unzip" || a == "--unzip") { const std::string v = val(); if (v != "host" && v != "device") die("--unzip: host or device"); unzip_device = v == "device"; }
     else if (a == "-zip" || a == "--zip") { const std::string v = val(); if (v != "host" && v != "device") die("--zip: host or device"); zip_device = v == "device"; }
     else if (a == "-otu" || a == "--otu") { const std::string v = val(); if (v != "host" && v != "device") die("--otu: host or device"); otu_device = v == "device"; }
     else if (a == "-otu_map" || a == "--otu_map") ro.otu_map = 1;
@@ -105,11 +108,12 @@ int main(int argc, char** argv) {
       printf("usage: smr_align --ref DB.fasta --gumbel LAMBDA K [--idx PREFIX] [--ref ...] --reads READS.fa|fq[.gz] [--reads MATES] [--out DIR]\n"
              "       [-e EVALUE] [-num_alignments N] [-no-best] [-min_lis N] [-num_seeds N] [-edges N] [-full_search] [-F|-R]\n"
              "       [-match N -mismatch N -gap_open N -gap_ext N] [-device K] [--fastx] [--other] [--blast '0' | '1 cigar qcov qstrand'] [--sam [-SQ]]\n"
-             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [--zip host|device] [--rows host|device] [--pairwise host|device] [-otu_map [-id X] [-coverage X]] [-de_novo_otu] [--otu host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
+             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [--zip host|device] [--unzip host|device] [--rows host|device] [--pairwise host|device] [-otu_map [-id X] [-coverage X]] [-de_novo_otu] [--otu host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
       return 0;
     } else die("unknown option " + a);
   }
   if (split_device && !pack_device) die("--split device writes aligned.* / other.* from the text the device parsed: it needs --pack device");
+  if (unzip_device && !pack_device) die("--unzip device inflates a gzip reads file into the text buffer the device parses: it needs --pack device");
   if (rows_device && !pack_device) die("--rows device writes the SAM / BLAST rows from the text the device parsed: it needs --pack device");
   if (pair_device && !pack_device) die("--pairwise device writes the BLAST pairwise text from the text the device parsed: it needs --pack device");
   if (pair_device && !ro.blast_pairwise) die("--pairwise device writes the pairwise text of --blast 0: without --blast 0 there is none");
@@ -152,7 +156,7 @@ int main(int argc, char** argv) {
   for (size_t b = 0; b < rf.size(); b++) {
     if (pack_device) {
       if (smr_batch_select(gpu, (int)b) != SMR_OK) die(smr_last_error(gpu));
-      if (smr_reads_upload_fastx_file(gpu, reads_paths[b].c_str(), slots, SMR_FASTX_VIEW | ((split_device || rows_device || pair_device || (otu_device && idcov)) ? SMR_FASTX_KEEP : 0u), &rf[b], err, sizeof err) != SMR_OK) die(err);
+      if (smr_reads_upload_fastx_file(gpu, reads_paths[b].c_str(), slots, SMR_FASTX_VIEW | (unzip_device ? SMR_FASTX_INFLATE : 0u) | ((split_device || rows_device || pair_device || (otu_device && idcov)) ? SMR_FASTX_KEEP : 0u), &rf[b], err, sizeof err) != SMR_OK) die(err);
     } else if (smr_reads_load_fastx_text(reads_paths[b].c_str(), 0, &rf[b], err, sizeof err) != SMR_OK) die(err);
     n += smr_reads_count(rf[b]); total_len += smr_reads_total_len(rf[b]);
     if (smr_reads_count(rf[b])) { min_len = std::min(min_len, smr_reads_min_len(rf[b])); max_len = std::max(max_len, smr_reads_max_len(rf[b])); }

@@ -273,9 +273,16 @@ int smr_reads_upload_batch(smr_ctx*, int batch, const smr_reads*, uint32_t max_a
  * record's header line and first sequence line, the format: what smr_reads_record_text reads -- for smr_fastx_split.  The buffers the parser
  * kernels worked on are handed over, not copied (the upload's scratch allocates again on its next use); text the host parser walked is
  * uploaded with the parser's offsets.  Cost: the text plus 16 bytes per record of device memory until the batch is uploaded into again by any
- * upload call (which drops it) or the context is destroyed; smr_state_reset keeps it.  Without the flag nothing is kept and nothing changes. */
+ * upload call (which drops it) or the context is destroyed; smr_state_reset keeps it.  Without the flag nothing is kept and nothing changes.
+ * flags & SMR_FASTX_INFLATE (combines with both): bytes that begin 1f 8b are a gzip file; they go to the device compressed (the file call's
+ * straight from the mapping), are inflated there into the text buffer (smr_gunzip_batch below says how, and when the host inflates instead)
+ * and parsed from it: the H2D of the text disappears.  With out != NULL the inflated text is copied back once, into a buffer *out owns (also
+ * under the two buffer calls); with out == NULL only the totals cross the bus.  Inflated text of 2^32 - 64 bytes or more is SMR_ERR_CAPACITY.
+ * A file zlib refuses is SMR_ERR_IO with zlib's verdict ("<path>: truncated gzip stream", "<path>: corrupt gzip stream"), as without the
+ * flag.  Without the flag, or for bytes that are not gzip, nothing changes. */
 #define SMR_FASTX_VIEW 1u
 #define SMR_FASTX_KEEP 2u
+#define SMR_FASTX_INFLATE 4u
 int smr_reads_upload_fastx(smr_ctx*, const char* text, uint64_t n_bytes, uint32_t max_alignments_per_read, uint32_t flags, smr_reads** out);
 int smr_reads_upload_fastx_batch(smr_ctx*, int batch, const char* text, uint64_t n_bytes, uint32_t max_alignments_per_read, uint32_t flags, smr_reads** out);
 int smr_reads_upload_fastx_file(smr_ctx*, const char* path, uint32_t max_alignments_per_read, uint32_t flags, smr_reads** out, char* err, size_t errcap);
@@ -429,6 +436,34 @@ int smr_fastx_denovo_gz(smr_ctx*, int mates, const smr_fxsplit_opts*, const uint
 /* HIP-event milliseconds of the last of the three calls above: {matching + CRC, code building, bit packing, scan + compaction, bytes D2H}
  * (the last three 0 for a sizes-only call) */
 int smr_gzip_times(const smr_ctx*, double ms[5]);
+
+/* ---- gunzip on the device --------------------------------------------------------------------------------------------------------------
+ * A DEFLATE decoder in HIP kernels (csrc/smr_gunzip.hpp): a gzip file of any number of members, inflated by many waves at once.  The starts of
+ * non-final dynamic-Huffman blocks and of members are found speculatively; tasks at least `grain` compressed bytes apart (1: every candidate;
+ * 0: the default, 65 536, and 1 for a file of fewer than 4 096 candidates) are decoded with the 32 KiB in front of each as placeholders,
+ * stitched in file order, and the placeholders resolved;
+ * CRC-32 and ISIZE of every member are checked.  The host inflate (zlib) stays the definition of every answer and every refusal: whatever the
+ * device does not settle -- a decode error, a CRC-32 or ISIZE mismatch, a truncated file, bytes behind the last member, more stitching rounds
+ * than the build allows -- is inflated by zlib in the same call, whose result, or error code (SMR_ERR_IO) and message, is then the call's.
+ * smr_gunzip_batch: the n bytes at gz (HOST memory) -> plain.  plain == NULL: the size only.  cap < *need: SMR_ERR_CAPACITY, *need valid,
+ * nothing written.  Otherwise exactly *need bytes are written.  The call changes no stored state and may be repeated: the same bytes. */
+int smr_gunzip_batch(smr_ctx*, const uint8_t* gz, uint64_t n, uint64_t grain /* 0 = default */, uint8_t* plain, uint64_t cap, uint64_t* need);
+/* Of the last smr_gunzip_batch / inflating smr_reads_upload_fastx*:
+ *   info[0]  path | why << 8 | rounds << 16.  path 0: the device, 1: the host.  why: 0 -, 1 not a file the device takes (shorter than 18
+ *            bytes, 2^38 bytes or more, no member header at byte 0, more than 16 MiB per candidate or 64 MiB in one piece -- serial work
+ *            for one wave --, text beyond the caller's limit), 2 more candidates than the list holds, 3 rounds exhausted, 4 a decode
+ *            error, 5 a distance too far back, 6 a CRC-32 or ISIZE mismatch, 7 truncated, 8 bytes behind the last member, 9 a header CRC
+ *            mismatch.  rounds: counting passes run (1: every end hit a task start)
+ *   info[1]  candidates found        info[2]  tasks (on the device path: the confirmed ones)        info[3]  members
+ *   info[4]  stored blocks | fixed blocks << 32        info[5]  dynamic blocks        info[6]  compressed bytes        info[7]  plain bytes */
+int smr_gunzip_info(const smr_ctx*, uint64_t info[8]);
+/* HIP-event milliseconds of the last such call on the device path: {H2D, find, count, write, window, resolve + CRC} (0 on the host path) */
+int smr_gunzip_times(const smr_ctx*, double ms[6]);
+/* A TEST SEAM, not part of the stable interface (it may change or go with the decoder's inner workings; tests/helpers/gunzipdev.py compares
+ * the starts with a model's): the confirmed tasks of the last such call on the device path, in file order: start bit << 2 | 2 (not a candidate of the
+ * search: made by the stitch from a predecessor's end) | 1 (starts at a member header; else at a block header).  starts may be NULL;
+ * at most cap entries are written, *count is the number of tasks. */
+int smr_gunzip_tasks(const smr_ctx*, uint64_t* starts, uint64_t cap, uint64_t* count);
 /* Forget all per-read results/counters of the resident batch (reads stay resident). */
 int smr_state_reset(smr_ctx*);
 

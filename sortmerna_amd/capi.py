@@ -71,6 +71,7 @@ class Kprof(C.Structure):
 
 
 EXPORTS = [
+    "smr_gunzip_batch", "smr_gunzip_info", "smr_gunzip_times", "smr_gunzip_tasks",
     "smr_gzip_chunk", "smr_gzip_bound", "smr_gzip_batch", "smr_fastx_split_gz", "smr_fastx_denovo_gz", "smr_gzip_times", "smr_report_add_fastx_gz", "smr_report_add_denovo_gz",
     "smr_otu_part", "smr_otu_times", "smr_otu_sort_batch", "smr_fastx_denovo", "smr_report_add_otu", "smr_report_skip_otu", "smr_report_add_denovo", "smr_report_skip_denovo",
     "smr_params_default", "smr_params_refused", "smr_index_load_files", "smr_index_build", "smr_index_build_gpu", "smr_index_write_files", "smr_index_save", "smr_index_load_flat", "smr_index_selfcheck", "smr_index_free",
@@ -281,6 +282,14 @@ def bind(L):
     L.smr_fastx_denovo_gz.argtypes = [vp, i32, C.POINTER(FxSplitOpts), vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.smr_gzip_times.restype = i32
     L.smr_gzip_times.argtypes = [vp, C.POINTER(C.c_double)]
+    L.smr_gunzip_batch.restype = i32
+    L.smr_gunzip_batch.argtypes = [vp, vp, u64, u64, vp, u64, C.POINTER(u64)]
+    L.smr_gunzip_info.restype = i32
+    L.smr_gunzip_info.argtypes = [vp, C.POINTER(u64)]
+    L.smr_gunzip_times.restype = i32
+    L.smr_gunzip_times.argtypes = [vp, C.POINTER(C.c_double)]
+    L.smr_gunzip_tasks.restype = i32
+    L.smr_gunzip_tasks.argtypes = [vp, C.POINTER(u64), u64, C.POINTER(u64)]
     L.smr_report_add_fastx_gz.restype = i32
     L.smr_report_add_fastx_gz.argtypes = [vp, vp, C.POINTER(u64)]
     L.smr_report_add_denovo_gz.restype = i32

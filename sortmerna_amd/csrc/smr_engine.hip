@@ -21,6 +21,7 @@
 #include "smr_pairwise.hpp"
 #include "smr_otu.hpp"
 #include "smr_gzip.hpp"
+#include "smr_gunzip.hpp"
 #include "smr_ibuild.hpp"
 #include "smr_pgbuild.hpp"
 #include "smr_hostmem.hpp"
@@ -144,6 +145,13 @@ struct GzScratch {
   StageClock<4, 5> clk;                   // of the last call: match, code build, encode, scan + compact, D2H
 };
 
+// scratch and staging of the DEFLATE decoder (smr_gunzip.hpp), grow-only; one set per stream smr_reads_upload_fastx* can run on
+struct GunzScratch {
+  DevBuf<uint32_t> in, n_cand, crc; DevBuf<unsigned long long> cand; DevBuf<GunzTask> tasks; DevBuf<GunzRes> res; DevBuf<GunzUnit> units;
+  DevBuf<uint16_t> sym; DevBuf<uint8_t> win, out;
+  StageClock<8, 6> clk;                   // of the last call: H2D, find, count, write, window, resolve + CRC (reported through smr_ctx::gunz_ms)
+};
+
 struct smr_ctx {
   const Tuning tune;                      // the environment switches as smr_create found them (smr_tuning.hpp)
   explicit smr_ctx(const Tuning& t) : tune(t) {}
@@ -223,6 +231,10 @@ struct smr_ctx {
   StageClock<7, 4> pair_clk;              // of the last smr_pairwise_part (its device buffers are those of `rows`): guards / statistics, sizes and scans, write, D2H
   OtuScratch otu;
   GzScratch gz;
+  std::mutex gz_tab_m;                    // the CRC table of `gz` is made at its first use, on either stream
+  // the DEFLATE decoder: [0] on `stream`, [1] on `upload_stream`; smr_gunzip_info / _times / _tasks of the last call (written under err_m)
+  GunzScratch gunz[2];
+  uint64_t gunz_info[8] = {}; double gunz_ms[6] = {}; std::vector<uint64_t> gunz_tasks;
 };
 struct KpSave { double ms[KP_COUNT]; uint64_t l[KP_COUNT]; };
 
@@ -879,8 +891,9 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
 #include "smr_engine_idcov.hpp"
 #include "smr_engine_import.hpp"
 #include "smr_engine_export.hpp"
-#include "smr_engine_fastx.hpp"
 #include "smr_engine_gzip.hpp"
+#include "smr_engine_gunzip.hpp"
+#include "smr_engine_fastx.hpp"
 #include "smr_engine_fxsplit.hpp"
 #include "smr_engine_rows.hpp"
 #include "smr_engine_pairwise.hpp"

@@ -42,18 +42,62 @@ int fx_host_path(smr_ctx* c, Batch& B, hipStream_t st, const char* name, const c
   return SMR_OK;
 }
 
-int fastx_upload(smr_ctx* c, Batch& B, FxScratch& S, hipStream_t st, const char* name, const char* text, uint64_t n64, const std::shared_ptr<void>& owner, uint32_t max_aln,
-                 uint32_t flags, smr_reads** out) {
-  if (n64 >= 0xFFFFFFFFull - 63ull) { set_err(c, "smr_reads_upload_fastx: 2^32 - 64 bytes of text or more: hand the text over in pieces that end at record boundaries"); return SMR_ERR_CAPACITY; }
+#define FX_TEXT_LIMIT (0xFFFFFFFFull - 63ull)      // 2^32 - 64: text of that many bytes or more is SMR_ERR_CAPACITY
+// SMR_FASTX_INFLATE: the gzip file at gz -> its text, in S.text on the device (on_device; text_n bytes, the host has none of them yet), or,
+// where the device does not settle the file, inflated by zlib into a buffer `owner` keeps (the host's answer, or its refusal under `name`)
+int fx_inflate(smr_ctx* c, FxScratch& S, GunzScratch& G, hipStream_t st, const char* name, const uint8_t* gz, uint64_t n, std::shared_ptr<void>& owner, const char*& text,
+               uint64_t& text_n, bool& on_device) {
+  uint64_t plain = 0;
+  int rc = gunz_device(c, G, st, gz, n, 0, S.text, &plain, &on_device, FX_TEXT_LIMIT);
+  if (rc) return rc;
+  if (on_device) { owner.reset(); text = nullptr; text_n = plain; return SMR_OK; }
+  if (plain >= FX_TEXT_LIMIT) { owner.reset(); text = ""; text_n = plain; return SMR_OK; }      // (known after the counting pass: fastx_upload refuses it before it touches the text)
+  auto v = std::make_shared<std::vector<char>>();
+  std::string why;
+  if (!smr::gunzip_bytes(name, gz, (size_t)n, *v, why)) { set_err(c, why); return SMR_ERR_IO; }
+  owner = v; text = v->empty() ? "" : v->data(); text_n = v->size();
+  return SMR_OK;
+}
+inline bool fx_is_gzip(const void* p, uint64_t n) { return n >= 2 && ((const uint8_t*)p)[0] == 0x1Fu && ((const uint8_t*)p)[1] == 0x8Bu; }
+
+// on_device: the n64 bytes of text are in S.text already (fx_inflate) and `text` is not given.  The host then reads back what it needs: all of
+// the text once for *out or for the host parser, otherwise the first bytes, which say the format.
+int fastx_upload(smr_ctx* c, Batch& B, FxScratch& S, hipStream_t st, const char* name, const char* text, uint64_t n64, std::shared_ptr<void> owner, uint32_t max_aln,
+                 uint32_t flags, smr_reads** out, bool on_device = false) {
+  if (n64 >= FX_TEXT_LIMIT) { set_err(c, "smr_reads_upload_fastx: 2^32 - 64 bytes of text or more: hand the text over in pieces that end at record boundaries"); return SMR_ERR_CAPACITY; }
   if (max_aln == 0) max_aln = 1;
   if (out) *out = nullptr;
   const uint32_t n = (uint32_t)n64;
-  uint32_t first = 0;
-  while (first < n && (text[first] == '\n' || text[first] == '\r')) first++;
-  // no record at all, or neither format: the host parser's batch of 0 reads / its message
-  if (first >= n || (text[first] != '@' && text[first] != '>')) return fx_host_path(c, B, st, name, text, n, owner, max_aln, flags, out, 0, 0);
-  const uint32_t fastq = text[first] == '@';
   int rc;
+  uint32_t have = n;                                   // bytes of the text the host can read
+  std::vector<char> head;
+  auto fetch = [&]() -> int {                           // (on_device) the whole text, once
+    if (have == n && text) return SMR_OK;
+    auto v = std::make_shared<std::vector<char>>((size_t)n + 1u);
+    if (n) HIPCHK(c, hipMemcpyAsync(v->data(), S.text, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    owner = v; text = v->data(); have = n;
+    return SMR_OK;
+  };
+  if (on_device) {
+    if (out) { if ((rc = fetch())) return rc; }
+    else {
+      have = std::min<uint32_t>(n, 4096u);
+      head.resize((size_t)have + 1u);
+      if (have) HIPCHK(c, hipMemcpyAsync(head.data(), S.text, have, hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipStreamSynchronize(st));
+      text = head.data();
+    }
+  }
+  uint32_t first = 0;
+  while (first < have && (text[first] == '\n' || text[first] == '\r')) first++;
+  if (first >= have && have < n) {                      // (nothing but line ends so far)
+    if ((rc = fetch())) return rc;
+    while (first < n && (text[first] == '\n' || text[first] == '\r')) first++;
+  }
+  // no record at all, or neither format: the host parser's batch of 0 reads / its message
+  if (first >= n || (text[first] != '@' && text[first] != '>')) { if ((rc = fetch())) return rc; return fx_host_path(c, B, st, name, text, n, owner, max_aln, flags, out, 0, 0); }
+  const uint32_t fastq = text[first] == '@';
   if ((rc = S.clk.begin(c))) return rc;
   // ---- the text, padded for the aligned loads of the kernels
   const size_t cap = (((size_t)n + 15u) & ~(size_t)15u) + 64u;
@@ -62,7 +106,7 @@ int fastx_upload(smr_ctx* c, Batch& B, FxScratch& S, hipStream_t st, const char*
   uint32_t h_tot[FXT_COUNT] = {};
   h_tot[FXT_FIRST_BLANK_HDR] = ~0u; h_tot[FXT_MIN_LEN] = ~0u;
   if ((rc = S.clk.mark(c, 0, st))) return rc;
-  HIPCHK(c, hipMemcpyAsync(S.text, text, n, hipMemcpyHostToDevice, st));
+  if (!on_device) HIPCHK(c, hipMemcpyAsync(S.text, text, n, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemsetAsync(S.text + n, '\n', cap - n, st));
   HIPCHK(c, hipMemcpyAsync(S.tot, h_tot, sizeof h_tot, hipMemcpyHostToDevice, st));
   if ((rc = S.clk.mark(c, 1, st))) return rc;
@@ -97,7 +141,7 @@ int fastx_upload(smr_ctx* c, Batch& B, FxScratch& S, hipStream_t st, const char*
   if ((rc = S.clk.mark(c, 3, st))) return rc;
   HIPCHK(c, hipMemcpyAsync(h_tot, S.tot, sizeof h_tot, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
-  if (h_tot[FXT_FLAG]) return fx_host_path(c, B, st, name, text, n, owner, max_aln, flags, out, nl, n);
+  if (h_tot[FXT_FLAG]) { if ((rc = fetch())) return rc; return fx_host_path(c, B, st, name, text, n, owner, max_aln, flags, out, nl, n); }
   // ---- the batch
   const uint32_t R = h_tot[FXT_RECORDS], W = h_tot[FXT_WORDS];
   if ((rc = batch_reserve(c, B, W, R, h_tot[FXT_MIN_LEN], h_tot[FXT_MAX_LEN], max_aln, st))) return rc;
@@ -149,6 +193,11 @@ int fastx_upload(smr_ctx* c, Batch& B, FxScratch& S, hipStream_t st, const char*
 extern "C" int smr_reads_upload_fastx(smr_ctx* c, const char* text, uint64_t n_bytes, uint32_t max_aln, uint32_t flags, smr_reads** out) {
   if (!c || !text) return SMR_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
+  if ((flags & SMR_FASTX_INFLATE) && fx_is_gzip(text, n_bytes)) {
+    std::shared_ptr<void> owner; const char* p = nullptr; uint64_t n = 0; bool on_device = false;
+    const int rc = fx_inflate(c, c->fx[0], c->gunz[0], c->stream, "smr_reads_upload_fastx", (const uint8_t*)text, n_bytes, owner, p, n, on_device);
+    return rc ? rc : fastx_upload(c, *c->b, c->fx[0], c->stream, "", p, n, owner, max_aln, flags, out, on_device);
+  }
   return fastx_upload(c, *c->b, c->fx[0], c->stream, "", text, n_bytes, std::shared_ptr<void>(), max_aln, flags, out);
 }
 extern "C" int smr_reads_upload_fastx_batch(smr_ctx* c, int batch, const char* text, uint64_t n_bytes, uint32_t max_aln, uint32_t flags, smr_reads** out) {
@@ -158,14 +207,25 @@ extern "C" int smr_reads_upload_fastx_batch(smr_ctx* c, int batch, const char* t
     if (&c->bt[batch] == c->b) { std::lock_guard<std::mutex> l2(c->err_m); c->err = "smr_reads_upload_fastx_batch: the batch is the selected one (use smr_reads_upload_fastx)"; return SMR_ERR_STATE; }
   }
   HIPCHK(c, hipSetDevice(c->device));
+  if ((flags & SMR_FASTX_INFLATE) && fx_is_gzip(text, n_bytes)) {
+    std::shared_ptr<void> owner; const char* p = nullptr; uint64_t n = 0; bool on_device = false;
+    const int rc = fx_inflate(c, c->fx[1], c->gunz[1], c->upload_stream, "smr_reads_upload_fastx_batch", (const uint8_t*)text, n_bytes, owner, p, n, on_device);
+    return rc ? rc : fastx_upload(c, c->bt[batch], c->fx[1], c->upload_stream, "", p, n, owner, max_aln, flags, out, on_device);
+  }
   return fastx_upload(c, c->bt[batch], c->fx[1], c->upload_stream, "", text, n_bytes, std::shared_ptr<void>(), max_aln, flags, out);
 }
 extern "C" int smr_reads_upload_fastx_file(smr_ctx* c, const char* path, uint32_t max_aln, uint32_t flags, smr_reads** out, char* err, size_t errcap) {
   if (!c || !path) return SMR_ERR_ARG;
   std::shared_ptr<void> owner; const char* p = nullptr; size_t n = 0; std::string why;
   int rc;
-  if (!smr::fastx_slurp(path, owner, p, n, why)) { set_err(c, why); rc = SMR_ERR_IO; }
+  const bool inflate = (flags & SMR_FASTX_INFLATE) != 0;          // (a gzip file then stays as it is in the mapping)
+  if (!smr::fastx_slurp(path, owner, p, n, why, inflate)) { set_err(c, why); rc = SMR_ERR_IO; }
   else if (hipSetDevice(c->device) != hipSuccess) { set_err(c, "hipSetDevice failed"); rc = SMR_ERR_DEVICE; }
+  else if (inflate && fx_is_gzip(p, n)) {
+    std::shared_ptr<void> towner; const char* t = nullptr; uint64_t tn = 0; bool on_device = false;
+    rc = fx_inflate(c, c->fx[0], c->gunz[0], c->stream, path, (const uint8_t*)p, n, towner, t, tn, on_device);
+    if (rc == SMR_OK) rc = fastx_upload(c, *c->b, c->fx[0], c->stream, path, t, tn, towner, max_aln, flags, out, on_device);
+  }
   else rc = fastx_upload(c, *c->b, c->fx[0], c->stream, path, p ? p : "", n, owner, max_aln, flags, out);
   if (rc != SMR_OK && err && errcap) snprintf(err, errcap, "%s", smr_last_error(c));
   return rc;

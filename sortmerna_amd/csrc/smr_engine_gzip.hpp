@@ -27,6 +27,19 @@ void gz_crc_words(uint32_t* w) {
   for (uint32_t k = 0; k < 8u; k++) { memcpy(w + 256u + 32u * k, m, sizeof m); square(); }
 }
 
+// the table on the device, made at its first use (by the compressor, or by the decoder of smr_engine_gunzip.hpp on either stream)
+int gz_crc_table(smr_ctx* c, hipStream_t st) {
+  std::lock_guard<std::mutex> l_(c->gz_tab_m);
+  if (c->gz.crc_tab) return SMR_OK;
+  uint32_t w[GZ_CRC_WORDS];
+  gz_crc_words(w);
+  int rc;
+  if ((rc = c->gz.crc_tab.alloc(c, GZ_CRC_WORDS))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->gz.crc_tab, w, sizeof w, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipStreamSynchronize(st));                 // (w leaves the scope)
+  return SMR_OK;
+}
+
 // n_streams ranges [off[k], off[k + 1]) of d_in -> their gzip members, back to back, in gz (may be null: sizes only); gz_off[n_streams + 1]
 int gz_run(smr_ctx* c, const char* who, const uint8_t* d_in, const uint64_t* off, uint32_t n_streams, uint8_t* gz, uint64_t cap, uint64_t* gz_off, uint64_t* need) {
   GzScratch& S = c->gz;
@@ -50,13 +63,7 @@ int gz_run(smr_ctx* c, const char* who, const uint8_t* d_in, const uint64_t* off
   if (chunks.empty()) return SMR_OK;
   if (chunks.size() >= 0x7FFFFFFFull) { set_err(c, std::string(who) + ": 2^31 - 1 chunks or more"); return SMR_ERR_CAPACITY; }
   const uint32_t nc = (uint32_t)chunks.size(), round = std::min(nc, GZ_ROUND);
-  if (!S.crc_tab) {
-    uint32_t w[GZ_CRC_WORDS];
-    gz_crc_words(w);
-    if ((rc = S.crc_tab.alloc(c, GZ_CRC_WORDS))) return rc;
-    HIPCHK(c, hipMemcpyAsync(S.crc_tab, w, sizeof w, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));        // (w leaves the scope)
-  }
+  if ((rc = gz_crc_table(c, c->stream))) return rc;
   if ((rc = S.chunks.reserve(c, nc)) || (rc = S.slot_off.reserve(c, nc)) || (rc = S.sizes.reserve(c, (size_t)nc + 1u)) || (rc = S.codes.reserve(c, nc)) ||
       (rc = S.crc.reserve(c, nc)) || (rc = S.tok.reserve(c, (size_t)round * GZ_TOK_STRIDE)) || (rc = S.freq.reserve(c, (size_t)round * GZ_FREQ_STRIDE)) ||
       (rc = S.ntok.reserve(c, round))) return rc;

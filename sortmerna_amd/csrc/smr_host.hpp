@@ -144,7 +144,9 @@ struct smr_reads {
 
 namespace smr {
 // smr_reads.cpp, for smr_reads_upload_fastx* of smr_engine.hip: the file as bytes (mapped, or inflated when it is gzip; owner keeps them alive),
-// and the host parser on bytes -- what smr_reads_load_fastx_mt / _text run after mapping the file
-bool fastx_slurp(const char* path, std::shared_ptr<void>& owner, const char*& p, size_t& n, std::string& why);
+// and the host parser on bytes -- what smr_reads_load_fastx_mt / _text run after mapping the file.  raw: a gzip file is not inflated
+bool fastx_slurp(const char* path, std::shared_ptr<void>& owner, const char*& p, size_t& n, std::string& why, bool raw = false);
 int load_fastx_bytes(const char* name, const char* p, size_t n, std::shared_ptr<void> owner, uint32_t threads, bool keep_text, smr_reads** out, std::string& why);
+// the host inflate of a gzip file that is in memory (zlib; the body of fastx_slurp's): false and why = "<name>: truncated | corrupt gzip stream"
+bool gunzip_bytes(const char* name, const unsigned char* u, size_t n, std::vector<char>& own, std::string& why);
 }

@@ -123,7 +123,35 @@ struct Bytes {              // the input text: a private mapping of the file, or
   const char* p = nullptr; size_t n = 0; void* map = nullptr; size_t map_n = 0; std::vector<char> own;
   ~Bytes() { if (map) munmap(map, map_n); }
 };
-bool slurp(const char* path, Bytes& b, std::string& why) {
+}  // namespace
+// zlib over the n bytes at u, a gzip file of one or more members -> own; false and `why` ("<name>: truncated gzip stream", "<name>: corrupt gzip
+// stream") where zlib refuses.  The one host inflate: of slurp below and of the calls that hand a gzip file to the device (smr_engine_gunzip.hpp)
+bool smr::gunzip_bytes(const char* name, const unsigned char* u, size_t n, std::vector<char>& own, std::string& why) {
+  z_stream z; memset(&z, 0, sizeof z);
+  if (inflateInit2(&z, 15 + 16) != Z_OK) { why = "inflateInit2 failed"; return false; }
+  own.resize(std::max<size_t>(n * 4, 1u << 16));
+  size_t out = 0, fed = 0;
+  z.next_in = (Bytef*)u; z.avail_in = 0;
+  for (;;) {
+    if (z.avail_in == 0 && fed < n) { const size_t c = std::min<size_t>(n - fed, 1u << 30); z.next_in = (Bytef*)u + fed; z.avail_in = (uInt)c; fed += c; }
+    if (out == own.size()) own.resize(own.size() * 2);
+    z.next_out = (Bytef*)own.data() + out; z.avail_out = (uInt)std::min<size_t>(own.size() - out, 1u << 30);
+    const uInt room = z.avail_out;
+    const int rc = inflate(&z, Z_NO_FLUSH);
+    out += room - z.avail_out;
+    if (rc == Z_STREAM_END) {
+      if (z.avail_in == 0 && fed == n) break;
+      if (inflateReset(&z) != Z_OK) { inflateEnd(&z); why = "inflateReset failed"; return false; }   // next member
+    } else if (rc == Z_BUF_ERROR) {
+      if (z.avail_in == 0 && fed == n && z.avail_out != 0) { inflateEnd(&z); why = std::string(name) + ": truncated gzip stream"; return false; }
+    } else if (rc != Z_OK) { inflateEnd(&z); why = std::string(name) + ": corrupt gzip stream"; return false; }
+  }
+  inflateEnd(&z);
+  own.resize(out);
+  return true;
+}
+namespace {
+bool slurp(const char* path, Bytes& b, std::string& why, bool raw) {
   int fd = open(path, O_RDONLY);
   if (fd < 0) { why = std::string("cannot open ") + path; return false; }
   struct stat st;
@@ -135,30 +163,10 @@ bool slurp(const char* path, Bytes& b, std::string& why) {
   madvise(m, (size_t)st.st_size, MADV_WILLNEED);
   b.map = m; b.map_n = (size_t)st.st_size;
   const unsigned char* u = (const unsigned char*)m;
-  if (b.map_n >= 2 && u[0] == 0x1f && u[1] == 0x8b) {   // gzip (possibly several members back to back)
-    z_stream z; memset(&z, 0, sizeof z);
-    if (inflateInit2(&z, 15 + 16) != Z_OK) { why = "inflateInit2 failed"; return false; }
-    b.own.resize(std::max<size_t>(b.map_n * 4, 1u << 16));
-    size_t out = 0, fed = 0;
-    z.next_in = (Bytef*)u; z.avail_in = 0;
-    for (;;) {
-      if (z.avail_in == 0 && fed < b.map_n) { const size_t c = std::min<size_t>(b.map_n - fed, 1u << 30); z.next_in = (Bytef*)u + fed; z.avail_in = (uInt)c; fed += c; }
-      if (out == b.own.size()) b.own.resize(b.own.size() * 2);
-      z.next_out = (Bytef*)b.own.data() + out; z.avail_out = (uInt)std::min<size_t>(b.own.size() - out, 1u << 30);
-      const uInt room = z.avail_out;
-      const int rc = inflate(&z, Z_NO_FLUSH);
-      out += room - z.avail_out;
-      if (rc == Z_STREAM_END) {
-        if (z.avail_in == 0 && fed == b.map_n) break;
-        if (inflateReset(&z) != Z_OK) { inflateEnd(&z); why = "inflateReset failed"; return false; }   // next member
-      } else if (rc == Z_BUF_ERROR) {
-        if (z.avail_in == 0 && fed == b.map_n && z.avail_out != 0) { inflateEnd(&z); why = std::string(path) + ": truncated gzip stream"; return false; }
-      } else if (rc != Z_OK) { inflateEnd(&z); why = std::string(path) + ": corrupt gzip stream"; return false; }
-    }
-    inflateEnd(&z);
-    b.own.resize(out);
+  if (!raw && b.map_n >= 2 && u[0] == 0x1f && u[1] == 0x8b) {   // gzip (possibly several members back to back)
+    if (!smr::gunzip_bytes(path, u, b.map_n, b.own, why)) return false;
     munmap(b.map, b.map_n); b.map = nullptr;
-    b.p = b.own.data(); b.n = out;
+    b.p = b.own.data(); b.n = b.own.size();
   } else { b.p = (const char*)m; b.n = b.map_n; }
   return true;
 }
@@ -272,9 +280,9 @@ int smr::load_fastx_bytes(const char* name, const char* p, size_t n, std::shared
   return SMR_OK;
 }
 
-bool smr::fastx_slurp(const char* path, std::shared_ptr<void>& owner, const char*& p, size_t& n, std::string& why) {
+bool smr::fastx_slurp(const char* path, std::shared_ptr<void>& owner, const char*& p, size_t& n, std::string& why, bool raw) {
   auto bp = std::make_shared<Bytes>();
-  if (!slurp(path, *bp, why)) return false;
+  if (!slurp(path, *bp, why, raw)) return false;
   p = bp->p; n = bp->n; owner = bp;
   return true;
 }

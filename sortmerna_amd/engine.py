@@ -239,6 +239,8 @@ def pigeonhole_layout(index):
 ROUTE_RECORD, ROUTE_GATHER, ROUTE_CHAIN, ROUTE_EXT = 1, 2, 4, 8      # SMR_ROUTE_* of smr_hip.h (Engine.cand_routes)
 FASTX_VIEW = 1                                                       # SMR_FASTX_VIEW (Engine.upload_fastx)
 FASTX_KEEP = 2                                                       # SMR_FASTX_KEEP
+FASTX_INFLATE = 4                                                    # SMR_FASTX_INFLATE
+GUNZIP_WHY = ("", "not taken", "candidates", "rounds", "decode", "distance", "check", "truncated", "trailing", "header crc")      # smr_gunzip_info
 
 
 class Engine:
@@ -392,14 +394,14 @@ class Engine:
         self._chk(self.L.smr_reads_upload_batch(self.h, batch, reads.h, max_alignments_per_read), "smr_reads_upload_batch")
         self._batch_n[batch] = reads.count
 
-    def upload_fastx(self, data_or_path, max_alignments_per_read=1, batch=None, view=False, keep=False):
+    def upload_fastx(self, data_or_path, max_alignments_per_read=1, batch=None, view=False, keep=False, inflate=False):
         """smr_reads_upload_fastx*: FASTA/FASTQ text (bytes), or the file at a path (str; gzip is inflated), parsed and 2-bit packed on the device
         into the selected batch -- or, with batch=k, into batch k on the upload stream.  Returns the Reads the host parser would have made of
         the same bytes, copied back from the device; view=True leaves the packed words there (SMR_FASTX_VIEW: record_text and the statistics
         work, digest is 0, slice and upload raise).  keep=True leaves the text with the batch on the device (SMR_FASTX_KEEP: the text plus 16 bytes
-        per record of device memory) for fastx_split."""
+        per record of device memory) for fastx_split.  inflate=True: a gzip file (or gzip bytes) is inflated on the device (SMR_FASTX_INFLATE)."""
         h = C.c_void_p()
-        flags = (FASTX_VIEW if view else 0) | (FASTX_KEEP if keep else 0)
+        flags = (FASTX_VIEW if view else 0) | (FASTX_KEEP if keep else 0) | (FASTX_INFLATE if inflate else 0)
         keep = None
         if isinstance(data_or_path, str):
             if batch is not None:
@@ -566,6 +568,38 @@ class Engine:
         self._chk(self.L.smr_gzip_batch(self.h, plain.ctypes.data, off, n, buf.ctypes.data, cap, gz_off, C.byref(need)), "smr_gzip_batch")
         raw = buf[:need.value].tobytes()
         return [raw[gz_off[k]:gz_off[k + 1]] for k in range(n)]
+
+    def gunzip_batch(self, blob, grain=0):
+        """smr_gunzip_batch: the gzip file `blob` (bytes, any number of members) inflated by the DEFLATE decoder kernels -> bytes.  grain: the
+        least distance of two tasks in compressed bytes (0: the default, 1: a task at every candidate).  What the device does not settle is
+        inflated by zlib inside the call (gunzip_info says which); a file zlib refuses raises SmrError."""
+        gz = np.frombuffer(bytes(blob) or b"\0", dtype=np.uint8)
+        need = C.c_uint64(0)
+        self._chk(self.L.smr_gunzip_batch(self.h, gz.ctypes.data, len(blob), int(grain), None, 0, C.byref(need)), "smr_gunzip_batch")
+        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
+        self._chk(self.L.smr_gunzip_batch(self.h, gz.ctypes.data, len(blob), int(grain), buf.ctypes.data, need.value, C.byref(need)), "smr_gunzip_batch")
+        return buf[:need.value].tobytes()
+
+    def gunzip_info(self):
+        """smr_gunzip_info of the last gunzip_batch / inflating upload_fastx: dict(path "device" | "host", why (a word of GUNZIP_WHY), rounds,
+        candidates, tasks, members, stored, fixed, dynamic (blocks), compressed, plain (bytes))"""
+        info = (C.c_uint64 * 8)()
+        self._chk(self.L.smr_gunzip_info(self.h, info), "smr_gunzip_info")
+        v = [int(x) for x in info]
+        return dict(path="host" if v[0] & 0xFF else "device", why=GUNZIP_WHY[(v[0] >> 8) & 0xFF], rounds=v[0] >> 16, candidates=v[1], tasks=v[2], members=v[3],
+                    stored=v[4] & 0xFFFFFFFF, fixed=v[4] >> 32, dynamic=v[5], compressed=v[6], plain=v[7])
+
+    def gunzip_times(self):
+        """HIP-event ms of the last gunzip_batch / inflating upload_fastx on the device path: dict(h2d, find, count, write, window, resolve)"""
+        return self._times("smr_gunzip_times", ("h2d", "find", "count", "write", "window", "resolve"))
+
+    def gunzip_tasks(self):
+        """smr_gunzip_tasks (a test seam): the confirmed tasks of the last call on the device path -> [(start bit, at a member header, made by the stitch)]"""
+        n = C.c_uint64(0)
+        self._chk(self.L.smr_gunzip_tasks(self.h, None, 0, C.byref(n)), "smr_gunzip_tasks")
+        buf = (C.c_uint64 * max(n.value, 1))()
+        self._chk(self.L.smr_gunzip_tasks(self.h, buf, n.value, C.byref(n)), "smr_gunzip_tasks")
+        return [(int(x) >> 2, bool(x & 1), bool(x & 2)) for x in buf[:n.value]]
 
     def gzip_times(self):
         """HIP-event ms of the last gzip_batch / fastx_split_gz / fastx_denovo_gz: dict(match, codes, encode, compact, d2h)"""
