@@ -24,6 +24,10 @@
 // --zip device (needs --split device and gzipped reports): aligned.* / other.*, and with --otu device aligned_denovo.*, are deflated by the
 // DEFLATE kernels where the split leaves them (smr_fastx_split_gz / smr_fastx_denovo_gz) and appended to the .gz files as gzip members
 // (smr_report_add_fastx_gz / _add_denovo_gz); every file inflates to what --zip host writes.
+// --ziprows device (needs --rows device or --pairwise device, and gzipped reports): the SAM / BLAST rows and the pairwise text are deflated
+// where those calls leave them, in members that end at line ends (smr_rows_part_gz / smr_pairwise_part_gz), and kept by the report as gzip
+// members until it closes (smr_report_add_rows_gz / _add_pairwise_gz); aligned.sam.gz and aligned.blast.gz inflate to what --ziprows host
+// writes.  Independent of --split and --zip.
 // --unzip device (needs --pack device): a gzip reads file goes to the device as it is and is inflated there by the DEFLATE decoder kernels
 // (SMR_FASTX_INFLATE) instead of by zlib on one host thread; the default, --unzip host, and every output file stay as they are.
 // Build:  g++ -std=c++17 -O2 examples/smr_align.cpp -Iinclude -Lsortmerna_amd/lib -lsmr_hip -Wl,-rpath,$PWD/sortmerna_amd/lib -o smr_align
@@ -50,7 +54,7 @@ int main(int argc, char** argv) {
   smr_params base; smr_params_default(&base);
   double evalue = 1.0;
   int device = 0;
-  bool pack_device = false, split_device = false, rows_device = false, pair_device = false, otu_device = false, zip_device = false, unzip_device = false;
+  bool pack_device = false, split_device = false, rows_device = false, pair_device = false, otu_device = false, zip_device = false, unzip_device = false, ziprows_device = false;
   bool id_given = false, cov_given = false;
   smr_report_opts ro; memset(&ro, 0, sizeof ro);
   for (int i = 1; i < argc; i++) {
@@ -81,6 +85,7 @@ int main(int argc, char** argv) {
     else if (a == "-pairwise" || a == "--pairwise") { const std::string v = val(); if (v != "host" && v != "device") die("--pairwise: host or device"); pair_device = v == "device"; }
     else if (a == "-unzip" || a == "--unzip") { const std::string v = val(); if (v != "host" && v != "device") die("--unzip: host or device"); unzip_device = v == "device"; }
     else if (a == "-zip" || a == "--zip") { const std::string v = val(); if (v != "host" && v != "device") die("--zip: host or device"); zip_device = v == "device"; }
+    else if (a == "-ziprows" || a == "--ziprows") { const std::string v = val(); if (v != "host" && v != "device") die("--ziprows: host or device"); ziprows_device = v == "device"; }
     else if (a == "-otu" || a == "--otu") { const std::string v = val(); if (v != "host" && v != "device") die("--otu: host or device"); otu_device = v == "device"; }
     else if (a == "-otu_map" || a == "--otu_map") ro.otu_map = 1;
     else if (a == "-de_novo_otu" || a == "--de_novo_otu") ro.denovo = 1;
@@ -108,7 +113,7 @@ int main(int argc, char** argv) {
       printf("usage: smr_align --ref DB.fasta --gumbel LAMBDA K [--idx PREFIX] [--ref ...] --reads READS.fa|fq[.gz] [--reads MATES] [--out DIR]\n"
              "       [-e EVALUE] [-num_alignments N] [-no-best] [-min_lis N] [-num_seeds N] [-edges N] [-full_search] [-F|-R]\n"
              "       [-match N -mismatch N -gap_open N -gap_ext N] [-device K] [--fastx] [--other] [--blast '0' | '1 cigar qcov qstrand'] [--sam [-SQ]]\n"
-             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [--zip host|device] [--unzip host|device] [--rows host|device] [--pairwise host|device] [-otu_map [-id X] [-coverage X]] [-de_novo_otu] [--otu host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
+             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [--zip host|device] [--ziprows host|device] [--unzip host|device] [--rows host|device] [--pairwise host|device] [-otu_map [-id X] [-coverage X]] [-de_novo_otu] [--otu host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
       return 0;
     } else die("unknown option " + a);
   }
@@ -143,6 +148,8 @@ int main(int argc, char** argv) {
   ro.zip_out = zip_out;
   if (zip_device && !split_device) die("--zip device compresses the aligned.* / other.* streams where --split device leaves them: it needs --split device");
   if (zip_device && !zip_out) die("--zip device writes gzip members: the reports of this run are not gzipped (a plain reads file without -zip-out 1, or -zip-out 0)");
+  if (ziprows_device && !rows_device && !pair_device) die("--ziprows device compresses the SAM / BLAST rows and the pairwise text where --rows device and --pairwise device leave them: it needs one of the two");
+  if (ziprows_device && !zip_out) die("--ziprows device writes gzip members: the reports of this run are not gzipped (a plain reads file without -zip-out 1, or -zip-out 0)");
   char err[512] = "";
   // reads (Readfeed::next -> Read::init, readfeed.hpp:124 / read.cpp:264-347)
   // (all cores parse and 2-bit pack the FASTA / FASTQ / .gz file; the text stays mapped for the report writers)
@@ -294,13 +301,29 @@ int main(int argc, char** argv) {
         p.part = (uint32_t)part;
         if (!keep_part && smr_index_upload(gpu, dbs[k].parts[part], 0) != SMR_OK) die(smr_last_error(gpu));
         uint64_t off[3], need = 0;
-        if (rows_dev) {
+        // --ziprows device: the buffer is sized once, by smr_gzip_lines_bound of what a sizes-only PLAIN call returns (two cheap kernels); a
+        // sizes-only _gz call would run the matching, most of a compression, twice
+        if (rows_dev && ziprows_device) {
+          uint64_t gz_off[3];
+          if (smr_rows_part(gpu, 0, &p, dbs[k].parts[part], &wo, nullptr, 0, off, &need) != SMR_OK) die(smr_last_error(gpu));
+          const uint64_t bound = smr_gzip_lines_bound(need, 2);
+          if (rb.size() < bound + 1) rb.resize((size_t)bound + 1);
+          if (smr_rows_part_gz(gpu, 0, &p, dbs[k].parts[part], &wo, rb.data(), bound, gz_off, off, &need) != SMR_OK) die(smr_last_error(gpu));
+          if (smr_report_add_rows_gz(rep, (uint32_t)k, (uint32_t)part, rb.data(), gz_off) != SMR_OK) die(smr_report_last_error(rep));
+        } else if (rows_dev) {
           if (smr_rows_part(gpu, 0, &p, dbs[k].parts[part], &wo, nullptr, 0, off, &need) != SMR_OK) die(smr_last_error(gpu));
           if (rb.size() < need + 1) rb.resize((size_t)need + 1);
           if (need && smr_rows_part(gpu, 0, &p, dbs[k].parts[part], &wo, rb.data(), need, off, &need) != SMR_OK) die(smr_last_error(gpu));
           if (smr_report_add_rows(rep, (uint32_t)k, (uint32_t)part, rb.data(), off) != SMR_OK) die(smr_report_last_error(rep));
         }
-        if (pair_dev) {
+        if (pair_dev && ziprows_device) {
+          uint64_t plain = 0;
+          if (smr_pairwise_part(gpu, 0, &p, dbs[k].parts[part], wo.lambda, wo.K, wo.full_ref_corr, wo.full_read_corr, nullptr, 0, &need) != SMR_OK) die(smr_last_error(gpu));
+          const uint64_t bound = smr_gzip_lines_bound(need, 1);
+          if (rb.size() < bound + 1) rb.resize((size_t)bound + 1);
+          if (smr_pairwise_part_gz(gpu, 0, &p, dbs[k].parts[part], wo.lambda, wo.K, wo.full_ref_corr, wo.full_read_corr, rb.data(), bound, &plain, &need) != SMR_OK) die(smr_last_error(gpu));
+          if (smr_report_add_pairwise_gz(rep, (uint32_t)k, (uint32_t)part, rb.data(), need) != SMR_OK) die(smr_report_last_error(rep));
+        } else if (pair_dev) {
           if (smr_pairwise_part(gpu, 0, &p, dbs[k].parts[part], wo.lambda, wo.K, wo.full_ref_corr, wo.full_read_corr, nullptr, 0, &need) != SMR_OK) die(smr_last_error(gpu));
           if (rb.size() < need + 1) rb.resize((size_t)need + 1);
           if (need && smr_pairwise_part(gpu, 0, &p, dbs[k].parts[part], wo.lambda, wo.K, wo.full_ref_corr, wo.full_read_corr, rb.data(), need, &need) != SMR_OK) die(smr_last_error(gpu));

@@ -433,8 +433,30 @@ int smr_fastx_split_gz(smr_ctx*, int mates, const smr_fxsplit_opts*, const uint8
                        uint8_t* gz, uint64_t cap, uint64_t gz_off[9], uint64_t plain_off[9], uint64_t* need);
 int smr_fastx_denovo_gz(smr_ctx*, int mates, const smr_fxsplit_opts*, const uint8_t* dn,
                         uint8_t* gz, uint64_t cap, uint64_t gz_off[5], uint64_t plain_off[5], uint64_t* need);
-/* HIP-event milliseconds of the last of the three calls above: {matching + CRC, code building, bit packing, scan + compaction, bytes D2H}
- * (the last three 0 for a sizes-only call) */
+/* The same compressor with members that end at line ends, for text made of rows.  Nominal cuts lie every 48 KiB (the pitch) of a stream; each
+ * is moved back to behind the last '\n' of the 16 KiB (the window) in front of it, and stays where it is when the window holds none: a line
+ * longer than 16 KiB is cut wherever the grid falls, which is no error.  A stream of n bytes gives ceil(n / pitch) members of at most 64 KiB -
+ * 1 plain bytes each; any prefix of the members of a text whose lines are shorter than the window inflates to whole lines.  Every cut is a
+ * function of the text alone (a kernel on a fixed grid, csrc/smr_gzip.hpp), so the output is as deterministic as smr_gzip_batch's.
+ * smr_gzip_lines_bound: no output for plain_bytes in n_streams streams is larger (smr_gzip_bound of plain_bytes / pitch + n_streams members).
+ * smr_gzip_lines_batch: the contract of smr_gzip_batch, argument for argument. */
+uint64_t smr_gzip_lines_bound(uint64_t plain_bytes, uint32_t n_streams);
+int smr_gzip_lines_batch(smr_ctx*, const uint8_t* plain, const uint64_t* off /* n_streams + 1 */, uint32_t n_streams,
+                         uint8_t* gz, uint64_t cap, uint64_t* gz_off /* n_streams + 1 */, uint64_t* need);
+/* smr_rows_part / smr_pairwise_part whose text stays on the device and crosses the bus as gzip members cut at line ends: the same guard, size
+ * and write kernels, then the compressor on the engine's stream.  Arguments, guards, refusals (their messages name the _gz call), call order
+ * and the state contract are the plain calls'; plain_off / *plain_bytes is what the plain call returns in off / *need.  Stream k (SAM rows,
+ * BLAST rows) is gz[gz_off[k], gz_off[k + 1]), gz_off[2] = *need; of smr_pairwise_part_gz the members are gz[0, *need).  A stream that is not
+ * wanted or holds no row has no byte.  gz == NULL: sizes only (the text is written and compressed but for the bit packing); cap < *need:
+ * SMR_ERR_CAPACITY with the offsets and *need valid and nothing written; otherwise exactly *need bytes, at most smr_gzip_lines_bound(plain
+ * bytes, streams).  The calls change no stored state and may be repeated: the same bytes.  smr_rows_times / smr_pairwise_times then report
+ * 0 for the copy that was not made; smr_gzip_times has the compressor's share. */
+int smr_rows_part_gz(smr_ctx*, int slot, const smr_params*, const smr_index* ix, const smr_rows_opts*,
+                     uint8_t* gz, uint64_t cap, uint64_t gz_off[3], uint64_t plain_off[3], uint64_t* need);
+int smr_pairwise_part_gz(smr_ctx*, int slot, const smr_params*, const smr_index* ix, double lambda, double K, uint64_t full_ref_corr, uint64_t full_read_corr,
+                         uint8_t* gz, uint64_t cap, uint64_t* plain_bytes, uint64_t* need);
+/* HIP-event milliseconds of the compressor in the last of the calls above: {matching + CRC (with the line cuts, where there are any), code
+ * building, bit packing, scan + compaction, bytes D2H} (the last three 0 for a sizes-only call) */
 int smr_gzip_times(const smr_ctx*, double ms[5]);
 
 /* ---- gunzip on the device --------------------------------------------------------------------------------------------------------------
@@ -760,6 +782,15 @@ int smr_report_skip_denovo(smr_report*, int on);
  * decrease.  A report that never sees one of these calls writes the bytes it always wrote. */
 int smr_report_add_fastx_gz(smr_report*, const uint8_t* gz, const uint64_t gz_off[9]);
 int smr_report_add_denovo_gz(smr_report*, const uint8_t* gz, const uint64_t gz_off[5]);
+/* The gzip members of smr_rows_part_gz / smr_pairwise_part_gz for (index_num, part): kept with the rows of that key, behind what the key holds
+ * already.  smr_report_close writes the keys in key order as ever and the pieces of a key in call order: plain rows through zlib, members as
+ * they are (what zlib holds is closed as a member first).  The SAM header stays plain text and comes first.  Any mix of these calls with
+ * smr_report_add / _add_rows / _add_pairwise, over any order of keys, leaves valid multi-member files that inflate to exactly what the plain
+ * calls alone would have written.  SMR_ERR_ARG, and nothing is appended: a report not opened with zip_out, a stream that is not empty for a
+ * report not opened for it (sam / blast_tabular; blast_pairwise without blast_tabular), decreasing offsets, an (index, part) that was not
+ * registered.  A report that never sees one of these calls writes the bytes it always wrote. */
+int smr_report_add_rows_gz(smr_report*, uint32_t index_num, uint32_t part, const uint8_t* gz, const uint64_t gz_off[3]);
+int smr_report_add_pairwise_gz(smr_report*, uint32_t index_num, uint32_t part, const uint8_t* gz, uint64_t n);
 /* *total_otu = lines of otu_map.txt (Readstats::total_otu, for smr_summary), stored when smr_report_close runs: the pointer must live until then */
 int smr_report_otu_count(smr_report*, uint64_t* total_otu);
 /* One otu_map.txt for a run whose reads went through several report objects (one per device, each fed a contiguous shard of the reads in input

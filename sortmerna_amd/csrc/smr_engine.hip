@@ -140,7 +140,7 @@ struct OtuScratch {
 
 // scratch and staging of the DEFLATE kernels (smr_gzip.hpp), grow-only
 struct GzScratch {
-  DevBuf<uint8_t> in, slots, out; DevBuf<GzChunk> chunks; DevBuf<GzCode> codes; DevBuf<unsigned long long> slot_off, sizes;
+  DevBuf<uint8_t> in, slots, out; DevBuf<GzChunk> chunks; DevBuf<GzCode> codes; DevBuf<unsigned long long> slot_off, sizes, cut_tab;
   DevBuf<uint32_t> crc_tab, crc, tok, freq, ntok;
   StageClock<4, 5> clk;                   // of the last call: match, code build, encode, scan + compact, D2H
 };

@@ -3,14 +3,20 @@
 // smr_results_fetch + smr_reads_record_text + smr_result_record + smr_report_add do on the host one read at a time.  The host's share is that of
 // smr_rows_part, whose pieces are used as they are: the preamble of a per-part call (PartCall), the names of the part's references (rows_names),
 // the e-value / bit-score texts per score (rows_table), the guards of k_rows_stat (rows_guard), the device buffers of RowsScratch; two small
-// copies back (the error counts, the total) and the bytes.  Its times are its own (smr_ctx::pair_clk).
+// copies back (the error counts, the total) and the bytes -- or, for smr_pairwise_part_gz, the gzip members that gz_run makes of the text where
+// it lies.  Its times are its own (smr_ctx::pair_clk).
 
-extern "C" int smr_pairwise_part(smr_ctx* c, int slot, const smr_params* p, const smr_index* ix, double lambda, double K, uint64_t full_ref_corr,
-                                 uint64_t full_read_corr, uint8_t* bytes, uint64_t cap, uint64_t* need) {
-  static const char* const who = "smr_pairwise_part";
-  if (!c || !need) return SMR_ERR_ARG;
+namespace {
+// The writer behind smr_pairwise_part (plain_bytes null: `bytes` takes the text, *need its size) and smr_pairwise_part_gz (plain_bytes given:
+// the text stays on the device and goes through gz_run with cuts at line ends, `bytes` takes the gzip members, *need their size, *plain_bytes
+// what the plain call returns)
+int pair_impl(smr_ctx* c, const char* who, int slot, const smr_params* p, const smr_index* ix, double lambda, double K, uint64_t full_ref_corr, uint64_t full_read_corr,
+              uint8_t* bytes, uint64_t cap, uint64_t* plain_bytes, uint64_t* need) {
+  const bool zip = plain_bytes != nullptr;
+  const std::string W = std::string(who) + ": ";
   *need = 0;
-  if (!ix || slot < 0 || slot >= 64) { set_err(c, "smr_pairwise_part: null index, or a slot outside 0..63"); return SMR_ERR_ARG; }
+  if (zip) *plain_bytes = 0;
+  if (!ix || slot < 0 || slot >= 64) { set_err(c, W + "null index, or a slot outside 0..63"); return SMR_ERR_ARG; }
   PartCall pc = {c->idx[slot], *c->b};
   int rc = part_call_open(c, who, p, ix, pc); if (rc) return rc;
   const Batch& B = pc.B;
@@ -43,9 +49,12 @@ extern "C" int smr_pairwise_part(smr_ctx* c, int slot, const smr_params* p, cons
   HIPCHK(c, hipMemcpyAsync(&total, S.part_b + np, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   T.set(1, 2, 3);
-  *need = total;
-  if (!bytes) return SMR_OK;
-  if (cap < total) { set_err(c, "smr_pairwise_part: the text takes " + std::to_string(total) + " bytes, the buffer has " + std::to_string(cap)); return SMR_ERR_CAPACITY; }
+  if (zip) *plain_bytes = total;                      // (*need stays 0 until gz_run knows the size of the members)
+  else {
+    *need = total;
+    if (!bytes) return SMR_OK;
+    if (cap < total) { set_err(c, W + "the text takes " + std::to_string(total) + " bytes, the buffer has " + std::to_string(cap)); return SMR_ERR_CAPACITY; }
+  }
   if (total == 0) return SMR_OK;
   if ((rc = S.out.reserve_headroom(c, (size_t)total, 8))) return rc;
   const uint32_t chunks = (n + 63u) / 64u, blocks = std::max(1u, std::min<uint32_t>((chunks + 3u) / 4u, (uint32_t)c->n_cu * 8u));
@@ -54,12 +63,31 @@ extern "C" int smr_pairwise_part(smr_ctx* c, int slot, const smr_params* p, cons
          pc.src, ref, D, (const uint4*)S.meta, (const unsigned long long*)S.excl_b, (const unsigned long long*)S.part_b, S.out);
   HIPCHK(c, hipGetLastError());
   if ((rc = T.mark(c, 5, c->stream))) return rc;
+  if (zip) {                                           // (the time of a copy that is not made stays 0)
+    const uint64_t off[2] = {0, total};
+    uint64_t gz_off[2];
+    if ((rc = gz_run(c, who, S.out, off, 1, bytes, cap, gz_off, need, true)) && rc != SMR_ERR_CAPACITY) return rc;
+    T.set(2, 4, 5);
+    return rc;
+  }
   HIPCHK(c, hipMemcpyAsync(bytes, S.out, (size_t)total, hipMemcpyDeviceToHost, c->stream));
   if ((rc = T.mark(c, 6, c->stream))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   T.set(2, 4, 5);
   T.set(3, 5, 6);
   return SMR_OK;
+}
+}  // namespace
+
+extern "C" int smr_pairwise_part(smr_ctx* c, int slot, const smr_params* p, const smr_index* ix, double lambda, double K, uint64_t full_ref_corr,
+                                 uint64_t full_read_corr, uint8_t* bytes, uint64_t cap, uint64_t* need) {
+  if (!c || !need) return SMR_ERR_ARG;
+  return pair_impl(c, "smr_pairwise_part", slot, p, ix, lambda, K, full_ref_corr, full_read_corr, bytes, cap, nullptr, need);
+}
+extern "C" int smr_pairwise_part_gz(smr_ctx* c, int slot, const smr_params* p, const smr_index* ix, double lambda, double K, uint64_t full_ref_corr,
+                                    uint64_t full_read_corr, uint8_t* gz, uint64_t cap, uint64_t* plain_bytes, uint64_t* need) {
+  if (!c || !plain_bytes || !need) return SMR_ERR_ARG;
+  return pair_impl(c, "smr_pairwise_part_gz", slot, p, ix, lambda, K, full_ref_corr, full_read_corr, gz, cap, plain_bytes, need);
 }
 
 extern "C" int smr_pairwise_times(const smr_ctx* c, double ms[4]) {

@@ -2,7 +2,8 @@
 // BLAST tabular report of one (index, part) over the selected batch, counted, sized and written on the device -- what smr_results_fetch +
 // smr_reads_record_text + smr_result_record + smr_report_add do on the host one read at a time.  The host's share: the names of the part's
 // references (uploaded once per slot), the e-value / bit-score texts per score (smr::score_texts, the report writer's own), three small
-// copies back (the error counts, the two totals) and the bytes.  Also here, for smr_pairwise_part and smr_otu_part behind it: the preamble of a
+// copies back (the error counts, the two totals) and the bytes -- or, for smr_rows_part_gz, the gzip members that gz_run (smr_engine_gzip.hpp)
+// makes of the rows where they lie.  Also here, for smr_pairwise_part and smr_otu_part behind it: the preamble of a
 // call on one (index, part) (PartCall, part_call_open, part_call_views) and the guard loop of k_rows_stat (rows_guard).
 
 namespace {
@@ -128,17 +129,22 @@ int rows_guard(smr_ctx* c, const char* who, StageClock<7, 4>& clk, const PartCal
 }
 }  // namespace
 
-extern "C" int smr_rows_part(smr_ctx* c, int slot, const smr_params* p, const smr_index* ix, const smr_rows_opts* o,
-                             uint8_t* bytes, uint64_t cap, uint64_t off[3], uint64_t* need) {
-  static const char* const who = "smr_rows_part";
-  if (!c || !off) return SMR_ERR_ARG;
+namespace {
+// The writer behind smr_rows_part (gz_off null: `bytes` takes the two streams, `off` their offsets) and smr_rows_part_gz (gz_off given: the
+// streams stay on the device and go through gz_run with cuts at line ends, `bytes` takes the gzip members, gz_off their offsets, `off` what
+// the plain call returns)
+int rows_impl(smr_ctx* c, const char* who, int slot, const smr_params* p, const smr_index* ix, const smr_rows_opts* o, uint8_t* bytes, uint64_t cap, uint64_t* off,
+              uint64_t* gz_off, uint64_t* need) {
+  const bool zip = gz_off != nullptr;
+  const std::string W = std::string(who) + ": ";
   off[0] = off[1] = off[2] = 0;
+  if (zip) gz_off[0] = gz_off[1] = gz_off[2] = 0;
   if (need) *need = 0;
-  if (!o || !ix || slot < 0 || slot >= 64) { set_err(c, "smr_rows_part: null options or index, or a slot outside 0..63"); return SMR_ERR_ARG; }
-  if (!o->want_sam && !o->want_blast) { set_err(c, "smr_rows_part: neither the SAM nor the BLAST rows are wanted"); return SMR_ERR_ARG; }
+  if (!o || !ix || slot < 0 || slot >= 64) { set_err(c, W + "null options or index, or a slot outside 0..63"); return SMR_ERR_ARG; }
+  if (!o->want_sam && !o->want_blast) { set_err(c, W + "neither the SAM nor the BLAST rows are wanted"); return SMR_ERR_ARG; }
   RowsOpts D;
   memset(&D, 0, sizeof D);
-  if (!rows_parse_cols(o->blast_cols, D)) { set_err(c, "smr_rows_part: blast_cols takes \"cigar\", \"qcov\" and \"qstrand\", space separated"); return SMR_ERR_ARG; }
+  if (!rows_parse_cols(o->blast_cols, D)) { set_err(c, W + "blast_cols takes \"cigar\", \"qcov\" and \"qstrand\", space separated"); return SMR_ERR_ARG; }
   PartCall pc = {c->idx[slot], *c->b};
   int rc = part_call_open(c, who, p, ix, pc); if (rc) return rc;
   const Batch& B = pc.B;
@@ -173,9 +179,13 @@ extern "C" int smr_rows_part(smr_ctx* c, int slot, const smr_params* p, const sm
   const uint64_t total = tot[0] + tot[1];
   off[1] = tot[0]; off[2] = total;
   if (need) *need = total;
-  if (!bytes) return SMR_OK;
-  if (cap < total) { set_err(c, "smr_rows_part: the rows take " + std::to_string(total) + " bytes, the buffer has " + std::to_string(cap)); return SMR_ERR_CAPACITY; }
+  if (zip) *need = 0;                                  // (until gz_run knows the size of the members)
+  else {
+    if (!bytes) return SMR_OK;
+    if (cap < total) { set_err(c, W + "the rows take " + std::to_string(total) + " bytes, the buffer has " + std::to_string(cap)); return SMR_ERR_CAPACITY; }
+  }
   if (total == 0) return SMR_OK;
+  // the rows, staged on the device: copied to the host from there, or compressed from there
   if ((rc = S.out.reserve_headroom(c, (size_t)total, 8))) return rc;
   const uint32_t chunks = (n + 63u) / 64u, blocks = std::max(1u, std::min<uint32_t>((chunks + 3u) / 4u, (uint32_t)c->n_cu * 8u));
   if ((rc = T.mark(c, 4, c->stream))) return rc;
@@ -185,12 +195,29 @@ extern "C" int smr_rows_part(smr_ctx* c, int slot, const smr_params* p, const sm
                      (const uint4*)S.stat, pc.src, ref, D, (const uint4*)S.meta, (const unsigned long long*)S.excl_b, (const unsigned long long*)S.part_b, tot[0], S.out);
   HIPCHK(c, hipGetLastError());
   if ((rc = T.mark(c, 5, c->stream))) return rc;
+  if (zip) {                                           // (the time of a copy that is not made stays 0)
+    if ((rc = gz_run(c, who, S.out, off, 2, bytes, cap, gz_off, need, true)) && rc != SMR_ERR_CAPACITY) return rc;
+    T.set(2, 4, 5);
+    return rc;
+  }
   HIPCHK(c, hipMemcpyAsync(bytes, S.out, (size_t)total, hipMemcpyDeviceToHost, c->stream));
   if ((rc = T.mark(c, 6, c->stream))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   T.set(2, 4, 5);
   T.set(3, 5, 6);
   return SMR_OK;
+}
+}  // namespace
+
+extern "C" int smr_rows_part(smr_ctx* c, int slot, const smr_params* p, const smr_index* ix, const smr_rows_opts* o,
+                             uint8_t* bytes, uint64_t cap, uint64_t off[3], uint64_t* need) {
+  if (!c || !off) return SMR_ERR_ARG;
+  return rows_impl(c, "smr_rows_part", slot, p, ix, o, bytes, cap, off, nullptr, need);
+}
+extern "C" int smr_rows_part_gz(smr_ctx* c, int slot, const smr_params* p, const smr_index* ix, const smr_rows_opts* o,
+                                uint8_t* gz, uint64_t cap, uint64_t gz_off[3], uint64_t plain_off[3], uint64_t* need) {
+  if (!c || !gz_off || !plain_off || !need) return SMR_ERR_ARG;
+  return rows_impl(c, "smr_rows_part_gz", slot, p, ix, o, gz, cap, plain_off, gz_off, need);
 }
 
 extern "C" int smr_rows_times(const smr_ctx* c, double ms[4]) {

@@ -17,6 +17,11 @@
 //   k_gz_encode   one workgroup per chunk.  Per tile of 256 tokens: bit lengths, a scan, the bits OR-ed into an LDS window, the window's whole
 //                 dwords stored coalesced into the chunk's worst-case slot.  A stored member is copied as blocks of at most 65 535 bytes.
 //   k_gz_compact  one workgroup per chunk: the member from its slot to its place behind the members in front of it (k_export_scan of the sizes).
+//
+// Text made of rows can be cut at line ends instead (k_gz_cut_lines): nominal cuts every GZ_LINE_PITCH bytes of a stream, each moved back to
+// behind the last '\n' of the GZ_LINE_WIN bytes in front of it.  A chunk then holds at most GZ_LINE_PITCH + GZ_LINE_WIN - 1 bytes, within
+// GZ_CHUNK, so the four kernels above take such chunks as they are; every member but a stream's last ends with a line, unless a line is longer
+// than the window: that one is cut where the grid falls.
 #pragma once
 
 namespace smr {
@@ -34,6 +39,8 @@ namespace smr {
 #define GZ_PREFIX_WORDS 80u      // 80 bits of gzip header + 3 + 14 + 19 * 3 + 316 * 7 bits of block header at the most
 #define GZ_TOK_EOB 256u
 #define GZ_CRC_WORDS (256u + 8u * 32u)       // the byte table, then the eight operators of 32 columns each
+#define GZ_LINE_PITCH 49152u     // cuts at line ends: the distance of two nominal cuts
+#define GZ_LINE_WIN 16384u       // and how far in front of a nominal cut a line end is looked for; GZ_LINE_PITCH + GZ_LINE_WIN = GZ_CHUNK
 
 struct GzChunk { unsigned long long src; uint32_t len, pad; };      // where the chunk's plain bytes begin in the input buffer
 // what k_gz_codes leaves per chunk
@@ -433,6 +440,48 @@ __global__ void __launch_bounds__(256) k_gz_compact(const GzCode* __restrict__ c
   }
   const uint32_t done = head + 4u * n_dw;
   if (t < size - done) dst[done + t] = src[done + t];
+}
+
+// ---- cuts at line ends -------------------------------------------------------------------------------------------------------------------
+// the place behind the last '\n' of in[b - GZ_LINE_WIN .. b), or b where the window holds none.  The whole workgroup of 256 threads; every
+// thread gets the value.  Whole dwords of the window are loaded as dwords, the up to two dwords it shares with its neighbours byte by byte
+__device__ __forceinline__ unsigned long long gz_cut_at(const uint8_t* __restrict__ in, unsigned long long b, uint32_t* s_wave) {
+  const uint32_t t = threadIdx.x;
+  const uintptr_t lo = (uintptr_t)in + (uintptr_t)(b - GZ_LINE_WIN), hi = (uintptr_t)in + (uintptr_t)b;
+  uint32_t best = 0;                                   // 1 + the line end's place in the window
+  for (uintptr_t w = (lo & ~(uintptr_t)3u) + 4u * t; w < hi; w += 4u * 256u) {
+    uint32_t v = 0;
+    if (w >= lo && w + 4u <= hi) v = *(const uint32_t*)w;
+    else for (uint32_t k = 0; k < 4u; k++) if (w + k >= lo && w + k < hi) v |= (uint32_t)*(const uint8_t*)(w + k) << (8u * k);
+    const uint32_t x = v ^ 0x0A0A0A0Au;                // (a byte outside the window is 0 here: no line end)
+    for (uint32_t k = 4u; k-- > 0u;) if (((x >> (8u * k)) & 0xFFu) == 0u) { best = (uint32_t)(w + k - lo) + 1u; break; }
+  }
+  best = gz_wave_max(best);
+  if ((t & 63u) == 0u) s_wave[t >> 6] = best;
+  __syncthreads();
+  best = max(max(s_wave[0], s_wave[1]), max(s_wave[2], s_wave[3]));
+  __syncthreads();                                     // (s_wave is written again by the next call)
+  return best ? b - GZ_LINE_WIN + best : b;
+}
+
+// One workgroup per chunk of the fixed grid: chunk j of stream k (first[k] <= blockIdx.x < first[k + 1]; a stream of n bytes has
+// ceil(n / GZ_LINE_PITCH) chunks) lies between cut j - 1 and cut j of the stream, cut -1 its begin, the last cut its end, and cut j otherwise
+// gz_cut_at(off[k] + (j + 1) * GZ_LINE_PITCH).  A cut is a function of the text alone, so the workgroup finds both of its own and no cut
+// waits for another.  -> chunks[], and in slot_size[] the bytes of the chunk's worst-case slot (gz_run turns them into offsets)
+__global__ void __launch_bounds__(256) k_gz_cut_lines(const uint8_t* __restrict__ in, const unsigned long long* __restrict__ off, const unsigned long long* __restrict__ first,
+                                                      uint32_t n_streams, GzChunk* __restrict__ chunks, unsigned long long* __restrict__ slot_size) {
+  __shared__ uint32_t s_wave[4];
+  const unsigned long long c = blockIdx.x;
+  uint32_t k = 0, above = n_streams;                   // first[k] <= c < first[above]; streams without bytes share their first[] with the next one
+  while (above - k > 1u) { const uint32_t mid = (k + above) >> 1; if (first[mid] <= c) k = mid; else above = mid; }
+  const unsigned long long j = c - first[k], m = first[k + 1u] - first[k];
+  const unsigned long long begin = j ? gz_cut_at(in, off[k] + j * GZ_LINE_PITCH, s_wave) : off[k];
+  const unsigned long long end = j + 1u < m ? gz_cut_at(in, off[k] + (j + 1u) * GZ_LINE_PITCH, s_wave) : off[k + 1u];
+  if (threadIdx.x == 0u) {
+    GzChunk ck; ck.src = begin; ck.len = (uint32_t)(end - begin); ck.pad = 0u;
+    chunks[c] = ck;
+    slot_size[c] = gz_slot_size(ck.len);
+  }
 }
 
 }  // namespace smr

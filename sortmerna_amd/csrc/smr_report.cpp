@@ -13,6 +13,7 @@
 //   smr_report_add_fastx / _add_rows / _add_pairwise   aligned.* and other.*, the SAM and BLAST tabular rows, the BLAST pairwise text
 //   smr_report_add_otu         the groups of smr_otu_part, appended to the map entries of their (index, part)
 //   smr_report_add_denovo      the four aligned_denovo.* streams of smr_fastx_denovo
+//   smr_report_add_fastx_gz / _add_denovo_gz / _add_rows_gz / _add_pairwise_gz   the same streams as gzip members the device made, written as they are
 // Input per read: the original header line, letters, quality and the Read::toBinString record (read.cpp:429-462) that
 // smr_result_record returns.  Rows are buffered per (index, part) and written in that order, like the reference's loop.
 #include <algorithm>
@@ -73,6 +74,22 @@ struct Aln {
   uint16_t score1 = 0, part = 0, index_num = 0; uint8_t strand = 0;
 };
 struct Db { double lambda = 0, K = 0; uint64_t full_ref = 0, full_read = 0; };
+// The rows of one (index, part) in the order they were added: pieces that are either plain text (deflated by zlib at close) or gzip members
+// made elsewhere (smr_report_add_rows_gz / _add_pairwise_gz; written as they are).  Plain text that follows plain text joins its piece, so
+// rows that never met a gzip member are one piece, written with the one call they always were
+struct Rows {
+  struct Seg { bool raw; std::string bytes; };
+  std::vector<Seg> segs;
+  std::string& plain() { if (segs.empty() || segs.back().raw) segs.push_back(Seg{false, std::string()}); return segs.back().bytes; }
+  void add_raw(const uint8_t* p, uint64_t n) { segs.push_back(Seg{true, std::string(reinterpret_cast<const char*>(p), (size_t)n)}); }
+  bool write(Out& f) const {                           // (put_raw finishes the member zlib holds before the first raw byte)
+    for (const Seg& s : segs) {
+      if (!s.raw) f.put(s.bytes);
+      else if (!f.put_raw(reinterpret_cast<const uint8_t*>(s.bytes.data()), s.bytes.size())) return false;
+    }
+    return true;
+  }
+};
 
 // Read::toBinString layout (read.cpp:429-462, ssw.hpp:106-140)
 // idcov (may be null): Read::c_yid_ycov, n_yid_ncov, n_nid_ycov, n_denovo -- what smr_idcov_part (the reference: denovo_stats) left in the record
@@ -122,7 +139,7 @@ struct smr_report {
   int num_out = 1;                                                     // ReportFxBase::set_num_out (report_fx_base.cpp:163-169)
   std::map<uint32_t, Db> dbs;
   std::map<std::pair<uint32_t, uint32_t>, const smr_index*> parts;
-  std::map<std::pair<uint32_t, uint32_t>, std::string> blast, sam;     // rows per (index, part)
+  std::map<std::pair<uint32_t, uint32_t>, Rows> blast, sam;            // rows per (index, part)
   std::string err, cmdline = "libsmr_hip";
   bool skip_fx = false;                                                // smr_report_skip_fastx: aligned.* / other.* come from smr_report_add_fastx
   bool skip_rows = false;                                              // smr_report_skip_rows: the SAM and BLAST tabular rows come from smr_report_add_rows
@@ -276,8 +293,8 @@ extern "C" int smr_report_add_rows(smr_report* r, uint32_t index_num, uint32_t p
   if ((has_sam || has_blast) && !bytes) { r->err = "smr_report_add_rows: rows without bytes"; return SMR_ERR_ARG; }
   if (has_sam && !r->o.sam) { r->err = "smr_report_add_rows: SAM rows for a report that was not opened with sam"; return SMR_ERR_ARG; }
   if (has_blast && !r->o.blast_tabular) { r->err = "smr_report_add_rows: BLAST rows for a report that was not opened with blast_tabular"; return SMR_ERR_ARG; }
-  if (has_sam) r->sam[key].append(reinterpret_cast<const char*>(bytes) + off[0], (size_t)(off[1] - off[0]));
-  if (has_blast) r->blast[key].append(reinterpret_cast<const char*>(bytes) + off[1], (size_t)(off[2] - off[1]));
+  if (has_sam) r->sam[key].plain().append(reinterpret_cast<const char*>(bytes) + off[0], (size_t)(off[1] - off[0]));
+  if (has_blast) r->blast[key].plain().append(reinterpret_cast<const char*>(bytes) + off[1], (size_t)(off[2] - off[1]));
   return SMR_OK;
 }
 extern "C" int smr_report_skip_rows(smr_report* r, int on) {
@@ -293,7 +310,7 @@ extern "C" int smr_report_add_pairwise(smr_report* r, uint32_t index_num, uint32
   if (r->o.blast_tabular) { r->err = "smr_report_add_pairwise: the report was opened with blast_tabular as well, and then holds no pairwise text"; return SMR_ERR_ARG; }
   const std::pair<uint32_t, uint32_t> key{index_num, part};
   if (r->parts.find(key) == r->parts.end()) { r->err = "smr_report_add_pairwise: the (index, part) was not registered"; return SMR_ERR_ARG; }
-  r->blast[key].append(reinterpret_cast<const char*>(bytes), (size_t)n);
+  r->blast[key].plain().append(reinterpret_cast<const char*>(bytes), (size_t)n);
   return SMR_OK;
 }
 extern "C" int smr_report_skip_pairwise(smr_report* r, int on) {
@@ -386,6 +403,33 @@ extern "C" int smr_report_add_fastx_gz(smr_report* r, const uint8_t* gz, const u
 }
 extern "C" int smr_report_add_denovo_gz(smr_report* r, const uint8_t* gz, const uint64_t gz_off[5]) {
   return add_gz(r, "smr_report_add_denovo_gz", gz, gz_off, 4, [r](int k) -> Out& { return r->f_denovo[k]; });
+}
+// SAM / BLAST rows as gzip members: kept per (index, part) like the plain rows, and written at close in the order of the calls
+extern "C" int smr_report_add_rows_gz(smr_report* r, uint32_t index_num, uint32_t part, const uint8_t* gz, const uint64_t gz_off[3]) {
+  if (!r || !gz_off) return SMR_ERR_ARG;
+  if (!r->o.zip_out) { r->err = "smr_report_add_rows_gz: the report was not opened with zip_out"; return SMR_ERR_ARG; }
+  if (gz_off[1] < gz_off[0] || gz_off[2] < gz_off[1]) { r->err = "smr_report_add_rows_gz: the offsets decrease"; return SMR_ERR_ARG; }
+  const std::pair<uint32_t, uint32_t> key{index_num, part};
+  if (r->parts.find(key) == r->parts.end()) { r->err = "smr_report_add_rows_gz: the (index, part) was not registered"; return SMR_ERR_ARG; }
+  const bool has_sam = gz_off[1] > gz_off[0], has_blast = gz_off[2] > gz_off[1];
+  if ((has_sam || has_blast) && !gz) { r->err = "smr_report_add_rows_gz: rows without bytes"; return SMR_ERR_ARG; }
+  if (has_sam && !r->o.sam) { r->err = "smr_report_add_rows_gz: SAM rows for a report that was not opened with sam"; return SMR_ERR_ARG; }
+  if (has_blast && !r->o.blast_tabular) { r->err = "smr_report_add_rows_gz: BLAST rows for a report that was not opened with blast_tabular"; return SMR_ERR_ARG; }
+  if (has_sam) r->sam[key].add_raw(gz + gz_off[0], gz_off[1] - gz_off[0]);
+  if (has_blast) r->blast[key].add_raw(gz + gz_off[1], gz_off[2] - gz_off[1]);
+  return SMR_OK;
+}
+extern "C" int smr_report_add_pairwise_gz(smr_report* r, uint32_t index_num, uint32_t part, const uint8_t* gz, uint64_t n) {
+  if (!r) return SMR_ERR_ARG;
+  if (!r->o.zip_out) { r->err = "smr_report_add_pairwise_gz: the report was not opened with zip_out"; return SMR_ERR_ARG; }
+  if (n == 0) return SMR_OK;
+  if (!gz) { r->err = "smr_report_add_pairwise_gz: text without bytes"; return SMR_ERR_ARG; }
+  if (!r->o.blast_pairwise) { r->err = "smr_report_add_pairwise_gz: pairwise text for a report that was not opened with blast_pairwise"; return SMR_ERR_ARG; }
+  if (r->o.blast_tabular) { r->err = "smr_report_add_pairwise_gz: the report was opened with blast_tabular as well, and then holds no pairwise text"; return SMR_ERR_ARG; }
+  const std::pair<uint32_t, uint32_t> key{index_num, part};
+  if (r->parts.find(key) == r->parts.end()) { r->err = "smr_report_add_pairwise_gz: the (index, part) was not registered"; return SMR_ERR_ARG; }
+  r->blast[key].add_raw(gz, n);
+  return SMR_OK;
 }
 extern "C" int smr_report_skip_denovo(smr_report* r, int on) {
   if (!r) return SMR_ERR_ARG;
@@ -512,7 +556,7 @@ int add_rows(smr_report* r, const char* header, const char* seq, const char* qua
         ss << std::setw(20) << " " << ml;
         ss << "\nQuery: " << std::setw(9) << p0 + 1 << "    " << ql << "    " << p << "\n\n";
       }
-      r->blast[key] += ss.str();
+      r->blast[key].plain() += ss.str();
     }
     if (do_tab) {
       const Db& d = dit->second;
@@ -532,7 +576,7 @@ int add_rows(smr_report* r, const char* header, const char* seq, const char* qua
         p = e ? e + 1 : p + col.size();
       }
       ss << "\n";
-      r->blast[key] += ss.str();
+      r->blast[key].plain() += ss.str();
     }
     if (do_sam) {
       std::ostringstream ss;
@@ -546,7 +590,7 @@ int add_rows(smr_report* r, const char* header, const char* seq, const char* qua
         ss << qit->second;
       } else ss << "*";
       ss << "\tAS:i:" << a.score1 << "\tNM:i:" << n_miss + n_gap << "\n";
-      r->sam[key] += ss.str();
+      r->sam[key].plain() += ss.str();
     }
   }
   return SMR_OK;
@@ -579,7 +623,7 @@ extern "C" int smr_report_close(smr_report* r) {
   }
   if (r->o.blast_tabular || r->o.blast_pairwise) {
     Out f;
-    if (!f.open(r->dir + "/aligned.blast", r->o.zip_out != 0)) rc = SMR_ERR_IO; else { for (auto& kv : r->blast) f.put(kv.second); f.close(); }
+    if (!f.open(r->dir + "/aligned.blast", r->o.zip_out != 0)) rc = SMR_ERR_IO; else { for (auto& kv : r->blast) if (!kv.second.write(f)) rc = SMR_ERR_IO; f.close(); }
   }
   if (r->o.sam) {
     Out f;
@@ -595,7 +639,7 @@ extern "C" int smr_report_close(smr_report* r) {
         }
       }
       f.put("@PG\tID:sortmerna\tVN:1.0\tCL:" + r->cmdline + "\n");
-      for (auto& kv : r->sam) f.put(kv.second);
+      for (auto& kv : r->sam) if (!kv.second.write(f)) rc = SMR_ERR_IO;
       f.close();
     }
   }

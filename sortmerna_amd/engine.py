@@ -629,6 +629,55 @@ class Engine:
         o = self._denovo_opts(opts, kw)
         return self._fx_gz("smr_fastx_denovo_gz", 4, o, dn, mates)
 
+    def gzip_lines_bound(self, plain_bytes, n_streams):
+        """smr_gzip_lines_bound: no output of gzip_lines_batch / rows_part_gz / pairwise_part_gz for plain_bytes in n_streams streams is larger"""
+        return int(self.L.smr_gzip_lines_bound(int(plain_bytes), int(n_streams)))
+
+    def gzip_lines_batch(self, streams):
+        """smr_gzip_lines_batch: gzip_batch with the members cut at line ends -- nominal cuts every 48 KiB, each moved back to behind the last
+        newline of the 16 KiB in front of it -> a list of bytes objects, the members of each stream back to back (b"" for an empty one)"""
+        n = len(streams)
+        off = (C.c_uint64 * (n + 1))()
+        for k in range(n):
+            off[k + 1] = off[k] + len(streams[k])
+        plain = np.frombuffer(b"".join(streams) or b"\0", dtype=np.uint8)
+        gz_off = (C.c_uint64 * (n + 1))()
+        need = C.c_uint64(0)
+        cap = self.gzip_lines_bound(off[n], n)
+        buf = np.zeros(max(cap, 1), dtype=np.uint8)
+        self._chk(self.L.smr_gzip_lines_batch(self.h, plain.ctypes.data, off, n, buf.ctypes.data, cap, gz_off, C.byref(need)), "smr_gzip_lines_batch")
+        raw = buf[:need.value].tobytes()
+        return [raw[gz_off[k]:gz_off[k + 1]] for k in range(n)]
+
+    def rows_part_gz(self, slot, params, index, sam=True, blast=False, cols="", lam=0.0, K=0.0, full_ref=0, full_read=0):
+        """smr_rows_part_gz: the two streams of rows_part, compressed on the device into gzip members that end at line ends ->
+        (sam_gz, blast_gz, plain_off): the members of each stream (b"" for one that is not wanted or holds no row) and the three offsets
+        rows_part's streams would have.  Arguments as rows_part."""
+        o = capi.RowsOpts()
+        o.want_sam, o.want_blast = int(bool(sam)), int(bool(blast))
+        o.blast_cols = (cols if isinstance(cols, str) else " ".join(cols)).encode()
+        o.lam, o.K, o.full_ref_corr, o.full_read_corr = float(lam), float(K), int(full_ref), int(full_read)
+        gz_off, plain_off = (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        need = C.c_uint64(0)
+        args = (self.h, slot, C.byref(params), index.h, C.byref(o))
+        self._chk(self.L.smr_rows_part_gz(*args, None, 0, gz_off, plain_off, C.byref(need)), "smr_rows_part_gz")
+        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
+        if need.value:
+            self._chk(self.L.smr_rows_part_gz(*args, buf.ctypes.data, need.value, gz_off, plain_off, C.byref(need)), "smr_rows_part_gz")
+        raw = buf.tobytes()
+        return raw[gz_off[0]:gz_off[1]], raw[gz_off[1]:gz_off[2]], [int(x) for x in plain_off]
+
+    def pairwise_part_gz(self, slot, params, index, lam=0.0, K=0.0, full_ref=0, full_read=0):
+        """smr_pairwise_part_gz: the text of pairwise_part, compressed on the device into gzip members that end at line ends ->
+        (gz, plain_bytes): the members and the size pairwise_part's text would have.  Arguments as pairwise_part."""
+        need, plain = C.c_uint64(0), C.c_uint64(0)
+        args = (self.h, slot, C.byref(params), index.h, float(lam), float(K), int(full_ref), int(full_read))
+        self._chk(self.L.smr_pairwise_part_gz(*args, None, 0, C.byref(plain), C.byref(need)), "smr_pairwise_part_gz")
+        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
+        if need.value:
+            self._chk(self.L.smr_pairwise_part_gz(*args, buf.ctypes.data, need.value, C.byref(plain), C.byref(need)), "smr_pairwise_part_gz")
+        return buf[:need.value].tobytes(), int(plain.value)
+
     def rows_fmt_batch(self, num, den):
         """smr_rows_fmt_batch (a test seam): the device's `%.3g` of 100 * num[i] / den[i] -> list of str"""
         num = np.ascontiguousarray(num, dtype=np.uint32)

@@ -130,6 +130,18 @@ class Report:
         """the four streams of Engine.fastx_denovo_gz appended as they are to the open aligned_denovo.* .gz files (smr_report_add_denovo_gz)"""
         self._add_gz("smr_report_add_denovo_gz", streams, 4)
 
+    def add_rows_gz(self, index_num, part, sam_gz, blast_gz):
+        """the two streams of Engine.rows_part_gz -- gzip members -- kept with the report's SAM / BLAST rows of (index_num, part) and written as
+        they are at close (smr_report_add_rows_gz); the report must have been opened with zip_out"""
+        off = (C.c_uint64 * 3)(0, len(sam_gz), len(sam_gz) + len(blast_gz))
+        blob = bytes(sam_gz) + bytes(blast_gz)
+        self._chk(self.L.smr_report_add_rows_gz(self.h, index_num, part, blob if blob else None, off), "smr_report_add_rows_gz")
+
+    def add_pairwise_gz(self, index_num, part, gz):
+        """the members of Engine.pairwise_part_gz kept with the report's BLAST pairwise text of (index_num, part) (smr_report_add_pairwise_gz)"""
+        gz = bytes(gz)
+        self._chk(self.L.smr_report_add_pairwise_gz(self.h, index_num, part, gz if gz else None, len(gz)), "smr_report_add_pairwise_gz")
+
     def skip_denovo(self, on=True):
         """add / add_pair leave aligned_denovo.* alone: add_denovo writes them (smr_report_skip_denovo)"""
         self._chk(self.L.smr_report_skip_denovo(self.h, int(bool(on))), "smr_report_skip_denovo")
