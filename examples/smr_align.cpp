@@ -12,12 +12,16 @@
 // smr_report_add / smr_report_add_pair.  Every output file is the same.
 // --rows device (needs --pack device): the rows of aligned.sam and of the BLAST tabular report come from one smr_rows_part call per (index, part)
 // (smr_report_add_rows) instead of read by read; the default, --rows host, is smr_report_add.  Single reads and interleaved mates; refused with
-// --blast 0 (unless --pairwise device takes it) and with two reads files, whose rows stay with the host writer.  Every output file is the same.
+// --blast 0 (unless --pairwise device takes it) and with two reads files, whose rows stay with the host writer unless --mates device is given.  Every output file is the same.
 // --pairwise device (needs --pack device and --blast 0): the BLAST pairwise text comes from one smr_pairwise_part call per (index, part)
 // (smr_report_add_pairwise) instead of read by read; the default, --pairwise host, is smr_report_add.  Single reads and interleaved mates;
-// refused with two reads files.  With --rows device and --split device the per-read loop feeds the report nothing.  Every output file is the same.
+// refused with two reads files unless --mates device is given.  With --rows device and --split device the per-read loop feeds the report nothing.  Every output file is the same.
 // -otu_map -de_novo_otu -id X -coverage X: the %id / %coverage pass (smr_idcov_part, the reference's denovo_stats) per (index, part) after all
 // alignment, otu_map.txt and aligned_denovo.fa|fq, the two Results lines of aligned.log; defaults and refusals are the reference's.
+// --mates device (needs two reads files and --rows device or --pairwise device): the rows and the pairwise text of mates in two files come from
+// smr_rows_part_mates / smr_pairwise_part_mates (and, under --ziprows device, their _gz forms) with batch 0 selected and mates = 1, in the visit
+// per (index, part) where the plain calls are made: the two batches' streams are interleaved on the device into the order of
+// smr_report_add_pair.  The default, --mates host, keeps the refusals above.  Every output file is the same.
 // --otu device (needs --pack device): the members of otu_map.txt come from one smr_otu_part call per (index, part) (smr_report_add_otu) and
 // aligned_denovo.* from one smr_fastx_denovo call (smr_report_add_denovo) instead of read by read; the default, --otu host, is smr_report_add.
 // Single reads and interleaved mates; refused with two reads files.  Every output file is the same.
@@ -54,7 +58,7 @@ int main(int argc, char** argv) {
   smr_params base; smr_params_default(&base);
   double evalue = 1.0;
   int device = 0;
-  bool pack_device = false, split_device = false, rows_device = false, pair_device = false, otu_device = false, zip_device = false, unzip_device = false, ziprows_device = false;
+  bool pack_device = false, split_device = false, rows_device = false, pair_device = false, otu_device = false, zip_device = false, unzip_device = false, ziprows_device = false, mates_device = false;
   bool id_given = false, cov_given = false;
   smr_report_opts ro; memset(&ro, 0, sizeof ro);
   for (int i = 1; i < argc; i++) {
@@ -86,6 +90,7 @@ int main(int argc, char** argv) {
     else if (a == "-unzip" || a == "--unzip") { const std::string v = val(); if (v != "host" && v != "device") die("--unzip: host or device"); unzip_device = v == "device"; }
     else if (a == "-zip" || a == "--zip") { const std::string v = val(); if (v != "host" && v != "device") die("--zip: host or device"); zip_device = v == "device"; }
     else if (a == "-ziprows" || a == "--ziprows") { const std::string v = val(); if (v != "host" && v != "device") die("--ziprows: host or device"); ziprows_device = v == "device"; }
+    else if (a == "-mates" || a == "--mates") { const std::string v = val(); if (v != "host" && v != "device") die("--mates: host or device"); mates_device = v == "device"; }
     else if (a == "-otu" || a == "--otu") { const std::string v = val(); if (v != "host" && v != "device") die("--otu: host or device"); otu_device = v == "device"; }
     else if (a == "-otu_map" || a == "--otu_map") ro.otu_map = 1;
     else if (a == "-de_novo_otu" || a == "--de_novo_otu") ro.denovo = 1;
@@ -113,18 +118,20 @@ int main(int argc, char** argv) {
       printf("usage: smr_align --ref DB.fasta --gumbel LAMBDA K [--idx PREFIX] [--ref ...] --reads READS.fa|fq[.gz] [--reads MATES] [--out DIR]\n"
              "       [-e EVALUE] [-num_alignments N] [-no-best] [-min_lis N] [-num_seeds N] [-edges N] [-full_search] [-F|-R]\n"
              "       [-match N -mismatch N -gap_open N -gap_ext N] [-device K] [--fastx] [--other] [--blast '0' | '1 cigar qcov qstrand'] [--sam [-SQ]]\n"
-             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [--zip host|device] [--ziprows host|device] [--unzip host|device] [--rows host|device] [--pairwise host|device] [-otu_map [-id X] [-coverage X]] [-de_novo_otu] [--otu host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
+             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [--zip host|device] [--ziprows host|device] [--unzip host|device] [--rows host|device] [--pairwise host|device] [--mates host|device] [-otu_map [-id X] [-coverage X]] [-de_novo_otu] [--otu host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
       return 0;
     } else die("unknown option " + a);
   }
+  if (mates_device && reads_paths.size() < 2) die("--mates device interleaves the rows of mates in two reads files on the device: it needs two --reads files");
+  if (mates_device && !rows_device && !pair_device) die("--mates device interleaves what --rows device and --pairwise device write for two reads files: it needs one of the two");
   if (split_device && !pack_device) die("--split device writes aligned.* / other.* from the text the device parsed: it needs --pack device");
   if (unzip_device && !pack_device) die("--unzip device inflates a gzip reads file into the text buffer the device parses: it needs --pack device");
   if (rows_device && !pack_device) die("--rows device writes the SAM / BLAST rows from the text the device parsed: it needs --pack device");
   if (pair_device && !pack_device) die("--pairwise device writes the BLAST pairwise text from the text the device parsed: it needs --pack device");
   if (pair_device && !ro.blast_pairwise) die("--pairwise device writes the pairwise text of --blast 0: without --blast 0 there is none");
-  if (pair_device && reads_paths.size() == 2) die("--pairwise device takes one reads file (single reads or interleaved mates): the blocks of mates in two files alternate between the batches and stay with --pairwise host");
+  if (pair_device && reads_paths.size() == 2 && !mates_device) die("--pairwise device takes one reads file (single reads or interleaved mates): the blocks of mates in two files alternate between the batches and stay with --pairwise host");
   if (rows_device && ro.blast_pairwise && !pair_device) die("--rows device writes BLAST tabular rows only: --blast 0 (pairwise) stays with --rows host");
-  if (rows_device && reads_paths.size() == 2) die("--rows device takes one reads file (single reads or interleaved mates): the rows of mates in two files alternate between the batches and stay with --rows host");
+  if (rows_device && reads_paths.size() == 2 && !mates_device) die("--rows device takes one reads file (single reads or interleaved mates): the rows of mates in two files alternate between the batches and stay with --rows host");
   // the reference's rules for the four options (options.cpp:1623-1628, 1667-1674, 1744-1757)
   if ((id_given || cov_given) && !ro.otu_map) die("options '-id' and '-coverage' can only be used together with '-otu_map': they are the thresholds of the OTU map");
   if (ro.otu_map && !base.is_best) die("option '-otu_map' cannot be used with '-no-best': the OTU map is built from the best alignments");
@@ -288,6 +295,21 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> rb;
     std::vector<smr_otu_group> gb;
     if (smr_batch_select(gpu, 0) != SMR_OK) die(smr_last_error(gpu));
+    // --mates device: the same calls in their form for mates in two files (batch 0 selected, the mates in batch 1)
+    auto rows_part = [&](const smr_params* p, const smr_index* ix, const smr_rows_opts* o, uint8_t* b, uint64_t cap, uint64_t* off, uint64_t* need) {
+      return mates_device ? smr_rows_part_mates(gpu, 1, 0, p, ix, o, b, cap, off, need) : smr_rows_part(gpu, 0, p, ix, o, b, cap, off, need);
+    };
+    auto rows_part_gz = [&](const smr_params* p, const smr_index* ix, const smr_rows_opts* o, uint8_t* b, uint64_t cap, uint64_t* gz_off, uint64_t* off, uint64_t* need) {
+      return mates_device ? smr_rows_part_mates_gz(gpu, 1, 0, p, ix, o, b, cap, gz_off, off, need) : smr_rows_part_gz(gpu, 0, p, ix, o, b, cap, gz_off, off, need);
+    };
+    auto pairwise_part = [&](const smr_params* p, const smr_index* ix, const smr_rows_opts& o, uint8_t* b, uint64_t cap, uint64_t* need) {
+      return mates_device ? smr_pairwise_part_mates(gpu, 1, 0, p, ix, o.lambda, o.K, o.full_ref_corr, o.full_read_corr, b, cap, need)
+                          : smr_pairwise_part(gpu, 0, p, ix, o.lambda, o.K, o.full_ref_corr, o.full_read_corr, b, cap, need);
+    };
+    auto pairwise_part_gz = [&](const smr_params* p, const smr_index* ix, const smr_rows_opts& o, uint8_t* b, uint64_t cap, uint64_t* plain, uint64_t* need) {
+      return mates_device ? smr_pairwise_part_mates_gz(gpu, 1, 0, p, ix, o.lambda, o.K, o.full_ref_corr, o.full_read_corr, b, cap, plain, need)
+                          : smr_pairwise_part_gz(gpu, 0, p, ix, o.lambda, o.K, o.full_ref_corr, o.full_read_corr, b, cap, plain, need);
+    };
     for (size_t k = 0; k < dbs.size(); k++) {
       smr_index_info info; smr_index_get_info(dbs[k].parts[0], &info);
       smr_params p = base;
@@ -305,28 +327,28 @@ int main(int argc, char** argv) {
         // sizes-only _gz call would run the matching, most of a compression, twice
         if (rows_dev && ziprows_device) {
           uint64_t gz_off[3];
-          if (smr_rows_part(gpu, 0, &p, dbs[k].parts[part], &wo, nullptr, 0, off, &need) != SMR_OK) die(smr_last_error(gpu));
+          if (rows_part(&p, dbs[k].parts[part], &wo, nullptr, 0, off, &need) != SMR_OK) die(smr_last_error(gpu));
           const uint64_t bound = smr_gzip_lines_bound(need, 2);
           if (rb.size() < bound + 1) rb.resize((size_t)bound + 1);
-          if (smr_rows_part_gz(gpu, 0, &p, dbs[k].parts[part], &wo, rb.data(), bound, gz_off, off, &need) != SMR_OK) die(smr_last_error(gpu));
+          if (rows_part_gz(&p, dbs[k].parts[part], &wo, rb.data(), bound, gz_off, off, &need) != SMR_OK) die(smr_last_error(gpu));
           if (smr_report_add_rows_gz(rep, (uint32_t)k, (uint32_t)part, rb.data(), gz_off) != SMR_OK) die(smr_report_last_error(rep));
         } else if (rows_dev) {
-          if (smr_rows_part(gpu, 0, &p, dbs[k].parts[part], &wo, nullptr, 0, off, &need) != SMR_OK) die(smr_last_error(gpu));
+          if (rows_part(&p, dbs[k].parts[part], &wo, nullptr, 0, off, &need) != SMR_OK) die(smr_last_error(gpu));
           if (rb.size() < need + 1) rb.resize((size_t)need + 1);
-          if (need && smr_rows_part(gpu, 0, &p, dbs[k].parts[part], &wo, rb.data(), need, off, &need) != SMR_OK) die(smr_last_error(gpu));
+          if (need && rows_part(&p, dbs[k].parts[part], &wo, rb.data(), need, off, &need) != SMR_OK) die(smr_last_error(gpu));
           if (smr_report_add_rows(rep, (uint32_t)k, (uint32_t)part, rb.data(), off) != SMR_OK) die(smr_report_last_error(rep));
         }
         if (pair_dev && ziprows_device) {
           uint64_t plain = 0;
-          if (smr_pairwise_part(gpu, 0, &p, dbs[k].parts[part], wo.lambda, wo.K, wo.full_ref_corr, wo.full_read_corr, nullptr, 0, &need) != SMR_OK) die(smr_last_error(gpu));
+          if (pairwise_part(&p, dbs[k].parts[part], wo, nullptr, 0, &need) != SMR_OK) die(smr_last_error(gpu));
           const uint64_t bound = smr_gzip_lines_bound(need, 1);
           if (rb.size() < bound + 1) rb.resize((size_t)bound + 1);
-          if (smr_pairwise_part_gz(gpu, 0, &p, dbs[k].parts[part], wo.lambda, wo.K, wo.full_ref_corr, wo.full_read_corr, rb.data(), bound, &plain, &need) != SMR_OK) die(smr_last_error(gpu));
+          if (pairwise_part_gz(&p, dbs[k].parts[part], wo, rb.data(), bound, &plain, &need) != SMR_OK) die(smr_last_error(gpu));
           if (smr_report_add_pairwise_gz(rep, (uint32_t)k, (uint32_t)part, rb.data(), need) != SMR_OK) die(smr_report_last_error(rep));
         } else if (pair_dev) {
-          if (smr_pairwise_part(gpu, 0, &p, dbs[k].parts[part], wo.lambda, wo.K, wo.full_ref_corr, wo.full_read_corr, nullptr, 0, &need) != SMR_OK) die(smr_last_error(gpu));
+          if (pairwise_part(&p, dbs[k].parts[part], wo, nullptr, 0, &need) != SMR_OK) die(smr_last_error(gpu));
           if (rb.size() < need + 1) rb.resize((size_t)need + 1);
-          if (need && smr_pairwise_part(gpu, 0, &p, dbs[k].parts[part], wo.lambda, wo.K, wo.full_ref_corr, wo.full_read_corr, rb.data(), need, &need) != SMR_OK) die(smr_last_error(gpu));
+          if (need && pairwise_part(&p, dbs[k].parts[part], wo, rb.data(), need, &need) != SMR_OK) die(smr_last_error(gpu));
           if (smr_report_add_pairwise(rep, (uint32_t)k, (uint32_t)part, rb.data(), need) != SMR_OK) die(smr_report_last_error(rep));
         }
         if (map_dev) {

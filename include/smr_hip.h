@@ -459,6 +459,48 @@ int smr_pairwise_part_gz(smr_ctx*, int slot, const smr_params*, const smr_index*
  * building, bit packing, scan + compaction, bytes D2H} (the last three 0 for a sizes-only call) */
 int smr_gzip_times(const smr_ctx*, double ms[5]);
 
+/* ---- the reports of mates in two reads files, written on the device (csrc/smr_mates.hpp, csrc/smr_engine_mates.hpp) ----
+ * smr_rows_part, smr_pairwise_part and their _gz forms for a paired run whose mates were read from two files: read i of the SELECTED batch is
+ * mate 1 of pair i, read i of batch `mates` its mate 2 (the layout 2 of smr_fastx_split).  Each stream holds exactly what the host writer
+ * appends for that (index, part) when it is fed smr_report_add_pair(pair 0), (pair 1), ...: the rows of mate 1 of pair 0, of mate 2 of pair 0,
+ * of mate 1 of pair 1, and so on -- no OTU or FASTX output, which have their own calls.  The guard, size and write kernels are the plain
+ * calls', run over the selected batch and then over batch `mates`; a further kernel (k_mates_zip) interleaves the two staged outputs on the
+ * device: with a[i] / b[i] the byte offsets of read i in the two batches' streams, the rows of mate 1 of pair i go to a[i] + b[i] and those
+ * of mate 2 to a[i + 1] + b[i].  smr_report_add_rows, smr_report_add_pairwise and their _gz forms take the bytes as they are.
+ * The contract is the sibling's, argument for argument: bytes == NULL: sizes only (the guard and size stages of the two batches and nothing
+ * else); cap < *need: SMR_ERR_CAPACITY with the offsets and *need valid and nothing written; otherwise exactly *need bytes and nothing behind
+ * them.  `bytes` may be pinned.  No stored state changes, the selected batch stays selected on every path, and a repeated call gives the same
+ * bytes.  The _gz forms return what smr_rows_part_gz / smr_pairwise_part_gz return, made of the interleaved text (the members smr_gzip_lines_batch
+ * makes of the plain _mates bytes).
+ * Refusals, in their precedence (every message names the _mates call made; afterwards the context is usable and nothing is written):
+ *   1. SMR_ERR_ARG: a NULL argument, a slot outside 0..63, `mates` outside 0..15 or the selected batch itself;
+ *   2. every refusal of the plain call for the selected batch, its device-side guards included;
+ *   3. SMR_ERR_STATE: batch `mates` holds no reads or not their text (SMR_FASTX_KEEP); the message names the batch;
+ *   4. SMR_ERR_ARG: the two batches differ in their number of reads, or one is FASTA and the other FASTQ (the words of smr_fastx_split);
+ *   5. the plain call's device-side guards for batch `mates` (a CIGAR missing, without columns, or past its read or reference; ref_num; a score
+ *      beyond the table); the message names the batch.
+ * Two empty batches: SMR_OK with zeros.
+ * Device memory, kept and grown only: the plain call's, the same once more for the mates' batch, and the interleaved output (the bytes of both
+ * batches plus an eighth).  The e-value table (sized for the longer max_len of the two batches) and the slot's reference names are shared. */
+int smr_rows_part_mates(smr_ctx*, int mates, int slot, const smr_params*, const smr_index* ix, const smr_rows_opts*,
+                        uint8_t* bytes, uint64_t cap, uint64_t off[3], uint64_t* need);
+int smr_pairwise_part_mates(smr_ctx*, int mates, int slot, const smr_params*, const smr_index* ix, double lambda, double K,
+                            uint64_t full_ref_corr, uint64_t full_read_corr, uint8_t* bytes, uint64_t cap, uint64_t* need);
+int smr_rows_part_mates_gz(smr_ctx*, int mates, int slot, const smr_params*, const smr_index* ix, const smr_rows_opts*,
+                           uint8_t* gz, uint64_t cap, uint64_t gz_off[3], uint64_t plain_off[3], uint64_t* need);
+int smr_pairwise_part_mates_gz(smr_ctx*, int mates, int slot, const smr_params*, const smr_index* ix, double lambda, double K,
+                               uint64_t full_ref_corr, uint64_t full_read_corr, uint8_t* gz, uint64_t cap,
+                               uint64_t* plain_bytes, uint64_t* need);
+/* The interleave kernel at its seam (a test seam and a building block): piece i of A is a[a_off[i], a_off[i + 1]), likewise B; HOST buffers,
+ * n + 1 ascending offsets each.  out takes piece 0 of A, piece 0 of B, piece 1 of A, ...: *need = the bytes of all pieces.  n == 0: SMR_OK;
+ * offsets that decrease: SMR_ERR_ARG; out == NULL: the size only; cap < *need: SMR_ERR_CAPACITY with *need valid and nothing written;
+ * otherwise exactly *need bytes and nothing behind them. */
+int smr_interleave_batch(smr_ctx*, uint32_t n, const uint8_t* a, const uint64_t* a_off, const uint8_t* b, const uint64_t* b_off,
+                         uint8_t* out, uint64_t cap, uint64_t* need);
+/* HIP-event milliseconds of the last *_mates call: {the selected batch's stages, the mates' stages, the interleave, bytes D2H (0 for a
+ * sizes-only call and for the _gz forms)} */
+int smr_mates_times(const smr_ctx*, double ms[4]);
+
 /* ---- gunzip on the device --------------------------------------------------------------------------------------------------------------
  * A DEFLATE decoder in HIP kernels (csrc/smr_gunzip.hpp): a gzip file of any number of members, inflated by many waves at once.  The starts of
  * non-final dynamic-Huffman blocks and of members are found speculatively; tasks at least `grain` compressed bytes apart (1: every candidate;

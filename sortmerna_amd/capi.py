@@ -71,6 +71,7 @@ class Kprof(C.Structure):
 
 
 EXPORTS = [
+    "smr_rows_part_mates", "smr_pairwise_part_mates", "smr_rows_part_mates_gz", "smr_pairwise_part_mates_gz", "smr_interleave_batch", "smr_mates_times",
     "smr_gzip_lines_bound", "smr_gzip_lines_batch", "smr_rows_part_gz", "smr_pairwise_part_gz", "smr_report_add_rows_gz", "smr_report_add_pairwise_gz",
     "smr_gunzip_batch", "smr_gunzip_info", "smr_gunzip_times", "smr_gunzip_tasks",
     "smr_gzip_chunk", "smr_gzip_bound", "smr_gzip_batch", "smr_fastx_split_gz", "smr_fastx_denovo_gz", "smr_gzip_times", "smr_report_add_fastx_gz", "smr_report_add_denovo_gz",
@@ -287,6 +288,18 @@ def bind(L):
     L.smr_gzip_lines_bound.argtypes = [u64, u32]
     L.smr_gzip_lines_batch.restype = i32
     L.smr_gzip_lines_batch.argtypes = [vp, vp, C.POINTER(u64), u32, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.smr_rows_part_mates.restype = i32
+    L.smr_rows_part_mates.argtypes = [vp, i32, i32, C.POINTER(Params), vp, C.POINTER(RowsOpts), vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.smr_pairwise_part_mates.restype = i32
+    L.smr_pairwise_part_mates.argtypes = [vp, i32, i32, C.POINTER(Params), vp, C.c_double, C.c_double, u64, u64, vp, u64, C.POINTER(u64)]
+    L.smr_rows_part_mates_gz.restype = i32
+    L.smr_rows_part_mates_gz.argtypes = [vp, i32, i32, C.POINTER(Params), vp, C.POINTER(RowsOpts), vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.smr_pairwise_part_mates_gz.restype = i32
+    L.smr_pairwise_part_mates_gz.argtypes = [vp, i32, i32, C.POINTER(Params), vp, C.c_double, C.c_double, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.smr_interleave_batch.restype = i32
+    L.smr_interleave_batch.argtypes = [vp, u32, vp, C.POINTER(u64), vp, C.POINTER(u64), vp, u64, C.POINTER(u64)]
+    L.smr_mates_times.restype = i32
+    L.smr_mates_times.argtypes = [vp, C.POINTER(C.c_double)]
     L.smr_rows_part_gz.restype = i32
     L.smr_rows_part_gz.argtypes = [vp, i32, C.POINTER(Params), vp, C.POINTER(RowsOpts), vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.smr_pairwise_part_gz.restype = i32

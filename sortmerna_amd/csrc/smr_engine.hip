@@ -19,6 +19,7 @@
 #include "smr_fxsplit.hpp"
 #include "smr_rows.hpp"
 #include "smr_pairwise.hpp"
+#include "smr_mates.hpp"
 #include "smr_otu.hpp"
 #include "smr_gzip.hpp"
 #include "smr_gunzip.hpp"
@@ -229,6 +230,12 @@ struct smr_ctx {
   FxSplitScratch fxs;
   RowsScratch rows;
   StageClock<7, 4> pair_clk;              // of the last smr_pairwise_part (its device buffers are those of `rows`): guards / statistics, sizes and scans, write, D2H
+  // smr_rows_part_mates / smr_pairwise_part_mates (smr_engine_mates.hpp): the scratch of the mates' batch (stat, meta, excl_*, part_*, err, out; the
+  // e-value table stays that of `rows`), the interleaved streams, the offsets of smr_interleave_batch, and the clocks of the last call
+  RowsScratch rows_m;
+  DevBuf<uint8_t> mates_out; DevBuf<unsigned long long> mates_off;
+  StageClock<7, 4> mates_clk[2];          // the stages of the selected batch / of the mates' batch
+  StageClock<3, 2> mates_zip_clk;         // interleave, D2H
   OtuScratch otu;
   GzScratch gz;
   std::mutex gz_tab_m;                    // the CRC table of `gz` is made at its first use, on either stream
@@ -342,7 +349,8 @@ DIndex dindex(const DevIndex& d) {
   x.n_refs = d.n_refs; x.n_ids = d.n_ids; x.lnwin = d.lnwin; x.partialwin = d.lnwin / 2; x.ref_any_n = d.ref_any_n;
   return x;
 }
-DReads dreads(const smr_ctx* c) { DReads r; r.words = c->b->d_words; r.rec_off = c->b->d_rec_off; r.len = c->b->d_len; r.n = c->b->n; r.max_len = c->b->max_len; return r; }
+DReads dreads(const Batch& b) { DReads r; r.words = b.d_words; r.rec_off = b.d_rec_off; r.len = b.d_len; r.n = b.n; r.max_len = b.max_len; return r; }
+DReads dreads(const smr_ctx* c) { return dreads(*c->b); }
 
 // blocks of k_chain (the one place that says how many): 3 waves per SIMD by registers
 constexpr uint32_t CHAIN_WAVES_PER_CU = 12;
@@ -897,6 +905,7 @@ extern "C" int smr_align_part(smr_ctx* c, int slot, const smr_params* p) {
 #include "smr_engine_fxsplit.hpp"
 #include "smr_engine_rows.hpp"
 #include "smr_engine_pairwise.hpp"
+#include "smr_engine_mates.hpp"
 #include "smr_engine_otu.hpp"
 extern "C" int smr_counters(smr_ctx* c, uint64_t* out, uint32_t n_db) {
   if (!c || !out) return SMR_ERR_ARG;

@@ -78,7 +78,7 @@ struct PartCall {
   RowsSrc src; DReads rd; DIndex dx;
 };
 // the refusals, in the order in which they take precedence, of a call made as {c->idx[slot], *c->b}; the caller has checked its own arguments
-// (slot within 0..63 among them)
+// (slot within 0..63 among them).  The mates' forms (smr_engine_mates.hpp) make it for the selected batch as well: no call here looks at c->b
 int part_call_open(smr_ctx* c, const char* who, const smr_params* p, const smr_index* ix, const PartCall& pc) {
   const std::string W = std::string(who) + ": ";
   if (!pc.di.used || !pc.B.d_saved) { set_err(c, W + "index slot empty or no reads uploaded"); return SMR_ERR_STATE; }
@@ -95,13 +95,13 @@ int part_call_views(smr_ctx* c, const char* who, PartCall& pc) {
   if (pc.ntot >= 0xFFFFFC00ull) { set_err(c, std::string(who) + ": reads x alignment slots of the batch must stay below 2^32"); return SMR_ERR_CAPACITY; }
   pc.pool_words = B.d_cigar ? B.cigar_words : 0ull;
   pc.src.text = B.fx_text; pc.src.n_text = B.fx_n; pc.src.fastq = B.fx_fastq; pc.src.hoff = B.fx_hoff; pc.src.soff = B.fx_soff;
-  pc.rd = dreads(c); pc.dx = dindex(pc.di);
+  pc.rd = dreads(pc.B); pc.dx = dindex(pc.di);
   return SMR_OK;
 }
 // k_rows_stat over the batch (events 0 and 1 of `clk`, time 0): the statistics of every alignment, and the refusal of state the writers would
-// read out of bounds for.  A score above the table of D.n_tab entries makes the table for every 16-bit score under `db`, once
-int rows_guard(smr_ctx* c, const char* who, StageClock<7, 4>& clk, const PartCall& pc, RowsOpts& D, RowsRef& ref, const smr_rows_opts* db) {
-  RowsScratch& S = c->rows;
+// read out of bounds for.  A score above the table of D.n_tab entries makes the table for every 16-bit score under `db`, once.  S: the scratch of
+// the batch (stat, err); the table is that of c->rows whichever batch asks
+int rows_guard(smr_ctx* c, const char* who, StageClock<7, 4>& clk, const PartCall& pc, RowsScratch& S, RowsOpts& D, RowsRef& ref, const smr_rows_opts* db) {
   const Batch& B = pc.B;
   const std::string W = std::string(who) + ": ";
   uint32_t h_err[ROWS_E_COUNT];
@@ -122,7 +122,7 @@ int rows_guard(smr_ctx* c, const char* who, StageClock<7, 4>& clk, const PartCal
     if (attempt || D.n_tab >= 65536u) { set_err(c, W + "a score beyond the e-value table"); return SMR_ERR_ARG; }
     D.n_tab = 65536u;
     if ((rc = rows_table(c, db, D.n_tab, who))) return rc;
-    ref.tab = S.tab;
+    ref.tab = c->rows.tab;
   }
   clk.set(0, 0, 1);
   return SMR_OK;
@@ -130,6 +130,54 @@ int rows_guard(smr_ctx* c, const char* who, StageClock<7, 4>& clk, const PartCal
 }  // namespace
 
 namespace {
+// The stages of smr_rows_part for one batch and its scratch {pc, S} -- the selected batch and c->rows for the plain calls, either batch of a pair
+// for the mates' forms (smr_engine_mates.hpp).  rows_sizes: the guards and the sizes (events 0 .. 3 of T, times 0 and 1); tot[0] / tot[1]: the
+// bytes of the SAM / the BLAST rows.  rows_write: the rows into S.out as [SAM | BLAST] (events 4 and 5 of T)
+int rows_sizes(smr_ctx* c, const char* who, StageClock<7, 4>& T, const PartCall& pc, RowsScratch& S, RowsOpts& D, RowsRef& ref, const smr_rows_opts* o, unsigned long long tot[2]) {
+  const Batch& B = pc.B;
+  const uint32_t n = pc.n, np = (n + ROWS_BLOCK - 1u) / ROWS_BLOCK;
+  int rc;
+  tot[0] = tot[1] = 0;
+  if ((rc = S.stat.reserve(c, pc.ntot)) || (rc = S.meta.reserve(c, n)) || (rc = S.excl_s.reserve(c, n)) || (rc = S.excl_b.reserve(c, n)) ||
+      (rc = S.part_s.reserve(c, (size_t)np + 1)) || (rc = S.part_b.reserve(c, (size_t)np + 1)) || (rc = S.err.reserve(c, ROWS_E_COUNT))) return rc;
+  if ((rc = rows_guard(c, who, T, pc, S, D, ref, o))) return rc;
+  if ((rc = T.mark(c, 2, c->stream))) return rc;
+  launch(c, k_rows_size, dim3(np), dim3(ROWS_BLOCK), 0, pc.rd, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar, pc.pool_words,
+         (const uint4*)S.stat, pc.src, ref, D, S.meta, S.excl_s, S.excl_b, S.part_s, S.part_b);
+  launch(c, k_export_scan, dim3(1), dim3(EXP_SIZE_BLOCK), 0, S.part_s, np + 1u);
+  launch(c, k_export_scan, dim3(1), dim3(EXP_SIZE_BLOCK), 0, S.part_b, np + 1u);
+  HIPCHK(c, hipGetLastError());
+  if ((rc = T.mark(c, 3, c->stream))) return rc;
+  HIPCHK(c, hipMemcpyAsync(&tot[0], S.part_s + np, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&tot[1], S.part_b + np, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  T.set(1, 2, 3);
+  return SMR_OK;
+}
+int rows_write(smr_ctx* c, StageClock<7, 4>& T, const PartCall& pc, RowsScratch& S, const RowsOpts& D, const RowsRef& ref, const unsigned long long tot[2]) {
+  const Batch& B = pc.B;
+  const uint32_t n = pc.n;
+  int rc;
+  // the rows, staged on the device: copied to the host from there, or compressed from there
+  if ((rc = S.out.reserve_headroom(c, (size_t)(tot[0] + tot[1]), 8))) return rc;
+  const uint32_t chunks = (n + 63u) / 64u, blocks = std::max(1u, std::min<uint32_t>((chunks + 3u) / 4u, (uint32_t)c->n_cu * 8u));
+  if ((rc = T.mark(c, 4, c->stream))) return rc;
+  if (tot[0]) launch(c, k_rows_write<0u>, dim3(blocks), dim3(256), 0, pc.rd, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar, pc.pool_words,
+                     (const uint4*)S.stat, pc.src, ref, D, (const uint4*)S.meta, (const unsigned long long*)S.excl_s, (const unsigned long long*)S.part_s, 0ull, S.out);
+  if (tot[1]) launch(c, k_rows_write<1u>, dim3(blocks), dim3(256), 0, pc.rd, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar, pc.pool_words,
+                     (const uint4*)S.stat, pc.src, ref, D, (const uint4*)S.meta, (const unsigned long long*)S.excl_b, (const unsigned long long*)S.part_b, tot[0], S.out);
+  HIPCHK(c, hipGetLastError());
+  return T.mark(c, 5, c->stream);
+}
+// the arguments of smr_rows_part* that are checked before any state: D takes the columns
+int rows_check_opts(smr_ctx* c, const std::string& W, int slot, const smr_index* ix, const smr_rows_opts* o, RowsOpts& D) {
+  if (!o || !ix || slot < 0 || slot >= 64) { set_err(c, W + "null options or index, or a slot outside 0..63"); return SMR_ERR_ARG; }
+  if (!o->want_sam && !o->want_blast) { set_err(c, W + "neither the SAM nor the BLAST rows are wanted"); return SMR_ERR_ARG; }
+  memset(&D, 0, sizeof D);
+  if (!rows_parse_cols(o->blast_cols, D)) { set_err(c, W + "blast_cols takes \"cigar\", \"qcov\" and \"qstrand\", space separated"); return SMR_ERR_ARG; }
+  return SMR_OK;
+}
+
 // The writer behind smr_rows_part (gz_off null: `bytes` takes the two streams, `off` their offsets) and smr_rows_part_gz (gz_off given: the
 // streams stay on the device and go through gz_run with cuts at line ends, `bytes` takes the gzip members, gz_off their offsets, `off` what
 // the plain call returns)
@@ -140,13 +188,10 @@ int rows_impl(smr_ctx* c, const char* who, int slot, const smr_params* p, const 
   off[0] = off[1] = off[2] = 0;
   if (zip) gz_off[0] = gz_off[1] = gz_off[2] = 0;
   if (need) *need = 0;
-  if (!o || !ix || slot < 0 || slot >= 64) { set_err(c, W + "null options or index, or a slot outside 0..63"); return SMR_ERR_ARG; }
-  if (!o->want_sam && !o->want_blast) { set_err(c, W + "neither the SAM nor the BLAST rows are wanted"); return SMR_ERR_ARG; }
   RowsOpts D;
-  memset(&D, 0, sizeof D);
-  if (!rows_parse_cols(o->blast_cols, D)) { set_err(c, W + "blast_cols takes \"cigar\", \"qcov\" and \"qstrand\", space separated"); return SMR_ERR_ARG; }
+  int rc = rows_check_opts(c, W, slot, ix, o, D); if (rc) return rc;
   PartCall pc = {c->idx[slot], *c->b};
-  int rc = part_call_open(c, who, p, ix, pc); if (rc) return rc;
+  if ((rc = part_call_open(c, who, p, ix, pc))) return rc;
   const Batch& B = pc.B;
   if (B.n == 0) return SMR_OK;
   if ((rc = part_call_views(c, who, pc))) return rc;
@@ -154,28 +199,14 @@ int rows_impl(smr_ctx* c, const char* who, int slot, const smr_params* p, const 
   RowsScratch& S = c->rows;
   StageClock<7, 4>& T = S.clk;
   if ((rc = T.begin(c))) return rc;
-  const uint32_t n = pc.n, np = (n + ROWS_BLOCK - 1u) / ROWS_BLOCK;
   if ((rc = rows_names(c, pc.di, ix, p->part, who))) return rc;
   if (D.want_blast) {
     D.n_tab = (uint32_t)std::min<uint64_t>(65536u, (uint64_t)p->match * B.max_len + 1u);
     if ((rc = rows_table(c, o, D.n_tab, who))) return rc;
   }
-  if ((rc = S.stat.reserve(c, pc.ntot)) || (rc = S.meta.reserve(c, n)) || (rc = S.excl_s.reserve(c, n)) || (rc = S.excl_b.reserve(c, n)) ||
-      (rc = S.part_s.reserve(c, (size_t)np + 1)) || (rc = S.part_b.reserve(c, (size_t)np + 1)) || (rc = S.err.reserve(c, ROWS_E_COUNT))) return rc;
   RowsRef ref; ref.names = pc.di.rows_names; ref.name_off = pc.di.rows_name_off; ref.tab = S.tab;
-  if ((rc = rows_guard(c, who, T, pc, D, ref, o))) return rc;
-  if ((rc = T.mark(c, 2, c->stream))) return rc;
-  launch(c, k_rows_size, dim3(np), dim3(ROWS_BLOCK), 0, pc.rd, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar, pc.pool_words,
-         (const uint4*)S.stat, pc.src, ref, D, S.meta, S.excl_s, S.excl_b, S.part_s, S.part_b);
-  launch(c, k_export_scan, dim3(1), dim3(EXP_SIZE_BLOCK), 0, S.part_s, np + 1u);
-  launch(c, k_export_scan, dim3(1), dim3(EXP_SIZE_BLOCK), 0, S.part_b, np + 1u);
-  HIPCHK(c, hipGetLastError());
-  if ((rc = T.mark(c, 3, c->stream))) return rc;
-  unsigned long long tot[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(&tot[0], S.part_s + np, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&tot[1], S.part_b + np, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  T.set(1, 2, 3);
+  unsigned long long tot[2];
+  if ((rc = rows_sizes(c, who, T, pc, S, D, ref, o, tot))) return rc;
   const uint64_t total = tot[0] + tot[1];
   off[1] = tot[0]; off[2] = total;
   if (need) *need = total;
@@ -185,16 +216,7 @@ int rows_impl(smr_ctx* c, const char* who, int slot, const smr_params* p, const 
     if (cap < total) { set_err(c, W + "the rows take " + std::to_string(total) + " bytes, the buffer has " + std::to_string(cap)); return SMR_ERR_CAPACITY; }
   }
   if (total == 0) return SMR_OK;
-  // the rows, staged on the device: copied to the host from there, or compressed from there
-  if ((rc = S.out.reserve_headroom(c, (size_t)total, 8))) return rc;
-  const uint32_t chunks = (n + 63u) / 64u, blocks = std::max(1u, std::min<uint32_t>((chunks + 3u) / 4u, (uint32_t)c->n_cu * 8u));
-  if ((rc = T.mark(c, 4, c->stream))) return rc;
-  if (tot[0]) launch(c, k_rows_write<0u>, dim3(blocks), dim3(256), 0, pc.rd, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar, pc.pool_words,
-                     (const uint4*)S.stat, pc.src, ref, D, (const uint4*)S.meta, (const unsigned long long*)S.excl_s, (const unsigned long long*)S.part_s, 0ull, S.out);
-  if (tot[1]) launch(c, k_rows_write<1u>, dim3(blocks), dim3(256), 0, pc.rd, B.slots, (const RState*)B.d_saved, (const AlignRec*)B.d_saved_aln, (const uint32_t*)B.d_cigar, pc.pool_words,
-                     (const uint4*)S.stat, pc.src, ref, D, (const uint4*)S.meta, (const unsigned long long*)S.excl_b, (const unsigned long long*)S.part_b, tot[0], S.out);
-  HIPCHK(c, hipGetLastError());
-  if ((rc = T.mark(c, 5, c->stream))) return rc;
+  if ((rc = rows_write(c, T, pc, S, D, ref, tot))) return rc;
   if (zip) {                                           // (the time of a copy that is not made stays 0)
     if ((rc = gz_run(c, who, S.out, off, 2, bytes, cap, gz_off, need, true)) && rc != SMR_ERR_CAPACITY) return rc;
     T.set(2, 4, 5);

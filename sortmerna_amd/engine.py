@@ -678,6 +678,84 @@ class Engine:
             self._chk(self.L.smr_pairwise_part_gz(*args, buf.ctypes.data, need.value, C.byref(plain), C.byref(need)), "smr_pairwise_part_gz")
         return buf[:need.value].tobytes(), int(plain.value)
 
+    @staticmethod
+    def _rows_opts(sam, blast, cols, lam, K, full_ref, full_read):
+        o = capi.RowsOpts()
+        o.want_sam, o.want_blast = int(bool(sam)), int(bool(blast))
+        o.blast_cols = (cols if isinstance(cols, str) else " ".join(cols)).encode()
+        o.lam, o.K, o.full_ref_corr, o.full_read_corr = float(lam), float(K), int(full_ref), int(full_read)
+        return o
+
+    def rows_part_mates(self, mates, slot, params, index, sam=True, blast=False, cols="", lam=0.0, K=0.0, full_ref=0, full_read=0):
+        """smr_rows_part_mates: rows_part for mates in two reads files -- read i of the selected batch and read i of batch `mates` (both uploaded
+        with keep=True) -- in the order in which Report.add_pair appends them -> (sam_bytes, blast_bytes).  Other arguments as rows_part."""
+        o = self._rows_opts(sam, blast, cols, lam, K, full_ref, full_read)
+        off = (C.c_uint64 * 3)()
+        need = C.c_uint64(0)
+        args = (self.h, int(mates), slot, C.byref(params), index.h, C.byref(o))
+        self._chk(self.L.smr_rows_part_mates(*args, None, 0, off, C.byref(need)), "smr_rows_part_mates")
+        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
+        if need.value:
+            self._chk(self.L.smr_rows_part_mates(*args, buf.ctypes.data, need.value, off, C.byref(need)), "smr_rows_part_mates")
+        raw = buf.tobytes()
+        return raw[off[0]:off[1]], raw[off[1]:off[2]]
+
+    def pairwise_part_mates(self, mates, slot, params, index, lam=0.0, K=0.0, full_ref=0, full_read=0):
+        """smr_pairwise_part_mates: pairwise_part for mates in two reads files (the selected batch and batch `mates`), in the order of
+        Report.add_pair -> bytes.  Other arguments as pairwise_part."""
+        need = C.c_uint64(0)
+        args = (self.h, int(mates), slot, C.byref(params), index.h, float(lam), float(K), int(full_ref), int(full_read))
+        self._chk(self.L.smr_pairwise_part_mates(*args, None, 0, C.byref(need)), "smr_pairwise_part_mates")
+        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
+        if need.value:
+            self._chk(self.L.smr_pairwise_part_mates(*args, buf.ctypes.data, need.value, C.byref(need)), "smr_pairwise_part_mates")
+        return buf[:need.value].tobytes()
+
+    def rows_part_mates_gz(self, mates, slot, params, index, sam=True, blast=False, cols="", lam=0.0, K=0.0, full_ref=0, full_read=0):
+        """smr_rows_part_mates_gz: the two streams of rows_part_mates, compressed on the device -> (sam_gz, blast_gz, plain_off) as rows_part_gz"""
+        o = self._rows_opts(sam, blast, cols, lam, K, full_ref, full_read)
+        gz_off, plain_off = (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        need = C.c_uint64(0)
+        args = (self.h, int(mates), slot, C.byref(params), index.h, C.byref(o))
+        self._chk(self.L.smr_rows_part_mates_gz(*args, None, 0, gz_off, plain_off, C.byref(need)), "smr_rows_part_mates_gz")
+        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
+        if need.value:
+            self._chk(self.L.smr_rows_part_mates_gz(*args, buf.ctypes.data, need.value, gz_off, plain_off, C.byref(need)), "smr_rows_part_mates_gz")
+        raw = buf.tobytes()
+        return raw[gz_off[0]:gz_off[1]], raw[gz_off[1]:gz_off[2]], [int(x) for x in plain_off]
+
+    def pairwise_part_mates_gz(self, mates, slot, params, index, lam=0.0, K=0.0, full_ref=0, full_read=0):
+        """smr_pairwise_part_mates_gz: the text of pairwise_part_mates, compressed on the device -> (gz, plain_bytes) as pairwise_part_gz"""
+        need, plain = C.c_uint64(0), C.c_uint64(0)
+        args = (self.h, int(mates), slot, C.byref(params), index.h, float(lam), float(K), int(full_ref), int(full_read))
+        self._chk(self.L.smr_pairwise_part_mates_gz(*args, None, 0, C.byref(plain), C.byref(need)), "smr_pairwise_part_mates_gz")
+        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
+        if need.value:
+            self._chk(self.L.smr_pairwise_part_mates_gz(*args, buf.ctypes.data, need.value, C.byref(plain), C.byref(need)), "smr_pairwise_part_mates_gz")
+        return buf[:need.value].tobytes(), int(plain.value)
+
+    def interleave_batch(self, a_pieces, b_pieces):
+        """smr_interleave_batch (the seam of the interleave kernel): two equally long lists of bytes objects -> a[0] + b[0] + a[1] + b[1] + ..."""
+        n = len(a_pieces)
+        if len(b_pieces) != n:
+            raise SmrError("interleave_batch: %d pieces against %d" % (n, len(b_pieces)))
+        a_off = np.concatenate([[0], np.cumsum([len(x) for x in a_pieces], dtype=np.uint64)]).astype(np.uint64)
+        b_off = np.concatenate([[0], np.cumsum([len(x) for x in b_pieces], dtype=np.uint64)]).astype(np.uint64)
+        a = np.frombuffer(b"".join(a_pieces) or b"\0", dtype=np.uint8)
+        b = np.frombuffer(b"".join(b_pieces) or b"\0", dtype=np.uint8)
+        u64p = C.POINTER(C.c_uint64)
+        need = C.c_uint64(0)
+        args = (self.h, n, a.ctypes.data, a_off.ctypes.data_as(u64p), b.ctypes.data, b_off.ctypes.data_as(u64p))
+        self._chk(self.L.smr_interleave_batch(*args, None, 0, C.byref(need)), "smr_interleave_batch")
+        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
+        if need.value:
+            self._chk(self.L.smr_interleave_batch(*args, buf.ctypes.data, need.value, C.byref(need)), "smr_interleave_batch")
+        return buf[:need.value].tobytes()
+
+    def mates_times(self):
+        """HIP-event ms of the last *_mates call: dict(selected, mates, interleave, d2h)"""
+        return self._times("smr_mates_times", ("selected", "mates", "interleave", "d2h"))
+
     def rows_fmt_batch(self, num, den):
         """smr_rows_fmt_batch (a test seam): the device's `%.3g` of 100 * num[i] / den[i] -> list of str"""
         num = np.ascontiguousarray(num, dtype=np.uint32)
