@@ -218,6 +218,14 @@ int smr_seed_tuples_fetch(smr_ctx*, uint64_t* tuples, uint64_t cap_tuples, uint3
 /* Test seam of the seed-hit pool (SMR_SEED_POOL_WORDS=<n> starts it at n words, clamped to [64, 0x7FFFFFF0]): info = {pool words, regrows
  * since smr_create, one past the highest pool word the selected batch's last seed stage handed out, 1 if that stage inlined one-hit windows}. */
 int smr_seed_pool_info(smr_ctx*, uint64_t info[4]);
+/* Test seams of the search bitmap (SMR_SEED_NBMAP, csrc/smr_nbmap.hpp).  smr_seed_nbmap_info: info = {1 if the part in `slot` has a bitmap, pattern
+ * chars it leaves out, its bytes, present mini-tries of the part, their strings, microseconds of the builder kernel, then from the selected batch's
+ * counters: searches probed, searches whose bit was set, searches of those that accepted no string}; an empty slot gives zeros for the part.
+ * The three count the chunks k_seed_pg finished itself: a wave chunk handed to the DFS kernel (candidate pool overflow) or made of repeated seeds only is in none of them.
+ * smr_seed_nbmap_fetch: slabs [first, first + n)
+ * of the part's bitmap (slab 2 * key + direction, 4^(partialwin - chars left out) / 32 words each). */
+int smr_seed_nbmap_info(smr_ctx*, int slot, uint64_t info[9]);
+int smr_seed_nbmap_fetch(smr_ctx*, int slot, uint64_t first, uint64_t n, uint32_t* out, uint64_t cap_words);
 /* Test seam of the candidate stage (tests/test_gpu_cand_limits.py).  smr_cand_info: info = {attempts of the last smr_align_part, how many of them
  * were redone because of HITCAP, POOL, PAIRS, REDO, SCAP (five words), then chain_ext, chain_scap, keys_cap, pairs_cap, hits_cap of the context as
  * they stand, 1 if the route bytes are switched on, the number of reads they cover}.  After smr_cand_info_enable(ctx, 1) every smr_align_part also

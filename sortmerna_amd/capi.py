@@ -79,7 +79,7 @@ EXPORTS = [
     "smr_params_default", "smr_params_refused", "smr_index_load_files", "smr_index_build", "smr_index_build_gpu", "smr_index_write_files", "smr_index_save", "smr_index_load_flat", "smr_index_selfcheck", "smr_index_free",
     "smr_index_get_info", "smr_minimal_score", "smr_minimal_score_split", "smr_refstats_corrected_split", "smr_reads_pack", "smr_reads_load_fastx", "smr_reads_load_fastx_mt", "smr_reads_load_fastx_text", "smr_reads_is_fastq", "smr_reads_record_text", "smr_reads_free", "smr_reads_slice",
     "smr_reads_digest", "smr_reads_count", "smr_reads_total_len", "smr_reads_min_len", "smr_reads_max_len", "smr_create", "smr_device_count", "smr_destroy",
-    "smr_last_error", "smr_tuning_text", "smr_index_upload", "smr_index_check_device", "smr_index_pigeonhole", "smr_seed_tuples_fetch", "smr_seed_pool_info", "smr_cand_info_enable", "smr_cand_info", "smr_cand_routes", "smr_index_unload", "smr_batch_select", "smr_set_seed_mode", "smr_reads_upload", "smr_reads_upload_batch", "smr_reads_upload_fastx", "smr_reads_upload_fastx_batch", "smr_reads_upload_fastx_file", "smr_fastx_info", "smr_fastx_times", "smr_fastx_split", "smr_fastx_split_times", "smr_rows_part", "smr_rows_times", "smr_rows_fmt_batch", "smr_pairwise_part", "smr_pairwise_times", "smr_state_reset", "smr_align_part",
+    "smr_last_error", "smr_tuning_text", "smr_index_upload", "smr_index_check_device", "smr_index_pigeonhole", "smr_seed_tuples_fetch", "smr_seed_pool_info", "smr_seed_nbmap_info", "smr_seed_nbmap_fetch", "smr_cand_info_enable", "smr_cand_info", "smr_cand_routes", "smr_index_unload", "smr_batch_select", "smr_set_seed_mode", "smr_reads_upload", "smr_reads_upload_batch", "smr_reads_upload_fastx", "smr_reads_upload_fastx_batch", "smr_reads_upload_fastx_file", "smr_fastx_info", "smr_fastx_times", "smr_fastx_split", "smr_fastx_split_times", "smr_rows_part", "smr_rows_times", "smr_rows_fmt_batch", "smr_pairwise_part", "smr_pairwise_times", "smr_state_reset", "smr_align_part",
     "smr_traceback", "smr_counters", "smr_counters_device", "smr_state_import", "smr_state_export", "smr_counters_import", "smr_results_fetch", "smr_result_record", "smr_result_record_batch", "smr_counters_accumulate",
     "smr_result_is_hit", "smr_seed_scan", "smr_seed_hits_fetch", "smr_sw_selfcheck", "smr_sw_mode", "smr_walk_rounds", "smr_ssw_batch", "smr_sw16_batch", "smr_sw16_prefix_batch", "smr_walk_prefix_stats", "smr_sw16_launches", "smr_sw16_f16", "smr_sw_long_rows", "smr_cigar_batch", "smr_idcov_part", "smr_idcov_counters", "smr_idcov_counters_device", "smr_idcov_batch", "smr_prof_reset", "smr_prof_get", "smr_prof_kernels", "smr_refstats_corrected", "smr_report_open",
     "smr_report_set_db", "smr_report_set_part", "smr_report_add", "smr_report_add_pair", "smr_report_add_fastx", "smr_report_skip_fastx", "smr_report_add_rows", "smr_report_skip_rows", "smr_report_add_pairwise", "smr_report_skip_pairwise", "smr_report_set_cmdline", "smr_report_otu_count", "smr_report_otu_merge", "smr_report_close", "smr_report_last_error",
@@ -166,6 +166,10 @@ def bind(L):
     L.smr_seed_tuples_fetch.argtypes = [vp, vp, u64, vp, u32, C.POINTER(u32)]
     L.smr_seed_pool_info.restype = i32
     L.smr_seed_pool_info.argtypes = [vp, C.POINTER(u64)]
+    L.smr_seed_nbmap_info.restype = i32
+    L.smr_seed_nbmap_info.argtypes = [vp, i32, C.POINTER(u64)]
+    L.smr_seed_nbmap_fetch.restype = i32
+    L.smr_seed_nbmap_fetch.argtypes = [vp, i32, u64, u64, vp, u64]
     L.smr_cand_info_enable.restype = i32
     L.smr_cand_info_enable.argtypes = [vp, i32]
     L.smr_cand_info.restype = i32

@@ -41,6 +41,14 @@ template <class T> class DevBuf {
     cap_ = count;
     return 0;
   }
+  // the same for a buffer the caller can do without: false when the device has no room (no error is set; the buffer is empty then)
+  bool try_alloc(size_t count) {
+    release();
+    if (count == 0) count = 1;
+    if (hipMalloc((void**)&p_, count * sizeof(T)) != hipSuccess) { p_ = nullptr; (void)hipGetLastError(); return false; }
+    cap_ = count;
+    return true;
+  }
   // grow-only: a new array when this one holds fewer than `need` elements
   int reserve(smr_ctx* c, size_t need) { return (p_ && cap_ >= need) ? 0 : alloc(c, need); }
   // a staging buffer for `total` elements of which a kernel may touch `slack` more: when it is too small, a new one with an eighth to spare,

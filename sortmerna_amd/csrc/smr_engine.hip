@@ -25,6 +25,7 @@
 #include "smr_gunzip.hpp"
 #include "smr_ibuild.hpp"
 #include "smr_pgbuild.hpp"
+#include "smr_nbmap.hpp"
 #include "smr_hostmem.hpp"
 #include "smr_devbuf.hpp"
 #include "smr_stage.hpp"
@@ -39,6 +40,9 @@ struct DevIndex {
   bool used = false;
   DevBuf<Lookup> lookup; DevBuf<uint32_t> trie, pos_off; DevBuf<uint2> pos_arr;
   DevBuf<uint32_t> pg, root3, lkc;
+  // the bitmap of the searches that can accept a string (smr_nbmap.hpp), or one word of ones (nb_words = 0); nb_info = {1 if built, chars dropped,
+  // bytes, present mini-tries, their strings, microseconds of the builder kernel} (smr_seed_nbmap_info)
+  DevBuf<uint32_t> nbmap; uint32_t nb_words = 0, nb_mask = 0, nb_slabs = 0; uint64_t nb_info[6] = {0, 0, 0, 0, 0, 0};
   DevBuf<uint8_t> ref_seq; DevBuf<uint64_t> ref_off;
   uint32_t n_refs = 0, n_ids = 0, lnwin = 0;
   uint32_t ref_any_n = 1;     // does any reference hold an ambiguous letter (0 only when the upload looked and found none)
@@ -345,7 +349,7 @@ int part_refuse_state(smr_ctx* c, const char* who, uint32_t no_cigar, uint32_t b
 }
 
 DIndex dindex(const DevIndex& d) {
-  DIndex x; x.lookup = d.lookup; x.trie = d.trie; x.pg = d.pg; x.lkc = d.lkc; x.root3 = reinterpret_cast<const uint2*>(d.root3.get()); x.pos_off = d.pos_off; x.pos_arr = d.pos_arr; x.ref_seq = d.ref_seq; x.ref_off = d.ref_off;
+  DIndex x; x.lookup = d.lookup; x.trie = d.trie; x.pg = d.pg; x.lkc = d.lkc; x.root3 = reinterpret_cast<const uint2*>(d.root3.get()); x.nbmap = d.nbmap; x.nb_words = d.nb_words; x.nb_mask = d.nb_mask; x.pos_off = d.pos_off; x.pos_arr = d.pos_arr; x.ref_seq = d.ref_seq; x.ref_off = d.ref_off;
   x.n_refs = d.n_refs; x.n_ids = d.n_ids; x.lnwin = d.lnwin; x.partialwin = d.lnwin / 2; x.ref_any_n = d.ref_any_n;
   return x;
 }
@@ -546,6 +550,60 @@ int build_pigeonhole_device(smr_ctx* c, DevIndex& d, uint32_t nk, uint32_t pw) {
   d.pg_words = W;
   return SMR_OK;
 }
+
+// The bitmap of slot d's part (smr_nbmap.hpp), by the policy of SMR_SEED_NBMAP: none when the switch is 0, when mode 1 finds the part too sparse for
+// it to pay, when no projection of at least NB_MIN_CHARS chars fits the byte budget, or when the device has no room for it -- never an error.
+int build_nbmap(smr_ctx* c, DevIndex& d, uint32_t nk, uint32_t pw) {
+  int rc;
+  d.nb_words = d.nb_mask = d.nb_slabs = 0;
+  for (auto& x : d.nb_info) x = 0;
+  if ((rc = d.nbmap.alloc(c, 4))) return rc;
+  HIPCHK(c, hipMemsetAsync(d.nbmap, 0xFF, 16, c->stream));
+  const Tuning& t = c->tune;
+  if (t.seed_nbmap == 0) return SMR_OK;
+  const uint32_t nb = 2 * nk;
+  DevBuf<unsigned long long> cen;
+  if ((rc = cen.alloc(c, 2))) return rc;
+  HIPCHK(c, hipMemsetAsync(cen, 0, 16, c->stream));
+  launch(c, smr::k_nbmap_census, dim3((nb + 255) / 256), dim3(256), 0, (const uint32_t*)d.root3, nb, cen);
+  unsigned long long h[2] = {0, 0};
+  HIPCHK(c, hipMemcpyAsync(h, cen, 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  d.nb_info[3] = h[0]; d.nb_info[4] = h[1];
+  if (h[0] == 0 || (t.seed_nbmap == 1 && h[1] < (unsigned long long)t.nbmap_min * h[0])) return SMR_OK;
+  uint64_t budget = t.nbmap_bytes;
+  if (t.seed_nbmap == 1) {
+    size_t mem_free = 0, mem_total = 0;
+    if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); return SMR_OK; }
+    // (a quarter of what is free: the part is uploaded before its batches, whose buffers, seed-hit pool and regrows come out of the rest)
+    budget = std::min<uint64_t>(budget, (uint64_t)mem_free / 4);
+  }
+  uint32_t drop = t.nbmap_drop;
+  auto bytes_at = [&](uint32_t s) { return (uint64_t)nb * smr::nb_slab_words(pw, s) * 4; };
+  while (drop < pw && pw - drop >= NB_MIN_CHARS && (pw - drop > NB_MAX_CHARS || bytes_at(drop) > budget)) drop++;
+  if (drop >= pw || pw - drop < NB_MIN_CHARS) { say(t, "index part: no search bitmap (none of at least %u pattern chars fits %.2f GB)\n", NB_MIN_CHARS, budget * 1e-9); return SMR_OK; }
+  const uint64_t bytes = bytes_at(drop);
+  DevBuf<uint32_t> map;                                    // (takes the place of the word of ones only once it is built)
+  if (bytes > t.nbmap_alloc_max || !map.try_alloc(bytes / 4)) {
+    say(t, "index part: no search bitmap (no room for %.2f GB on the device)\n", bytes * 1e-9);
+    return SMR_OK;
+  }
+  const uint32_t words = (uint32_t)smr::nb_slab_words(pw, drop);
+  struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } e0, e1;
+  HIPCHK(c, hipEventCreate(&e0.e)); HIPCHK(c, hipEventCreate(&e1.e));
+  HIPCHK(c, hipEventRecord(e0.e, c->stream));
+  launch(c, smr::k_nbmap_build, dim3(nb), dim3(256), (size_t)words * 4, (const uint32_t*)d.root3, (const uint32_t*)d.pg, pw, drop, map.get());
+  HIPCHK(c, hipEventRecord(e1.e, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, e0.e, e1.e);
+  d.nbmap = std::move(map);
+  d.nb_words = words; d.nb_mask = (1u << (2 * (pw - drop))) - 1u; d.nb_slabs = nb;
+  d.nb_info[0] = 1; d.nb_info[1] = drop; d.nb_info[2] = bytes; d.nb_info[5] = (uint64_t)(ms * 1000.0f);
+  say(t, "index part: search bitmap %.2f GB (%u of %u pattern chars, %.0f strings per mini-trie), built in %.1f ms\n", bytes * 1e-9, pw - drop, pw, (double)h[1] / (double)h[0], ms);
+  return SMR_OK;
+}
 }  // namespace
 
 extern "C" int smr_index_upload(smr_ctx* c, const smr_index* ix, int slot) {
@@ -592,6 +650,8 @@ extern "C" int smr_index_upload(smr_ctx* c, const smr_index* ix, int slot) {
   if ((rc = d.ref_seq.alloc(c, ix->ref_seq.size() + 64))) return rc;
   if ((rc = d.ref_off.alloc(c, ix->ref_off.size()))) return rc;
   HIPCHK(c, hipMemcpyAsync(d.ref_seq, ix->ref_seq.data(), ix->ref_seq.size(), hipMemcpyHostToDevice, c->stream));
+  // (after everything else of the part has its memory: the bitmap takes what is left, or is not built)
+  if ((rc = build_nbmap(c, d, (uint32_t)ix->lookup.size(), ix->lnwin / 2))) return rc;
   d.ref_any_n = (!ix->ref_seq.empty() && memchr(ix->ref_seq.data(), 4, ix->ref_seq.size())) ? 1u : 0u;      // (k_sw16 asks each window for its ambiguous letters only then)
   HIPCHK(c, hipMemcpyAsync(d.ref_off, ix->ref_off.data(), ix->ref_off.size() * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1115,6 +1175,31 @@ extern "C" int smr_seed_pool_info(smr_ctx* c, uint64_t info[4]) {
   uint64_t hi = 0;
   for (int s = 0; s < C_NSHARD; s++) if (cur[s * C_PCUR_STRIDE]) hi = std::max<uint64_t>(hi, s * region + cur[s * C_PCUR_STRIDE]);
   info[0] = c->pool_words; info[1] = c->n_pool_grown; info[2] = hi; info[3] = c->pool_inline;
+  return SMR_OK;
+}
+
+// Test seams of the search bitmap (smr_nbmap.hpp).  smr_seed_nbmap_info: info = {1 if slot's part has a bitmap, pattern chars it leaves out, its bytes,
+// present mini-tries of the part, their strings, microseconds of the builder kernel, then of the SELECTED batch's counters: searches k_seed_pg
+// probed, of which their bit was set, of which accepted no string}.  smr_seed_nbmap_fetch: the slabs [first, first + n) of the part (slab 2 * key +
+// direction; words_per_slab as info says: 4^(pw - dropped) / 32) into out.
+extern "C" int smr_seed_nbmap_info(smr_ctx* c, int slot, uint64_t info[9]) {
+  if (!c || !info || slot < 0 || slot >= 64) return SMR_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  const DevIndex& d = c->idx[slot];
+  for (int q = 0; q < 6; q++) info[q] = d.used ? d.nb_info[q] : 0;       // (an empty slot: zeros, the counters below all the same)
+  std::vector<unsigned long long> h(C_TOTAL, 0ull);
+  if (c->b->d_ctr) { int rc = read_ctr(c, h); if (rc) return rc; }        // (the census is sharded like the work counters: folded on the host)
+  info[6] = h[C_NB_PROBED]; info[7] = h[C_NB_PASSED]; info[8] = h[C_NB_EMPTY];
+  return SMR_OK;
+}
+extern "C" int smr_seed_nbmap_fetch(smr_ctx* c, int slot, uint64_t first, uint64_t n, uint32_t* out, uint64_t cap_words) {
+  if (!c || !out || slot < 0 || slot >= 64 || !c->idx[slot].used) return SMR_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  const DevIndex& d = c->idx[slot];
+  if (!d.nb_words) { set_err(c, "smr_seed_nbmap_fetch: the part has no bitmap"); return SMR_ERR_STATE; }
+  if (first > d.nb_slabs || n > d.nb_slabs - first) return SMR_ERR_ARG;
+  if (cap_words < n * d.nb_words) return SMR_ERR_CAPACITY;
+  if (n) HIPCHK(c, hipMemcpy(out, d.nbmap + first * d.nb_words, n * d.nb_words * 4, hipMemcpyDeviceToHost));
   return SMR_OK;
 }
 

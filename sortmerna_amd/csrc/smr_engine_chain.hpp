@@ -257,6 +257,7 @@ void fold_shards(std::vector<unsigned long long>& h) {
     for (int k = 0; k < C_SHARD_W; k++) {
       if (k < C_SHARD_X) h[C_WINDOWS + k] += h[C_SHARDS + C_SHARD_W * s + k];
       else if (k < C_SHARD_X + C_SHARD_NX) h[C_TUP_F + k - C_SHARD_X] += h[C_SHARDS + C_SHARD_W * s + k];
+      else if (k >= C_SHARD_NB && k < C_SHARD_NB + 3) h[C_NB_PROBED + k - C_SHARD_NB] += h[C_SHARDS + C_SHARD_W * s + k];
       h[C_SHARDS + C_SHARD_W * s + k] = 0;
     }
   unsigned long long mx = 0;

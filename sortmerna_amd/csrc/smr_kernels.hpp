@@ -39,6 +39,8 @@ struct DIndex {
   const uint32_t* trie;
   const uint32_t* pg;          // pigeonhole arena (smr_host.hpp) and its block table: forward / reverse mini-trie of key k at [2k], [2k+1] = {offset / 4, n | cA << 24 | cB << 28}
   const uint2* root3;
+  const uint32_t* nbmap;       // per block table entry nb_words words: bit proj(P) = "a search with pattern P can accept a string" (smr_nbmap.hpp); a part without a
+  uint32_t nb_words, nb_mask;  // bitmap: one word of ones, nb_words = nb_mask = 0 (every probe reads that word); nb_mask: the pattern bits that proj keeps
   const uint32_t* pos_off;     // the index's CSR offsets (id -> list start): what a search's id is made of, id' = pos_off[id] + id
   const uint2* pos_arr;        // per seed, at [id']: a header {positions, the index's id}, then its positions {pos, seq} (k_pos2_build)
   const uint8_t* ref_seq;
@@ -115,13 +117,16 @@ enum {
   C_TUP_F, C_TUP_ALL, C_B_KEYS, C_B_PG0, C_B_PG1, C_B_FIN,
   // the id / coverage pass (smr_idcov.hpp): Readstats::n_yid_ycov, n_yid_ncov, n_nid_ycov, num_denovo (readstats.hpp:77-85; they start over with
   // the batch's state like num_aligned), then the lengths of its two work lists and the alignments it found without a CIGAR
-  C_IDCOV, C_IDCOV_FEW = C_IDCOV + 4, C_IDCOV_MANY, C_IDCOV_NOCIG, C_COUNT = 112,
+  C_IDCOV, C_IDCOV_FEW = C_IDCOV + 4, C_IDCOV_MANY, C_IDCOV_NOCIG,
+  // k_seed_pg with a bitmap (smr_nbmap.hpp): searches probed, searches whose bit was set, and of those the ones that accepted no string
+  C_NB_PROBED, C_NB_PASSED, C_NB_EMPTY, C_COUNT = 112,
   // Work counters and the pool cursor are sharded 64 ways (by block id): one address would serialise ~10 ns per
   // atomic over ~10^6 waves.  Shard s keeps counter C_WINDOWS+k (k < 9) at C_SHARDS + 32*s + k and C_TUP_F+k at C_SHARDS + 32*s + 9 + k
   // (slots 16.. of a shard: the cycle counters of the -DSMR_*_PHASES debug builds); the host folds them.
-  C_NSHARD = 64, C_SHARD_W = 32, C_SHARD_X = 9, C_SHARD_NX = 6, C_SHARD_PH = 16, C_SHARDS = C_COUNT, C_PCUR = C_SHARDS + C_SHARD_W * C_NSHARD, C_PCUR_STRIDE = 16 /* a 128-byte line per cursor: atomics on one line queue up */, C_TOTAL = C_PCUR + C_NSHARD * C_PCUR_STRIDE
+  // (slots 23..25: the bitmap census C_NB_PROBED.. of k_seed_pg, one add per wave of a launch of 262144 waves like the work counters)
+  C_NSHARD = 64, C_SHARD_W = 32, C_SHARD_X = 9, C_SHARD_NX = 6, C_SHARD_PH = 16, C_SHARD_NB = 23, C_SHARDS = C_COUNT, C_PCUR = C_SHARDS + C_SHARD_W * C_NSHARD, C_PCUR_STRIDE = 16 /* a 128-byte line per cursor: atomics on one line queue up */, C_TOTAL = C_PCUR + C_NSHARD * C_PCUR_STRIDE
 };
-static_assert(C_IDCOV_NOCIG < C_COUNT, "counter block");
+static_assert(C_NB_EMPTY < C_COUNT, "counter block");
 __device__ __forceinline__ void ctr_add(unsigned long long* ctr, int idx, unsigned long long v) {
   atomicAdd(&ctr[C_SHARDS + (blockIdx.x & (C_NSHARD - 1)) * C_SHARD_W + (idx >= C_TUP_F ? C_SHARD_X + idx - C_TUP_F : idx - C_WINDOWS)], v);
 }

@@ -201,7 +201,9 @@ __global__ void __launch_bounds__(64 * PG_WAVES, PG_OCC / PG_WAVES) k_seed_pg(DI
   // the wave's work counters: summed in LDS (not in registers: the kernel sits on its 64-VGPR budget), added to the shard once after its last chunk
   __shared__ unsigned long long s_acc[PG_WAVES][3];
   unsigned long long* acc = s_acc[threadIdx.x >> 6];
-  if (lane == 0) { acc[0] = 0; acc[1] = 0; acc[2] = 0; }
+  __shared__ uint32_t s_nbc[PG_WAVES][3];                  // ... and its bitmap census (C_NB_*)
+  uint32_t* nbc = s_nbc[threadIdx.x >> 6];
+  if (lane == 0) { acc[0] = 0; acc[1] = 0; acc[2] = 0; nbc[0] = 0; nbc[1] = 0; nbc[2] = 0; }
   for (uint32_t it = uni(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)); ; it += stride) {      // (uni: the wave's number -- the chunk arithmetic belongs on the scalar unit)
   uint32_t vb = 0;                                         // this wave's 64 tuples
   { const int ck = chunk_of(it, vb); if (ck == 0) break; if (ck == 2) continue; }
@@ -211,6 +213,7 @@ __global__ void __launch_bounds__(64 * PG_WAVES, PG_OCC / PG_WAVES) k_seed_pg(DI
   bool mine = DIR ? (pos >= n_fwd && pos < n_tup) : pos < n_fwd;
   uint32_t nh = 0, P9 = 0, slot = 0, gfl = 0;
   uint2 rt = make_uint2(NONE, 0);
+  uint32_t nbw = 0;                                        // the search's word of the part's bitmap (a part without one: a word of ones)
   uint32_t n_rep = 0;                                      // tuples of this launch in the chunk that repeat another one's seed (k_seed_dedup): read, not searched
   {
     const bool hit = pf && pf_vb == vb;
@@ -230,7 +233,9 @@ __global__ void __launch_bounds__(64 * PG_WAVES, PG_OCC / PG_WAVES) k_seed_pg(DI
       while (pos >= nx) { c++; nx = sb.cbase[c + 1]; }          // (pos < cbase[nc]: ends; a chunk of 64 tuples rarely spans more than two bins)
       SeedKey tk;
       tk.slot = (uint32_t)t; tk.chars = (uint32_t)(t >> 32) & ((1u << sb.cb) - 1u); tk.key = (c << sb.fb) | (uint32_t)(t >> (32u + sb.cb));
-      rt = ix.root3[2 * (tk.key - (DIR ? sb.nkh : 0u)) + DIR];
+      const uint32_t ri = 2 * (tk.key - (DIR ? sb.nkh : 0u)) + DIR;
+      rt = ix.root3[ri];
+      nbw = ix.nbmap[(size_t)ri * ix.nb_words + ((tk.chars & ix.nb_mask) >> 5)];      // (independent of the block table entry: both are under way together)
       P9 = tk.chars; slot = tk.slot;
       if (DIR == 1) gfl = sb.gflag[slot >> 11];              // (asked for with the block table entry, not after it)
     }
@@ -239,6 +244,10 @@ __global__ void __launch_bounds__(64 * PG_WAVES, PG_OCC / PG_WAVES) k_seed_pg(DI
   if (mine) {
     if (DIR == 1 && ((gfl >> ((slot >> 6) & 31u)) & 1u) && ((sb.zbits[slot >> 5] >> (slot & 31u)) & 1u)) mine = false;   // accept_zero_kmer: no reverse search (paralleltraversal.cpp:188)
   }
+  // a search that no string of its mini-trie can accept (smr_nbmap.hpp) is not made: it gets no directory ranges and no strings and writes nothing,
+  // which is what it would have come to (a key without a mini-trie has a zero slab)
+  const uint32_t n_prob = (uint32_t)__popcll(__ballot(mine));
+  if (mine && !((nbw >> (P9 & 31u)) & 1u)) mine = false;
   if (lane == 0) s_ncand = 0;
   __syncthreads();
   GPH(0)
@@ -325,6 +334,10 @@ __global__ void __launch_bounds__(64 * PG_WAVES, PG_OCC / PG_WAVES) k_seed_pg(DI
     }
     continue;
   }
+  if (ix.nb_words) {                                // the census of the bitmap: probed, passed, passed for nothing
+    const uint32_t n_pass = (uint32_t)__popcll(__ballot(srch)), n_empty = (uint32_t)__popcll(__ballot(srch && hd[lane] == PG_NIL));
+    if (lane == 0) { nbc[0] += n_prob; nbc[1] += n_pass; nbc[2] += n_empty; }
+  }
   own[lane] = 0;
   __builtin_amdgcn_wave_barrier();
   pg_resolve(s_ncand, lane, O.blo, O.bhi, rt.y, cdk, cdv, own);
@@ -384,12 +397,14 @@ __global__ void __launch_bounds__(64 * PG_WAVES, PG_OCC / PG_WAVES) k_seed_pg(DI
   unsigned long long w_bytes = (uint32_t)__popcll(__ballot(counted)) * ((uint32_t)sizeof(SeedTup) + 8u + (DIR ? 1u : 0u))
                              + 32u * (uint32_t)__popcll(__ballot(srch && cA)) + 4u * (uint32_t)__popcll(__ballot(wr));
   w_bytes += 4ull * wtot + 4ull * total + 8ull * min(s_ncand, ccap) + 2u + 8ull * n_rep;
+  if (ix.nb_words) w_bytes += 4ull * (uint32_t)__popcll(__ballot(counted));      // the bitmap word of every tuple decoded
   if (lane == 0) { acc[0] += w_node; acc[1] += w_entry; acc[2] += w_bytes; }
 #ifdef SMR_SEED_PHASES
   GPH(5)
   if (lane == 0) for (int q = 0; q < 7; q++) if (tph[q]) { atomicAdd(&ctr[C_SHARDS + (vb & (C_NSHARD - 1)) * C_SHARD_W + C_SHARD_PH + q], tph[q]); tph[q] = 0; }
 #endif
   }
+  if (lane == 0 && nbc[0]) for (int q = 0; q < 3; q++) atomicAdd(&ctr[C_SHARDS + (blockIdx.x & (C_NSHARD - 1)) * C_SHARD_W + C_SHARD_NB + q], (unsigned long long)nbc[q]);
   if (lane == 0) { if (acc[0]) ctr_add(ctr, C_NODE, acc[0]); if (acc[1]) ctr_add(ctr, C_ENTRY, acc[1]); if (acc[2]) ctr_add(ctr, DIR ? C_B_PG1 : C_B_PG0, acc[2]); }
 }
 

@@ -36,6 +36,12 @@ struct Tuning {
                                           //   (not in the table below, whose names tests/test_emu_tuning.py pins: smr_walk_prefix_stats hands out what was latched)
   int sw16_f16 = 1;                       // SMR_SW16_F16: 0 = k_sw16 (packed 16-bit integers) scores every task list, 1 = k_sw16h (packed f16, three-operand maxima) where sw_h16_fits holds
                                           //   (not in the table below either: smr_sw16_f16 hands out the mode in use)
+  int seed_nbmap = 1;                     // SMR_SEED_NBMAP: the per-key bitmap of the searches that can accept a string (smr_nbmap.hpp): 0 none, 1 where the part is dense enough and the map fits, 2 whatever the density (tests)
+  uint32_t nbmap_drop = 1;                //   SMR_SEED_NBMAP_DROP: pattern chars the bitmap leaves out, at least (the policy raises it until the map fits); 1 measured best of 0, 1, 2 on the bench workload (profiles/nbmap_census.log)   [0..SEED_MAXPW]
+  uint32_t nbmap_min = 128;               //   SMR_SEED_NBMAP_MIN: strings per present mini-trie from which mode 1 builds (the bench DB has 377, refs8's first member 51, config2's 6; where between 51 and 377 it pays was not measured)
+  uint64_t nbmap_bytes = 24ull << 30;     //   SMR_SEED_NBMAP_BYTES: the most a part's bitmap may take (mode 1: and a quarter of the free device memory)
+  uint64_t nbmap_alloc_max = ~0ull;       //   SMR_SEED_NBMAP_ALLOC_MAX: test aid, a bitmap larger than this finds no memory (the fall-back to no filter)
+                                          //   (none of the five in the table below: smr_seed_nbmap_info hands out what a part got)
   bool begins_x4 = false;                 // SMR_BEGINS_X4 (set): begin cells four per wave (k_begins) instead of sixteen (k_sw16)
   bool pg_host = false;                   // SMR_PG_HOST: the host transform of the pigeonhole layout instead of the device build at upload
   bool trace_global_rows = false;         // SMR_TRACE_GLOBAL_ROWS (set): the wide-band variant of k_trace_wide, rows in global memory
@@ -81,6 +87,11 @@ inline Tuning read_tuning(const TuningLimits& L) {
   if ((e = getenv("SMR_WALK_ASSUME"))) t.walk_assume = (uint32_t)atoi(e);
   if ((e = getenv("SMR_WALK_PREFIX"))) t.walk_prefix = (uint32_t)std::max(0, std::min(100, atoi(e)));
   if ((e = getenv("SMR_SW16_F16"))) t.sw16_f16 = atoi(e) != 0 ? 1 : 0;
+  if ((e = getenv("SMR_SEED_NBMAP"))) t.seed_nbmap = std::max(0, std::min(2, atoi(e)));
+  if ((e = getenv("SMR_SEED_NBMAP_DROP"))) t.nbmap_drop = (uint32_t)std::max(0, std::min(10, atoi(e)));
+  if ((e = getenv("SMR_SEED_NBMAP_MIN"))) t.nbmap_min = (uint32_t)std::max(0, atoi(e));
+  if ((e = getenv("SMR_SEED_NBMAP_BYTES"))) t.nbmap_bytes = strtoull(e, nullptr, 0);
+  if ((e = getenv("SMR_SEED_NBMAP_ALLOC_MAX"))) t.nbmap_alloc_max = strtoull(e, nullptr, 0);
   t.begins_x4 = getenv("SMR_BEGINS_X4") != nullptr;
   if ((e = getenv("SMR_PG_HOST"))) t.pg_host = atoi(e) != 0;
   t.trace_global_rows = getenv("SMR_TRACE_GLOBAL_ROWS") != nullptr;

@@ -916,6 +916,19 @@ class Engine:
         self.L.smr_tuning_text(self.h, buf, len(buf))
         return {k: int(v) for k, v in (line.split("=") for line in buf.value.decode().splitlines())}
 
+    def seed_nbmap_info(self, slot=0):
+        """dict(built, drop, bytes, tries, strings, build_us, probed, passed, empty) of the search bitmap of the part in `slot` (smr_seed_nbmap_info: a
+        test seam); the last three are the selected batch's counters of k_seed_pg"""
+        info = (C.c_uint64 * 9)()
+        self._chk(self.L.smr_seed_nbmap_info(self.h, slot, info), "smr_seed_nbmap_info")
+        return dict(zip(("built", "drop", "bytes", "tries", "strings", "build_us", "probed", "passed", "empty"), (int(x) for x in info)))
+
+    def seed_nbmap_fetch(self, slot, first, n, words_per_slab):
+        """uint32[n, words_per_slab]: slabs first .. first + n - 1 of the part's search bitmap (slab 2 * key + direction)"""
+        out = np.empty((n, words_per_slab), dtype=np.uint32)
+        self._chk(self.L.smr_seed_nbmap_fetch(self.h, slot, first, n, out.ctypes.data_as(C.c_void_p), out.size), "smr_seed_nbmap_fetch")
+        return out
+
     def seed_pool_info(self):
         """dict(words, grown, hi, inline) of the seed-hit pool (smr_seed_pool_info: a test seam): its size in words, its regrows since the engine
         was created, one past the highest word the last seed stage handed out, whether that stage inlined one-hit windows"""
