@@ -25,6 +25,10 @@
 // --otu device (needs --pack device): the members of otu_map.txt come from one smr_otu_part call per (index, part) (smr_report_add_otu) and
 // aligned_denovo.* from one smr_fastx_denovo call (smr_report_add_denovo) instead of read by read; the default, --otu host, is smr_report_add.
 // Single reads and interleaved mates; refused with two reads files.  Every output file is the same.
+// --otu-mates device (needs two reads files and --pack device): what --otu device does, for mates in two files: the members of otu_map.txt come
+// from one smr_otu_part_mates call per (index, part) with batch 0 selected and mates = 1, in the visit that serves --rows device, and
+// aligned_denovo.* from one smr_fastx_denovo call of layout 2.  With --split device and, for rows or pairwise text, --mates device, the per-pair
+// loop feeds the report nothing.  The default, --otu-mates host, is smr_report_add_pair.  Every output file is the same.
 // --zip device (needs --split device and gzipped reports): aligned.* / other.*, and with --otu device aligned_denovo.*, are deflated by the
 // DEFLATE kernels where the split leaves them (smr_fastx_split_gz / smr_fastx_denovo_gz) and appended to the .gz files as gzip members
 // (smr_report_add_fastx_gz / _add_denovo_gz); every file inflates to what --zip host writes.
@@ -58,7 +62,7 @@ int main(int argc, char** argv) {
   smr_params base; smr_params_default(&base);
   double evalue = 1.0;
   int device = 0;
-  bool pack_device = false, split_device = false, rows_device = false, pair_device = false, otu_device = false, zip_device = false, unzip_device = false, ziprows_device = false, mates_device = false;
+  bool pack_device = false, split_device = false, rows_device = false, pair_device = false, otu_device = false, otu_mates_device = false, zip_device = false, unzip_device = false, ziprows_device = false, mates_device = false;
   bool id_given = false, cov_given = false;
   smr_report_opts ro; memset(&ro, 0, sizeof ro);
   for (int i = 1; i < argc; i++) {
@@ -91,6 +95,7 @@ int main(int argc, char** argv) {
     else if (a == "-zip" || a == "--zip") { const std::string v = val(); if (v != "host" && v != "device") die("--zip: host or device"); zip_device = v == "device"; }
     else if (a == "-ziprows" || a == "--ziprows") { const std::string v = val(); if (v != "host" && v != "device") die("--ziprows: host or device"); ziprows_device = v == "device"; }
     else if (a == "-mates" || a == "--mates") { const std::string v = val(); if (v != "host" && v != "device") die("--mates: host or device"); mates_device = v == "device"; }
+    else if (a == "-otu-mates" || a == "--otu-mates") { const std::string v = val(); if (v != "host" && v != "device") die("--otu-mates: host or device"); otu_mates_device = v == "device"; }
     else if (a == "-otu" || a == "--otu") { const std::string v = val(); if (v != "host" && v != "device") die("--otu: host or device"); otu_device = v == "device"; }
     else if (a == "-otu_map" || a == "--otu_map") ro.otu_map = 1;
     else if (a == "-de_novo_otu" || a == "--de_novo_otu") ro.denovo = 1;
@@ -118,7 +123,7 @@ int main(int argc, char** argv) {
       printf("usage: smr_align --ref DB.fasta --gumbel LAMBDA K [--idx PREFIX] [--ref ...] --reads READS.fa|fq[.gz] [--reads MATES] [--out DIR]\n"
              "       [-e EVALUE] [-num_alignments N] [-no-best] [-min_lis N] [-num_seeds N] [-edges N] [-full_search] [-F|-R]\n"
              "       [-match N -mismatch N -gap_open N -gap_ext N] [-device K] [--fastx] [--other] [--blast '0' | '1 cigar qcov qstrand'] [--sam [-SQ]]\n"
-             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [--zip host|device] [--ziprows host|device] [--unzip host|device] [--rows host|device] [--pairwise host|device] [--mates host|device] [-otu_map [-id X] [-coverage X]] [-de_novo_otu] [--otu host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
+             "       [-zip-out 0|1] [--pack host|device] [--split host|device] [--zip host|device] [--ziprows host|device] [--unzip host|device] [--rows host|device] [--pairwise host|device] [--mates host|device] [-otu_map [-id X] [-coverage X]] [-de_novo_otu] [--otu host|device] [--otu-mates host|device] [-paired_in | -paired_out] [-out2] [-sout]     (two --reads files, or one interleaved file with -paired_in / -paired_out)\n");
       return 0;
     } else die("unknown option " + a);
   }
@@ -140,6 +145,8 @@ int main(int argc, char** argv) {
   const bool idcov = ro.otu_map || ro.denovo;
   if (otu_device && !pack_device) die("--otu device writes the OTU map and aligned_denovo.* from the text the device parsed: it needs --pack device");
   if (otu_device && reads_paths.size() == 2) die("--otu device takes one reads file (single reads or interleaved mates): the members of a group of mates in two files alternate between the batches and stay with --otu host");
+  if (otu_mates_device && reads_paths.size() < 2) die("--otu-mates device writes the OTU map and aligned_denovo.* of mates in two reads files on the device: it needs two --reads files");
+  if (otu_mates_device && !pack_device) die("--otu-mates device writes the OTU map and aligned_denovo.* from the text the device parsed: it needs --pack device");
   if (dbs.empty() || reads_paths.empty()) die("--ref and --reads are required (see --help)");
   if (const char* why = smr_params_refused(&base)) die(std::string("these options are outside what libsmr_hip aligns (the reference accepts them): ") + why);
   // minimal_score (which reads count as aligned) and the e-values / bit scores of the BLAST report depend on the Gumbel parameters of the
@@ -170,7 +177,7 @@ int main(int argc, char** argv) {
   for (size_t b = 0; b < rf.size(); b++) {
     if (pack_device) {
       if (smr_batch_select(gpu, (int)b) != SMR_OK) die(smr_last_error(gpu));
-      if (smr_reads_upload_fastx_file(gpu, reads_paths[b].c_str(), slots, SMR_FASTX_VIEW | (unzip_device ? SMR_FASTX_INFLATE : 0u) | ((split_device || rows_device || pair_device || (otu_device && idcov)) ? SMR_FASTX_KEEP : 0u), &rf[b], err, sizeof err) != SMR_OK) die(err);
+      if (smr_reads_upload_fastx_file(gpu, reads_paths[b].c_str(), slots, SMR_FASTX_VIEW | (unzip_device ? SMR_FASTX_INFLATE : 0u) | ((split_device || rows_device || pair_device || ((otu_device || otu_mates_device) && idcov)) ? SMR_FASTX_KEEP : 0u), &rf[b], err, sizeof err) != SMR_OK) die(err);
     } else if (smr_reads_load_fastx_text(reads_paths[b].c_str(), 0, &rf[b], err, sizeof err) != SMR_OK) die(err);
     n += smr_reads_count(rf[b]); total_len += smr_reads_total_len(rf[b]);
     if (smr_reads_count(rf[b])) { min_len = std::min(min_len, smr_reads_min_len(rf[b])); max_len = std::max(max_len, smr_reads_max_len(rf[b])); }
@@ -210,7 +217,7 @@ int main(int argc, char** argv) {
   for (auto& d : dbs) n_parts_all += d.parts.size();
   const bool rows_dev = rows_device && (ro.sam || ro.blast_tabular);
   const bool pair_dev = pair_device && !ro.blast_tabular;            // (with tabular rows as well the host writes no pairwise text either)
-  const bool otu_dev = otu_device && idcov;
+  const bool otu_dev = (otu_device || otu_mates_device) && idcov;       // (two reads files: --otu-mates device, the calls in their form for mates)
   const bool keep_part = (rows_dev || pair_dev || idcov) && n_parts_all == 1; // one part in all: it stays resident for the pass and for smr_rows_part / smr_pairwise_part / smr_otu_part
   for (size_t k = 0; k < dbs.size(); k++) {
     smr_index_info info; smr_index_get_info(dbs[k].parts[0], &info);
@@ -289,7 +296,7 @@ int main(int argc, char** argv) {
   }
   // --rows device: the SAM / BLAST rows of every (index, part) in one call each, after all alignment (the call order of smr_idcov_part); a run of
   // more than one part uploads each part again for it.  --pairwise device: the pairwise text of the part, while it is there
-  // --otu device: the members of the map of the part from smr_otu_part, in the same visit
+  // --otu device / --otu-mates device: the members of the map of the part from smr_otu_part / smr_otu_part_mates, in the same visit
   const bool map_dev = otu_dev && ro.otu_map;
   if (rows_dev || pair_dev || map_dev) {
     std::vector<uint8_t> rb;
@@ -305,6 +312,10 @@ int main(int argc, char** argv) {
     auto pairwise_part = [&](const smr_params* p, const smr_index* ix, const smr_rows_opts& o, uint8_t* b, uint64_t cap, uint64_t* need) {
       return mates_device ? smr_pairwise_part_mates(gpu, 1, 0, p, ix, o.lambda, o.K, o.full_ref_corr, o.full_read_corr, b, cap, need)
                           : smr_pairwise_part(gpu, 0, p, ix, o.lambda, o.K, o.full_ref_corr, o.full_read_corr, b, cap, need);
+    };
+    auto otu_part = [&](const smr_params* p, const smr_index* ix, uint8_t* b, uint64_t cap, smr_otu_group* g, uint64_t gcap, uint64_t* need2, int* any) {
+      return otu_mates_device ? smr_otu_part_mates(gpu, 1, 0, p, ix, ro.min_id, ro.min_cov, b, cap, g, gcap, need2, any)
+                              : smr_otu_part(gpu, 0, p, ix, ro.min_id, ro.min_cov, b, cap, g, gcap, need2, any);
     };
     auto pairwise_part_gz = [&](const smr_params* p, const smr_index* ix, const smr_rows_opts& o, uint8_t* b, uint64_t cap, uint64_t* plain, uint64_t* need) {
       return mates_device ? smr_pairwise_part_mates_gz(gpu, 1, 0, p, ix, o.lambda, o.K, o.full_ref_corr, o.full_read_corr, b, cap, plain, need)
@@ -353,10 +364,10 @@ int main(int argc, char** argv) {
         }
         if (map_dev) {
           uint64_t need2[2] = {0, 0}; int any = 0;
-          if (smr_otu_part(gpu, 0, &p, dbs[k].parts[part], ro.min_id, ro.min_cov, nullptr, 0, nullptr, 0, need2, &any) != SMR_OK) die(smr_last_error(gpu));
+          if (otu_part(&p, dbs[k].parts[part], nullptr, 0, nullptr, 0, need2, &any) != SMR_OK) die(smr_last_error(gpu));
           if (rb.size() < need2[0] + 1) rb.resize((size_t)need2[0] + 1);
           if (gb.size() < need2[1] + 1) gb.resize((size_t)need2[1] + 1);
-          if (need2[1] && smr_otu_part(gpu, 0, &p, dbs[k].parts[part], ro.min_id, ro.min_cov, rb.data(), need2[0], gb.data(), need2[1], need2, &any) != SMR_OK) die(smr_last_error(gpu));
+          if (need2[1] && otu_part(&p, dbs[k].parts[part], rb.data(), need2[0], gb.data(), need2[1], need2, &any) != SMR_OK) die(smr_last_error(gpu));
           if (smr_report_add_otu(rep, (uint32_t)k, (uint32_t)part, rb.data(), need2[0], gb.data(), need2[1], any) != SMR_OK) die(smr_report_last_error(rep));
         }
         smr_index_unload(gpu, 0);
@@ -366,22 +377,23 @@ int main(int argc, char** argv) {
     if (rows_dev) smr_report_skip_rows(rep, 1);
     if (pair_dev) smr_report_skip_pairwise(rep, 1);
   }
-  // --otu device: aligned_denovo.* of the whole input in one call (layout 0: single reads, 1: mates interleaved)
+  // --otu device: aligned_denovo.* of the whole input in one call (layout 0: single reads, 1: mates interleaved; --otu-mates device: 2, mates in batch 1)
   const bool dn_dev = otu_dev && ro.denovo;
   if (dn_dev) {
     smr_fxsplit_opts so; memset(&so, 0, sizeof so);
-    so.layout = paired ? 1 : 0;
+    so.layout = otu_mates_device ? 2 : paired ? 1 : 0;
+    const int dn_mates = otu_mates_device ? 1 : -1;
     so.paired_in = ro.paired_in; so.paired_out = ro.paired_out; so.out2 = ro.out2; so.sout = ro.sout;
     uint64_t off[5], need = 0;
-    if (smr_batch_select(gpu, 0) != SMR_OK || smr_fastx_denovo(gpu, -1, &so, nullptr, nullptr, 0, off, &need) != SMR_OK) die(smr_last_error(gpu));
+    if (smr_batch_select(gpu, 0) != SMR_OK || smr_fastx_denovo(gpu, dn_mates, &so, nullptr, nullptr, 0, off, &need) != SMR_OK) die(smr_last_error(gpu));
     if (zip_device) {
       uint64_t gz_off[5];
       std::vector<uint8_t> gz((size_t)smr_gzip_bound(need, need / smr_gzip_chunk() + 4) + 1);
-      if (smr_fastx_denovo_gz(gpu, -1, &so, nullptr, gz.data(), gz.size(), gz_off, off, &need) != SMR_OK) die(smr_last_error(gpu));
+      if (smr_fastx_denovo_gz(gpu, dn_mates, &so, nullptr, gz.data(), gz.size(), gz_off, off, &need) != SMR_OK) die(smr_last_error(gpu));
       if (smr_report_add_denovo_gz(rep, gz.data(), gz_off) != SMR_OK) die(smr_report_last_error(rep));
     } else {
     std::vector<uint8_t> fx((size_t)need + 1);
-    if (need && smr_fastx_denovo(gpu, -1, &so, nullptr, fx.data(), need, off, &need) != SMR_OK) die(smr_last_error(gpu));
+    if (need && smr_fastx_denovo(gpu, dn_mates, &so, nullptr, fx.data(), need, off, &need) != SMR_OK) die(smr_last_error(gpu));
     if (smr_report_add_denovo(rep, fx.data(), off) != SMR_OK) die(smr_report_last_error(rep));
     }
     smr_report_skip_denovo(rep, 1);

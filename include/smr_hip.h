@@ -401,8 +401,29 @@ int smr_pairwise_times(const smr_ctx*, double ms[4]);
 typedef struct { uint32_t ref_num, n_reads; uint64_t off; } smr_otu_group;
 int smr_otu_part(smr_ctx*, int slot, const smr_params*, const smr_index* ix, double min_id, double min_cov,
                  uint8_t* bytes, uint64_t cap, smr_otu_group* groups, uint64_t groups_cap, uint64_t need[2] /* bytes, groups */, int* any_yid_ycov);
-/* HIP-event milliseconds of the last smr_otu_part: {classify, sizes and scans, sort, write, D2H} (the last two 0 for a sizes-only call) */
+/* HIP-event milliseconds of the last smr_otu_part or smr_otu_part_mates: {classify, sizes and scans, sort, write, D2H} (the last two 0 for a sizes-only call) */
 int smr_otu_times(const smr_ctx*, double ms[5]);
+/* smr_otu_part for mates that were read from two files (csrc/smr_otu_mates.hpp; INTEGRATION.md, "The OTU map of two-file mates from the
+ * device"): read i of the selected batch is mate 1 of pair i, read i of batch `mates` its mate 2, as in smr_rows_part_mates and layout 2 of
+ * smr_fastx_split.  Call it after smr_idcov_part has run for every (index, part) on BOTH batches.  The result is what the add_otu calls inside
+ * smr_report_add_pair(pair 0), (pair 1), ... leave in the report's map entries of the key: groups ascend by ref_num; inside a group the members
+ * stand in pair order, mate 1 before mate 2, then alignment-slot order; each mate is judged by its own c_yid_ycov and its id comes from its own
+ * batch's kept text.  Group text, table, rounding, forward letters and id rule are those of smr_otu_part.  *any_yid_ycov: does any read of
+ * either batch have c_yid_ycov > 0.  The arguments behind `mates` and the bytes / groups / cap / need contract are smr_otu_part's.  Two empty
+ * batches, or two batches on which the pass never ran: SMR_OK with zeros (a batch without the pass has no members).
+ * Refusals, in this precedence: (1) SMR_ERR_ARG: a NULL, a slot outside 0..63, `mates` outside 0..15 or the selected batch, thresholds outside
+ * [0, 1] or NaN; (2) every refusal of smr_otu_part for the selected batch, its device-side guards included; (3) SMR_ERR_STATE: batch `mates`
+ * holds no reads or not their text (the message names SMR_FASTX_KEEP and the batch); (4) SMR_ERR_ARG: unequal read counts, FASTA against FASTQ;
+ * (5) the device-side guards of smr_otu_part for batch `mates` (the message names the batch).  SMR_ERR_CAPACITY: 2^31 reads or more in a batch,
+ * 2^32 members or more over both.  Every message names the call; nothing is written and the context stays usable.  Changes no stored state,
+ * selects no batch, may be repeated and gives the same bytes.  Device memory, kept and grown only: that of smr_otu_part (shared with it), its
+ * per-read part (1 byte per alignment slot, 24 per read) once more for the mates' batch, 32 bytes per member of both batches. */
+int smr_otu_part_mates(smr_ctx*, int mates, int slot, const smr_params*, const smr_index* ix, double min_id, double min_cov,
+                       uint8_t* bytes, uint64_t cap, smr_otu_group* groups, uint64_t groups_cap, uint64_t need[2] /* bytes, groups */, int* any_yid_ycov);
+/* HIP-event milliseconds of the last smr_otu_part_mates: {classify, size + scan of the selected batch; classify, size + scan of batch `mates`;
+ * the merged compaction (k_otu_mates_pairs)}; all 0 when the last call was smr_otu_part.  smr_otu_times reports the last call of either form
+ * (for this one: both classify stages; both size stages, the compaction and the sizes of the text; sort; write; D2H). */
+int smr_otu_mates_times(const smr_ctx*, double ms[5]);
 /* Test seam of the sort of smr_otu_part: perm[0..n) = the STABLE permutation that orders keys[] (each below 2^key_bits, key_bits <= 32:
  * SMR_ERR_ARG otherwise) ascending -- ceil(key_bits / 8) radix passes, none for key_bits = 0. */
 int smr_otu_sort_batch(smr_ctx*, uint32_t n, const uint32_t* keys, uint32_t key_bits, uint32_t* perm);

@@ -75,7 +75,7 @@ EXPORTS = [
     "smr_gzip_lines_bound", "smr_gzip_lines_batch", "smr_rows_part_gz", "smr_pairwise_part_gz", "smr_report_add_rows_gz", "smr_report_add_pairwise_gz",
     "smr_gunzip_batch", "smr_gunzip_info", "smr_gunzip_times", "smr_gunzip_tasks",
     "smr_gzip_chunk", "smr_gzip_bound", "smr_gzip_batch", "smr_fastx_split_gz", "smr_fastx_denovo_gz", "smr_gzip_times", "smr_report_add_fastx_gz", "smr_report_add_denovo_gz",
-    "smr_otu_part", "smr_otu_times", "smr_otu_sort_batch", "smr_fastx_denovo", "smr_report_add_otu", "smr_report_skip_otu", "smr_report_add_denovo", "smr_report_skip_denovo",
+    "smr_otu_part", "smr_otu_part_mates", "smr_otu_times", "smr_otu_mates_times", "smr_otu_sort_batch", "smr_fastx_denovo", "smr_report_add_otu", "smr_report_skip_otu", "smr_report_add_denovo", "smr_report_skip_denovo",
     "smr_params_default", "smr_params_refused", "smr_index_load_files", "smr_index_build", "smr_index_build_gpu", "smr_index_write_files", "smr_index_save", "smr_index_load_flat", "smr_index_selfcheck", "smr_index_free",
     "smr_index_get_info", "smr_minimal_score", "smr_minimal_score_split", "smr_refstats_corrected_split", "smr_reads_pack", "smr_reads_load_fastx", "smr_reads_load_fastx_mt", "smr_reads_load_fastx_text", "smr_reads_is_fastq", "smr_reads_record_text", "smr_reads_free", "smr_reads_slice",
     "smr_reads_digest", "smr_reads_count", "smr_reads_total_len", "smr_reads_min_len", "smr_reads_max_len", "smr_create", "smr_device_count", "smr_destroy",
@@ -272,6 +272,10 @@ def bind(L):
     L.smr_otu_part.argtypes = [vp, i32, C.POINTER(Params), vp, C.c_double, C.c_double, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(i32)]
     L.smr_otu_times.restype = i32
     L.smr_otu_times.argtypes = [vp, C.POINTER(C.c_double)]
+    L.smr_otu_part_mates.restype = i32
+    L.smr_otu_part_mates.argtypes = [vp, i32, i32, C.POINTER(Params), vp, C.c_double, C.c_double, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(i32)]
+    L.smr_otu_mates_times.restype = i32
+    L.smr_otu_mates_times.argtypes = [vp, C.POINTER(C.c_double)]
     L.smr_otu_sort_batch.restype = i32
     L.smr_otu_sort_batch.argtypes = [vp, u32, vp, u32, vp]
     L.smr_fastx_denovo.restype = i32

@@ -21,6 +21,7 @@
 #include "smr_pairwise.hpp"
 #include "smr_mates.hpp"
 #include "smr_otu.hpp"
+#include "smr_otu_mates.hpp"
 #include "smr_gzip.hpp"
 #include "smr_gunzip.hpp"
 #include "smr_ibuild.hpp"
@@ -136,11 +137,15 @@ struct RowsScratch {
   StageClock<7, 4> clk;                   // of the last call: stats, sizes and scans, write, D2H
 };
 
-// scratch and staging of smr_otu_part (smr_otu.hpp), grow-only
+// scratch and staging of smr_otu_part (smr_otu.hpp), grow-only; smr_otu_part_mates (smr_otu_mates.hpp) keeps the per-read part of it once more
+// for the mates' batch (pass_m, meta_m, excl_m, part_m)
 struct OtuScratch {
   DevBuf<uint8_t> pass, out; DevBuf<uint2> meta; DevBuf<uint4> pairs; DevBuf<uint32_t> key[2], val[2], gstart, err;
   DevBuf<unsigned long long> excl, part, hist, wexcl, wpart, gexcl, gpart; DevBuf<OtuGroup> groups;
-  StageClock<10, 5> clk;                  // of the last call: classify, size + scans, sort, write, D2H
+  DevBuf<uint8_t> pass_m; DevBuf<uint2> meta_m; DevBuf<unsigned long long> excl_m, part_m;
+  StageClock<10, 5> clk;                  // of the last call of either form: classify, size + scans, sort, write, D2H
+  StageClock<10, 5> clk_ab[2];            // smr_otu_part_mates: classify and size of the selected batch / of the mates' batch (events 0, 1, 9)
+  double compact_ms = 0.0; bool last_mates = false;      // ... its k_otu_mates_pairs; whether the last call was of that form (smr_otu_mates_times)
 };
 
 // scratch and staging of the DEFLATE kernels (smr_gzip.hpp), grow-only

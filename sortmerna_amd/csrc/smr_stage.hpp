@@ -38,5 +38,6 @@ template <int N_EV, int N_MS> class StageClock {
   // time k := / += the milliseconds from event a to event b; as it was when HIP cannot say
   void set(int k, int a, int b) { (void)elapsed(a, b, ms_[k]); }
   void add(int k, int a, int b) { double d; if (elapsed(a, b, d)) ms_[k] += d; }
+  void acc(int k, double ms) { ms_[k] += ms; }         // (a time that another clock measured)
   void copy_to(double* out) const { for (int k = 0; k < N_MS; k++) out[k] = ms_[k]; }
 };

@@ -512,6 +512,24 @@ class Engine:
         """HIP-event ms of the last otu_part: dict(classify, sizes, sort, write, d2h)"""
         return self._times("smr_otu_times", ("classify", "sizes", "sort", "write", "d2h"))
 
+    def otu_part_mates(self, mates, slot, params, index, min_id, min_cov):
+        """smr_otu_part_mates: otu_part for mates read from two files -- read i of the selected batch is mate 1 of pair i, read i of batch
+        `mates` its mate 2; both uploaded with keep=True, idcov_part of every part run on both -> (bytes, groups, any) as otu_part gives them,
+        the members of a group in pair order, mate 1 before mate 2; any: does a read of either batch have c_yid_ycov > 0"""
+        need = (C.c_uint64 * 2)()
+        any_ = C.c_int(0)
+        args = (self.h, int(mates), slot, C.byref(params), index.h, float(min_id), float(min_cov))
+        self._chk(self.L.smr_otu_part_mates(*args, None, 0, None, 0, need, C.byref(any_)), "smr_otu_part_mates")
+        buf = np.zeros(max(need[0], 1), dtype=np.uint8)
+        groups = np.zeros(max(need[1], 1), dtype=OTU_GROUP)
+        if need[1]:
+            self._chk(self.L.smr_otu_part_mates(*args, buf.ctypes.data, need[0], groups.ctypes.data, need[1], need, C.byref(any_)), "smr_otu_part_mates")
+        return buf[:need[0]].tobytes(), groups[:need[1]], bool(any_.value)
+
+    def otu_mates_times(self):
+        """HIP-event ms of the last otu_part_mates: dict(classify_a, sizes_a, classify_b, sizes_b, compact); otu_times gives the whole call"""
+        return self._times("smr_otu_mates_times", ("classify_a", "sizes_a", "classify_b", "sizes_b", "compact"))
+
     def otu_sort_batch(self, keys, key_bits):
         """smr_otu_sort_batch (a test seam): the stable permutation that sorts keys (each below 2 ** key_bits) ascending, found by the radix
         sort of otu_part -> uint32 array"""
