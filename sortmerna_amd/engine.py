@@ -33,6 +33,32 @@ def default_params(**kw):
     return p
 
 
+U64P = C.POINTER(C.c_uint64)
+
+
+def _err_call(fn, *args):
+    """fn(*args, err, 512) of the library, for the calls that say what went wrong in a buffer of the caller's; raises SmrError with that text"""
+    err = C.create_string_buffer(512)
+    rc = getattr(capi.load(), fn)(*args, err, 512)
+    if rc != 0:
+        raise SmrError("%s: %s (rc=%d)" % (fn, err.value.decode(), rc))
+
+
+def _new_handle(cls, fn, *args):
+    """cls(handle) of the object that fn(*args, &handle, err, 512) makes"""
+    h = C.c_void_p()
+    _err_call(fn, *args, C.byref(h))
+    return cls(h)
+
+
+def _packed(items):
+    """(off, blob) of a list of byte strings (or of what bytes() takes): item i is blob[off[i]:off[i + 1]], off a uint64 array of len(items) + 1
+    entries, blob a uint8 array of the items back to back and one NUL behind them (so that an empty list has an address as well)"""
+    off = np.zeros(len(items) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(x) for x in items], dtype=np.uint64)
+    return off, np.frombuffer(b"".join(bytes(x) for x in items) + b"\0", dtype=np.uint8)
+
+
 class Index:
     """One (index, part) on the host: flattened lookup / mini-trie arena / positions CSR / reference bytes."""
 
@@ -41,73 +67,42 @@ class Index:
 
     @staticmethod
     def load_files(prefix, part, ref_fasta):
-        L = capi.load()
-        h = C.c_void_p()
-        err = C.create_string_buffer(512)
-        rc = L.smr_index_load_files(prefix.encode(), part, ref_fasta.encode(), C.byref(h), err, 512)
-        if rc != 0:
-            raise SmrError("smr_index_load_files: %s (rc=%d)" % (err.value.decode(), rc))
-        return Index(h)
+        return _new_handle(Index, "smr_index_load_files", prefix.encode(), part, ref_fasta.encode())
+
+    @staticmethod
+    def _built(fn, *args):
+        """-> list of Index: the parts that the builder fn(*args, handles, 256, &n, err, 512) leaves"""
+        arr = (C.c_void_p * 256)()
+        n = C.c_uint32()
+        _err_call(fn, *args, C.cast(arr, C.POINTER(C.c_void_p)), 256, C.byref(n))
+        return [Index(C.c_void_p(arr[i])) for i in range(n.value)]
 
     @staticmethod
     def build(ref_fasta, seed_win_len=18, max_file_size_mb=3072.0, max_pos=10000, threads=0):
         """-> list of Index (one per part)"""
-        L = capi.load()
-        cap = 256
-        arr = (C.c_void_p * cap)()
-        n = C.c_uint32()
-        err = C.create_string_buffer(512)
-        rc = L.smr_index_build(ref_fasta.encode(), seed_win_len, max_file_size_mb, max_pos, threads,
-                               C.cast(arr, C.POINTER(C.c_void_p)), cap, C.byref(n), err, 512)
-        if rc != 0:
-            raise SmrError("smr_index_build: %s (rc=%d)" % (err.value.decode(), rc))
-        return [Index(C.c_void_p(arr[i])) for i in range(n.value)]
+        return Index._built("smr_index_build", ref_fasta.encode(), seed_win_len, max_file_size_mb, max_pos, threads)
 
     @staticmethod
     def build_gpu(engine, ref_fasta, seed_win_len=18, max_file_size_mb=3072.0, max_pos=10000):
         """like build(), with the sorting / id / position / mini-trie work on the device (smr_index_build_gpu)"""
-        L = capi.load()
-        cap = 256
-        arr = (C.c_void_p * cap)()
-        n = C.c_uint32()
-        err = C.create_string_buffer(512)
-        rc = L.smr_index_build_gpu(engine.h, ref_fasta.encode(), seed_win_len, max_file_size_mb, max_pos,
-                                   C.cast(arr, C.POINTER(C.c_void_p)), cap, C.byref(n), err, 512)
-        if rc != 0:
-            raise SmrError("smr_index_build_gpu: %s (rc=%d)" % (err.value.decode(), rc))
-        return [Index(C.c_void_p(arr[i])) for i in range(n.value)]
+        return Index._built("smr_index_build_gpu", engine.h, ref_fasta.encode(), seed_win_len, max_file_size_mb, max_pos)
 
     @staticmethod
     def write_files(parts, ref_fasta, prefix):
-        L = capi.load()
         arr = (C.c_void_p * len(parts))(*[p.h for p in parts])
-        err = C.create_string_buffer(512)
-        rc = L.smr_index_write_files(C.cast(arr, C.POINTER(C.c_void_p)), len(parts), ref_fasta.encode(), prefix.encode(), err, 512)
-        if rc != 0:
-            raise SmrError("smr_index_write_files: %s (rc=%d)" % (err.value.decode(), rc))
+        _err_call("smr_index_write_files", C.cast(arr, C.POINTER(C.c_void_p)), len(parts), ref_fasta.encode(), prefix.encode())
 
     def save(self, path, stamp=0):
         """flat cache of this part's host layout (smr_index_save)"""
-        err = C.create_string_buffer(512)
-        rc = capi.load().smr_index_save(self.h, path.encode(), stamp, err, 512)
-        if rc != 0:
-            raise SmrError("smr_index_save: %s (rc=%d)" % (err.value.decode(), rc))
+        _err_call("smr_index_save", self.h, path.encode(), stamp)
 
     @staticmethod
     def load_flat(path, stamp=0):
-        h = C.c_void_p()
-        err = C.create_string_buffer(512)
-        rc = capi.load().smr_index_load_flat(path.encode(), stamp, C.byref(h), err, 512)
-        if rc != 0:
-            raise SmrError("smr_index_load_flat: %s (rc=%d)" % (err.value.decode(), rc))
-        return Index(h)
+        return _new_handle(Index, "smr_index_load_flat", path.encode(), stamp)
 
     def selfcheck(self):
         """the pigeonhole device layout holds the same entries, with their DFS ranks, as the reference-shaped one"""
-        err = C.create_string_buffer(512)
-        rc = capi.load().smr_index_selfcheck(self.h, err, 512)
-        if rc != 0:
-            raise SmrError("smr_index_selfcheck: %s (rc=%d)" % (err.value.decode(), rc))
+        _err_call("smr_index_selfcheck", self.h)
 
     def info(self):
         i = capi.IndexInfo()
@@ -127,48 +122,26 @@ class Reads:
 
     @staticmethod
     def from_seqs(seqs):
-        L = capi.load()
-        blob = "".join(seqs).encode("latin-1")
-        offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
-        if seqs:
-            offs[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+        offs, blob = _packed([s.encode("latin-1") for s in seqs])
         h = C.c_void_p()
-        rc = L.smr_reads_pack(blob, offs.ctypes.data, len(seqs), C.byref(h))
+        rc = capi.load().smr_reads_pack(blob.ctypes.data_as(C.c_char_p), offs.ctypes.data, len(seqs), C.byref(h))
         if rc != 0:
             raise SmrError("smr_reads_pack rc=%d" % rc)
         return Reads(h)
 
     @staticmethod
     def from_fastx(path, first=0, count=0):
-        L = capi.load()
-        h = C.c_void_p()
-        err = C.create_string_buffer(512)
-        rc = L.smr_reads_load_fastx(path.encode(), first, count, C.byref(h), err, 512)
-        if rc != 0:
-            raise SmrError("smr_reads_load_fastx: %s (rc=%d)" % (err.value.decode(), rc))
-        return Reads(h)
+        return _new_handle(Reads, "smr_reads_load_fastx", path.encode(), first, count)
 
     @staticmethod
     def from_fastx_mt(path, threads=0):
         """whole file, parsed and packed by `threads` threads (0 = all cores)"""
-        L = capi.load()
-        h = C.c_void_p()
-        err = C.create_string_buffer(512)
-        rc = L.smr_reads_load_fastx_mt(path.encode(), threads, C.byref(h), err, 512)
-        if rc != 0:
-            raise SmrError("smr_reads_load_fastx_mt: %s (rc=%d)" % (err.value.decode(), rc))
-        return Reads(h)
+        return _new_handle(Reads, "smr_reads_load_fastx_mt", path.encode(), threads)
 
     @staticmethod
     def from_fastx_text(path, threads=0):
         """from_fastx_mt + the file text kept, so that record_text(i) returns (header line, letters, quality) for the report writers"""
-        L = capi.load()
-        h = C.c_void_p()
-        err = C.create_string_buffer(512)
-        rc = L.smr_reads_load_fastx_text(path.encode(), threads, C.byref(h), err, 512)
-        if rc != 0:
-            raise SmrError("smr_reads_load_fastx_text: %s (rc=%d)" % (err.value.decode(), rc))
-        return Reads(h)
+        return _new_handle(Reads, "smr_reads_load_fastx_text", path.encode(), threads)
 
     def slice(self, first, count):
         """records [first, first+count) as a batch of their own (the read shard of one rank / one pipeline chunk)"""
@@ -226,13 +199,9 @@ def minimal_score(lam, K, info, all_reads_count, all_reads_len, evalue=1.0, full
 
 def pigeonhole_layout(index):
     """(pg uint32[], root3 uint32[]) of a host index as the host transform builds it (smr_index_pigeonhole: a test seam; views into the index)"""
-    L = capi.load()
     pg, r3 = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)()
     npg, nr3 = C.c_uint64(), C.c_uint64()
-    err = C.create_string_buffer(512)
-    rc = L.smr_index_pigeonhole(index.h, C.byref(pg), C.byref(npg), C.byref(r3), C.byref(nr3), err, 512)
-    if rc != 0:
-        raise SmrError("smr_index_pigeonhole: %s (rc=%d)" % (err.value.decode(), rc))
+    _err_call("smr_index_pigeonhole", index.h, C.byref(pg), C.byref(npg), C.byref(r3), C.byref(nr3))
     return np.ctypeslib.as_array(pg, shape=(npg.value,)), np.ctypeslib.as_array(r3, shape=(nr3.value,))
 
 
@@ -248,12 +217,8 @@ class Engine:
 
     def __init__(self, device=0):
         self.L = capi.load()
-        h = C.c_void_p()
-        err = C.create_string_buffer(512)
-        rc = self.L.smr_create(device, C.byref(h), err, 512)
-        if rc != 0:
-            raise SmrError("smr_create: %s (rc=%d)" % (err.value.decode(), rc))
-        self.h = h
+        self.h = C.c_void_p()
+        _err_call("smr_create", device, C.byref(self.h))
         self.n_reads = 0
         self._batch_n = {}
         self._cur = 0
@@ -261,6 +226,24 @@ class Engine:
     def _chk(self, rc, what):
         if rc != 0:
             raise SmrError("%s: %s (rc=%d)" % (what, self.L.smr_last_error(self.h).decode(), rc))
+
+    def _fill(self, what, call, kinds=(np.uint8,), always=False):
+        """The size-then-fill protocol of smr_hip.h for the call named `what` (as its SmrError names it).  `call(need, (buf, cap), ...)` makes it,
+        with one (buffer, capacity) pair per entry of `kinds` -- (None, 0) for the sizes only -- and `need` the uint64 array, one entry per pair,
+        that the library leaves the sizes in.  The call is made for the sizes, then once more with zeroed arrays of those sizes (of one element
+        at least, so that each has an address) unless the last size is 0; -> the arrays, cut to the sizes (the array itself for one kind).
+        What the callers differ in:
+          * gunzip_batch, gunzip_tasks and seed_hits make the second call even for size 0 (always=True);
+          * otu_part and otu_part_mates have two buffers, the text and the groups, and the number of groups decides whether to fetch;
+          * export_state hands out the array as it is, so a batch without records gives a zero-length array;
+          * gzip_batch and gzip_lines_batch do not come here: with a bound for the buffer their one call is enough (_gzip)."""
+        need = (C.c_uint64 * len(kinds))()
+        self._chk(call(need, *[(None, 0)] * len(kinds)), what)
+        bufs = [np.zeros(max(n, 1), dtype=k) for n, k in zip(need, kinds)]
+        if always or need[-1]:
+            self._chk(call(need, *[(b.ctypes.data, n) for b, n in zip(bufs, list(need))]), what)
+        out = [b[:n] for b, n in zip(bufs, need)]
+        return out[0] if len(out) == 1 else out
 
     def upload_index(self, index, slot=0):
         self._chk(self.L.smr_index_upload(self.h, index.h, slot), "smr_index_upload")
@@ -300,11 +283,8 @@ class Engine:
     def ssw_batch(self, reads, refs, match=2, mismatch=-3, score_N=-3, gap_open=5, gap_ext=2, filters=0, mode=1):
         """reads / refs: lists of byte strings in the 0..4 alphabet; -> int32 array (n, 5): score1, ref_begin1, ref_end1, read_begin1, read_end1
         (ssw_align with flag 2, without the CIGAR), computed by the 32-bit (mode 0) or the packed (mode 1) SW kernel; mode 5: through the long-read strips"""
-        import numpy as np
         n = len(reads)
-        ro = np.zeros(n + 1, dtype=np.uint64); fo = np.zeros(n + 1, dtype=np.uint64)
-        ro[1:] = np.cumsum([len(x) for x in reads]); fo[1:] = np.cumsum([len(x) for x in refs])
-        rb = np.frombuffer(b"".join(reads) + b"\0", dtype=np.uint8).copy(); fb = np.frombuffer(b"".join(refs) + b"\0", dtype=np.uint8).copy()
+        (ro, rb), (fo, fb) = _packed(reads), _packed(refs)
         out = np.zeros((n, 5), dtype=np.int32)
         self._chk(self.L.smr_ssw_batch(self.h, n, rb.ctypes.data, ro.ctypes.data, fb.ctypes.data, fo.ctypes.data, match, mismatch, score_N,
                                        gap_open, gap_ext, filters, mode, out.ctypes.data), "smr_ssw_batch")
@@ -372,9 +352,7 @@ class Engine:
         """reads / refs: the aligned spans (byte strings in the 0..4 alphabet), scores: their score1; -> list of u32 CIGAR arrays (len << 4 | op),
         what the reference's banded_sw returns for each triple (the traceback kernels behind smr_traceback)"""
         n = len(reads)
-        ro = np.zeros(n + 1, dtype=np.uint64); fo = np.zeros(n + 1, dtype=np.uint64)
-        ro[1:] = np.cumsum([len(x) for x in reads]); fo[1:] = np.cumsum([len(x) for x in refs])
-        rb = np.frombuffer(b"".join(reads) + b"\0", dtype=np.uint8).copy(); fb = np.frombuffer(b"".join(refs) + b"\0", dtype=np.uint8).copy()
+        (ro, rb), (fo, fb) = _packed(reads), _packed(refs)
         sc = np.asarray(scores, dtype=np.uint16)
         off = np.zeros(n + 1, dtype=np.uint64)
         cap = int(ro[-1] + fo[-1]) + 4 * n + 16
@@ -441,17 +419,7 @@ class Engine:
         """smr_fastx_split: the aligned.* / other.* FASTX streams of the selected batch (uploaded with keep=True), written on the device -> a list
         of eight bytes objects, aligned[0..3] then other[0..3].  layout 0: single reads; 1: mates interleaved; 2: the mates are the reads of batch
         `mates`.  hit: one truth value per read (the selected batch's, then the mates') used instead of the batch's own is_hit."""
-        o = capi.FxSplitOpts(int(layout), int(bool(paired_in)), int(bool(paired_out)), int(bool(out2)), int(bool(sout)), int(bool(aligned)), int(bool(other)))
-        hb = None if hit is None else (C.c_uint8 * max(len(hit), 1))(*[1 if x else 0 for x in hit])
-        m = -1 if mates is None else int(mates)
-        off = (C.c_uint64 * 9)()
-        need = C.c_uint64(0)
-        self._chk(self.L.smr_fastx_split(self.h, m, C.byref(o), hb, None, 0, off, C.byref(need)), "smr_fastx_split")
-        buf = (C.c_uint8 * max(need.value, 1))()
-        if need.value:
-            self._chk(self.L.smr_fastx_split(self.h, m, C.byref(o), hb, buf, need.value, off, C.byref(need)), "smr_fastx_split")
-        raw = bytes(buf)
-        return [raw[off[k]:off[k + 1]] for k in range(8)]
+        return self._fx("smr_fastx_split", 8, self._fx_opts(layout, paired_in, paired_out, out2, sout, aligned, other), hit, mates)[0]
 
     def fastx_split_times(self):
         """HIP-event ms of the last fastx_split: dict(measure, scans, copy, d2h)"""
@@ -461,18 +429,7 @@ class Engine:
         """smr_rows_part: the rows of aligned.sam and of the BLAST tabular report of the selected batch (uploaded with keep=True) for the
         (index, part) of `params`, resident in `slot`, written on the device -> (sam_bytes, blast_bytes).  cols: "cigar", "qcov", "qstrand",
         space separated or as a list, in output order; lam, K, full_ref, full_read: what Report.set_db takes for that index."""
-        o = capi.RowsOpts()
-        o.want_sam, o.want_blast = int(bool(sam)), int(bool(blast))
-        o.blast_cols = (cols if isinstance(cols, str) else " ".join(cols)).encode()
-        o.lam, o.K, o.full_ref_corr, o.full_read_corr = float(lam), float(K), int(full_ref), int(full_read)
-        off = (C.c_uint64 * 3)()
-        need = C.c_uint64(0)
-        self._chk(self.L.smr_rows_part(self.h, slot, C.byref(params), index.h, C.byref(o), None, 0, off, C.byref(need)), "smr_rows_part")
-        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
-        if need.value:
-            self._chk(self.L.smr_rows_part(self.h, slot, C.byref(params), index.h, C.byref(o), buf.ctypes.data, need.value, off, C.byref(need)), "smr_rows_part")
-        raw = buf.tobytes()
-        return raw[off[0]:off[1]], raw[off[1]:off[2]]
+        return self._rows("smr_rows_part", None, slot, params, index, sam, blast, cols, lam, K, full_ref, full_read)
 
     def rows_times(self):
         """HIP-event ms of the last rows_part: dict(stats, sizes, write, d2h)"""
@@ -481,13 +438,7 @@ class Engine:
     def pairwise_part(self, slot, params, index, lam=0.0, K=0.0, full_ref=0, full_read=0):
         """smr_pairwise_part: the BLAST-like pairwise text (-blast 0) of the selected batch (uploaded with keep=True) for the (index, part) of
         `params`, resident in `slot`, written on the device -> bytes.  lam, K, full_ref, full_read: what Report.set_db takes for that index."""
-        need = C.c_uint64(0)
-        args = (self.h, slot, C.byref(params), index.h, float(lam), float(K), int(full_ref), int(full_read))
-        self._chk(self.L.smr_pairwise_part(*args, None, 0, C.byref(need)), "smr_pairwise_part")
-        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
-        if need.value:
-            self._chk(self.L.smr_pairwise_part(*args, buf.ctypes.data, need.value, C.byref(need)), "smr_pairwise_part")
-        return buf[:need.value].tobytes()
+        return self._pairwise("smr_pairwise_part", None, slot, params, index, lam, K, full_ref, full_read)
 
     def pairwise_times(self):
         """HIP-event ms of the last pairwise_part: dict(stats, sizes, write, d2h)"""
@@ -498,15 +449,7 @@ class Engine:
         (index, part) of `params`, resident in `slot`, grouped and written on the device -> (bytes, groups, any): groups is a structured array
         (ref_num, n_reads, off), ascending in ref_num; the text of group g is bytes[off[g]:off[g + 1]] (the last: to the end), its ids joined
         by tabs; any: does a read of the batch have c_yid_ycov > 0 (is there a map file at all)"""
-        need = (C.c_uint64 * 2)()
-        any_ = C.c_int(0)
-        args = (self.h, slot, C.byref(params), index.h, float(min_id), float(min_cov))
-        self._chk(self.L.smr_otu_part(*args, None, 0, None, 0, need, C.byref(any_)), "smr_otu_part")
-        buf = np.zeros(max(need[0], 1), dtype=np.uint8)
-        groups = np.zeros(max(need[1], 1), dtype=OTU_GROUP)
-        if need[1]:
-            self._chk(self.L.smr_otu_part(*args, buf.ctypes.data, need[0], groups.ctypes.data, need[1], need, C.byref(any_)), "smr_otu_part")
-        return buf[:need[0]].tobytes(), groups[:need[1]], bool(any_.value)
+        return self._otu("smr_otu_part", None, slot, params, index, min_id, min_cov)
 
     def otu_times(self):
         """HIP-event ms of the last otu_part: dict(classify, sizes, sort, write, d2h)"""
@@ -516,15 +459,7 @@ class Engine:
         """smr_otu_part_mates: otu_part for mates read from two files -- read i of the selected batch is mate 1 of pair i, read i of batch
         `mates` its mate 2; both uploaded with keep=True, idcov_part of every part run on both -> (bytes, groups, any) as otu_part gives them,
         the members of a group in pair order, mate 1 before mate 2; any: does a read of either batch have c_yid_ycov > 0"""
-        need = (C.c_uint64 * 2)()
-        any_ = C.c_int(0)
-        args = (self.h, int(mates), slot, C.byref(params), index.h, float(min_id), float(min_cov))
-        self._chk(self.L.smr_otu_part_mates(*args, None, 0, None, 0, need, C.byref(any_)), "smr_otu_part_mates")
-        buf = np.zeros(max(need[0], 1), dtype=np.uint8)
-        groups = np.zeros(max(need[1], 1), dtype=OTU_GROUP)
-        if need[1]:
-            self._chk(self.L.smr_otu_part_mates(*args, buf.ctypes.data, need[0], groups.ctypes.data, need[1], need, C.byref(any_)), "smr_otu_part_mates")
-        return buf[:need[0]].tobytes(), groups[:need[1]], bool(any_.value)
+        return self._otu("smr_otu_part_mates", int(mates), slot, params, index, min_id, min_cov)
 
     def otu_mates_times(self):
         """HIP-event ms of the last otu_part_mates: dict(classify_a, sizes_a, classify_b, sizes_b, compact); otu_times gives the whole call"""
@@ -544,24 +479,36 @@ class Engine:
         if isinstance(opts, capi.FxSplitOpts):
             return opts
         d = dict(opts or {}, **kw)
-        return capi.FxSplitOpts(int(d.get("layout", 0)), int(bool(d.get("paired_in"))), int(bool(d.get("paired_out"))), int(bool(d.get("out2"))), int(bool(d.get("sout"))), 1, 0)
+        return Engine._fx_opts(d.get("layout", 0), d.get("paired_in"), d.get("paired_out"), d.get("out2"), d.get("sout"), 1, 0)
+
+    @staticmethod
+    def _fx_opts(layout, paired_in, paired_out, out2, sout, aligned, other):
+        return capi.FxSplitOpts(int(layout), int(bool(paired_in)), int(bool(paired_out)), int(bool(out2)), int(bool(sout)), int(bool(aligned)), int(bool(other)))
+
+    def _fx(self, fn, n, o, flags, mates):
+        """the n FASTX streams of smr_fastx_split / smr_fastx_denovo or of their _gz forms (fn) -> (a list of n bytes objects, the n + 1 offsets
+        of the plain streams).  flags: one truth value per read to use instead of the batch's own, or None"""
+        fb = None if flags is None else (C.c_uint8 * max(len(flags), 1))(*[1 if x else 0 for x in flags])
+        return self._streams(fn, n, (self.h, -1 if mates is None else int(mates), C.byref(o), fb))
+
+    def _streams(self, fn, n, head):
+        """n streams in one buffer from the writer fn(*head, buf, cap, off, need) -- a _gz form: fn(*head, buf, cap, gz_off, plain_off, need) --
+        -> (a list of n bytes objects, the n + 1 offsets the plain streams have)"""
+        off, gz_off = (C.c_uint64 * (n + 1))(), (C.c_uint64 * (n + 1))()
+        tail, cut = ((gz_off, off), gz_off) if fn.endswith("_gz") else ((off,), off)
+        raw = self._fill(fn, lambda need, b: getattr(self.L, fn)(*head, *b, *tail, need)).tobytes()
+        return [raw[cut[k]:cut[k + 1]] for k in range(n)], [int(x) for x in off]
+
+    def _part_head(self, mates, slot, params, index):
+        """the leading arguments of a writer of one (index, part): the plain call's, or with `mates` (a batch number) those of its _mates form"""
+        return (self.h,) + (() if mates is None else (mates,)) + (slot, C.byref(params), index.h)
 
     def fastx_denovo(self, opts=None, mates=-1, dn=None, **kw):
         """smr_fastx_denovo: the aligned_denovo.* FASTX streams of the selected batch (uploaded with keep=True), written on the device -> a list
         of four bytes objects.  opts: a capi.FxSplitOpts, or a dict / keywords out of layout, paired_in, paired_out, out2, sout as fastx_split
         takes them (want_aligned / want_other are ignored); mates: the batch of the mates under layout 2, else -1.  dn: one truth value per
         read (the selected batch's, then the mates') used instead of the counters idcov_part left"""
-        o = self._denovo_opts(opts, kw)
-        db = None if dn is None else (C.c_uint8 * max(len(dn), 1))(*[1 if x else 0 for x in dn])
-        m = -1 if mates is None else int(mates)
-        off = (C.c_uint64 * 5)()
-        need = C.c_uint64(0)
-        self._chk(self.L.smr_fastx_denovo(self.h, m, C.byref(o), db, None, 0, off, C.byref(need)), "smr_fastx_denovo")
-        buf = (C.c_uint8 * max(need.value, 1))()
-        if need.value:
-            self._chk(self.L.smr_fastx_denovo(self.h, m, C.byref(o), db, buf, need.value, off, C.byref(need)), "smr_fastx_denovo")
-        raw = bytes(buf)
-        return [raw[off[k]:off[k + 1]] for k in range(4)]
+        return self._fx("smr_fastx_denovo", 4, self._denovo_opts(opts, kw), dn, mates)[0]
 
     def gzip_chunk(self):
         """smr_gzip_chunk: plain bytes per gzip member of the device compressor"""
@@ -574,16 +521,17 @@ class Engine:
     def gzip_batch(self, streams):
         """smr_gzip_batch: every bytes object of `streams` cut into chunks of gzip_chunk() bytes and each chunk made a gzip member by the
         DEFLATE kernels -> a list of bytes objects, the members of each stream back to back (b"" for an empty one)"""
+        chunk = self.gzip_chunk()
+        return self._gzip("smr_gzip_batch", streams, self.gzip_bound(sum(len(x) for x in streams), sum((len(x) + chunk - 1) // chunk for x in streams)))
+
+    def _gzip(self, fn, streams, cap):
+        """smr_gzip_batch / smr_gzip_lines_batch (fn) over a list of bytes objects: one call into a buffer of `cap` bytes, their bound"""
         n = len(streams)
-        off = (C.c_uint64 * (n + 1))()
-        for k in range(n):
-            off[k + 1] = off[k] + len(streams[k])
-        plain = np.frombuffer(b"".join(streams) or b"\0", dtype=np.uint8)
+        off, plain = _packed(streams)
         gz_off = (C.c_uint64 * (n + 1))()
         need = C.c_uint64(0)
-        cap = self.gzip_bound(off[n], sum((len(x) + self.gzip_chunk() - 1) // self.gzip_chunk() for x in streams))
         buf = np.zeros(max(cap, 1), dtype=np.uint8)
-        self._chk(self.L.smr_gzip_batch(self.h, plain.ctypes.data, off, n, buf.ctypes.data, cap, gz_off, C.byref(need)), "smr_gzip_batch")
+        self._chk(getattr(self.L, fn)(self.h, plain.ctypes.data, off.ctypes.data_as(U64P), n, buf.ctypes.data, cap, gz_off, C.byref(need)), fn)
         raw = buf[:need.value].tobytes()
         return [raw[gz_off[k]:gz_off[k + 1]] for k in range(n)]
 
@@ -592,11 +540,7 @@ class Engine:
         least distance of two tasks in compressed bytes (0: the default, 1: a task at every candidate).  What the device does not settle is
         inflated by zlib inside the call (gunzip_info says which); a file zlib refuses raises SmrError."""
         gz = np.frombuffer(bytes(blob) or b"\0", dtype=np.uint8)
-        need = C.c_uint64(0)
-        self._chk(self.L.smr_gunzip_batch(self.h, gz.ctypes.data, len(blob), int(grain), None, 0, C.byref(need)), "smr_gunzip_batch")
-        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
-        self._chk(self.L.smr_gunzip_batch(self.h, gz.ctypes.data, len(blob), int(grain), buf.ctypes.data, need.value, C.byref(need)), "smr_gunzip_batch")
-        return buf[:need.value].tobytes()
+        return self._fill("smr_gunzip_batch", lambda need, b: self.L.smr_gunzip_batch(self.h, gz.ctypes.data, len(blob), int(grain), *b, need), always=True).tobytes()
 
     def gunzip_info(self):
         """smr_gunzip_info of the last gunzip_batch / inflating upload_fastx: dict(path "device" | "host", why (a word of GUNZIP_WHY), rounds,
@@ -613,39 +557,21 @@ class Engine:
 
     def gunzip_tasks(self):
         """smr_gunzip_tasks (a test seam): the confirmed tasks of the last call on the device path -> [(start bit, at a member header, made by the stitch)]"""
-        n = C.c_uint64(0)
-        self._chk(self.L.smr_gunzip_tasks(self.h, None, 0, C.byref(n)), "smr_gunzip_tasks")
-        buf = (C.c_uint64 * max(n.value, 1))()
-        self._chk(self.L.smr_gunzip_tasks(self.h, buf, n.value, C.byref(n)), "smr_gunzip_tasks")
-        return [(int(x) >> 2, bool(x & 1), bool(x & 2)) for x in buf[:n.value]]
+        tasks = self._fill("smr_gunzip_tasks", lambda n, b: self.L.smr_gunzip_tasks(self.h, C.cast(b[0], U64P), b[1], n), kinds=(np.uint64,), always=True)
+        return [(int(x) >> 2, bool(x & 1), bool(x & 2)) for x in tasks.tolist()]
 
     def gzip_times(self):
         """HIP-event ms of the last gzip_batch / fastx_split_gz / fastx_denovo_gz: dict(match, codes, encode, compact, d2h)"""
         return self._times("smr_gzip_times", ("match", "codes", "encode", "compact", "d2h"))
 
-    def _fx_gz(self, fn, n, o, flags, mates):
-        fb = None if flags is None else (C.c_uint8 * max(len(flags), 1))(*[1 if x else 0 for x in flags])
-        m = -1 if mates is None else int(mates)
-        gz_off, plain_off = (C.c_uint64 * (n + 1))(), (C.c_uint64 * (n + 1))()
-        need = C.c_uint64(0)
-        call = getattr(self.L, fn)
-        self._chk(call(self.h, m, C.byref(o), fb, None, 0, gz_off, plain_off, C.byref(need)), fn)
-        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
-        if need.value:
-            self._chk(call(self.h, m, C.byref(o), fb, buf.ctypes.data, need.value, gz_off, plain_off, C.byref(need)), fn)
-        raw = buf.tobytes()
-        return [raw[gz_off[k]:gz_off[k + 1]] for k in range(n)], [int(x) for x in plain_off]
-
     def fastx_split_gz(self, layout=0, mates=None, paired_in=False, paired_out=False, out2=False, sout=False, aligned=True, other=True, hit=None):
         """smr_fastx_split_gz: the eight streams of fastx_split, compressed on the device -> (a list of eight bytes objects, each the gzip
         members of its stream or b"", and the nine offsets fastx_split's streams would have)"""
-        o = capi.FxSplitOpts(int(layout), int(bool(paired_in)), int(bool(paired_out)), int(bool(out2)), int(bool(sout)), int(bool(aligned)), int(bool(other)))
-        return self._fx_gz("smr_fastx_split_gz", 8, o, hit, mates)
+        return self._fx("smr_fastx_split_gz", 8, self._fx_opts(layout, paired_in, paired_out, out2, sout, aligned, other), hit, mates)
 
     def fastx_denovo_gz(self, opts=None, mates=-1, dn=None, **kw):
         """smr_fastx_denovo_gz: the four streams of fastx_denovo, compressed on the device -> (four bytes objects, the five plain offsets)"""
-        o = self._denovo_opts(opts, kw)
-        return self._fx_gz("smr_fastx_denovo_gz", 4, o, dn, mates)
+        return self._fx("smr_fastx_denovo_gz", 4, self._denovo_opts(opts, kw), dn, mates)
 
     def gzip_lines_bound(self, plain_bytes, n_streams):
         """smr_gzip_lines_bound: no output of gzip_lines_batch / rows_part_gz / pairwise_part_gz for plain_bytes in n_streams streams is larger"""
@@ -654,47 +580,18 @@ class Engine:
     def gzip_lines_batch(self, streams):
         """smr_gzip_lines_batch: gzip_batch with the members cut at line ends -- nominal cuts every 48 KiB, each moved back to behind the last
         newline of the 16 KiB in front of it -> a list of bytes objects, the members of each stream back to back (b"" for an empty one)"""
-        n = len(streams)
-        off = (C.c_uint64 * (n + 1))()
-        for k in range(n):
-            off[k + 1] = off[k] + len(streams[k])
-        plain = np.frombuffer(b"".join(streams) or b"\0", dtype=np.uint8)
-        gz_off = (C.c_uint64 * (n + 1))()
-        need = C.c_uint64(0)
-        cap = self.gzip_lines_bound(off[n], n)
-        buf = np.zeros(max(cap, 1), dtype=np.uint8)
-        self._chk(self.L.smr_gzip_lines_batch(self.h, plain.ctypes.data, off, n, buf.ctypes.data, cap, gz_off, C.byref(need)), "smr_gzip_lines_batch")
-        raw = buf[:need.value].tobytes()
-        return [raw[gz_off[k]:gz_off[k + 1]] for k in range(n)]
+        return self._gzip("smr_gzip_lines_batch", streams, self.gzip_lines_bound(sum(len(x) for x in streams), len(streams)))
 
     def rows_part_gz(self, slot, params, index, sam=True, blast=False, cols="", lam=0.0, K=0.0, full_ref=0, full_read=0):
         """smr_rows_part_gz: the two streams of rows_part, compressed on the device into gzip members that end at line ends ->
         (sam_gz, blast_gz, plain_off): the members of each stream (b"" for one that is not wanted or holds no row) and the three offsets
         rows_part's streams would have.  Arguments as rows_part."""
-        o = capi.RowsOpts()
-        o.want_sam, o.want_blast = int(bool(sam)), int(bool(blast))
-        o.blast_cols = (cols if isinstance(cols, str) else " ".join(cols)).encode()
-        o.lam, o.K, o.full_ref_corr, o.full_read_corr = float(lam), float(K), int(full_ref), int(full_read)
-        gz_off, plain_off = (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
-        need = C.c_uint64(0)
-        args = (self.h, slot, C.byref(params), index.h, C.byref(o))
-        self._chk(self.L.smr_rows_part_gz(*args, None, 0, gz_off, plain_off, C.byref(need)), "smr_rows_part_gz")
-        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
-        if need.value:
-            self._chk(self.L.smr_rows_part_gz(*args, buf.ctypes.data, need.value, gz_off, plain_off, C.byref(need)), "smr_rows_part_gz")
-        raw = buf.tobytes()
-        return raw[gz_off[0]:gz_off[1]], raw[gz_off[1]:gz_off[2]], [int(x) for x in plain_off]
+        return self._rows("smr_rows_part_gz", None, slot, params, index, sam, blast, cols, lam, K, full_ref, full_read)
 
     def pairwise_part_gz(self, slot, params, index, lam=0.0, K=0.0, full_ref=0, full_read=0):
         """smr_pairwise_part_gz: the text of pairwise_part, compressed on the device into gzip members that end at line ends ->
         (gz, plain_bytes): the members and the size pairwise_part's text would have.  Arguments as pairwise_part."""
-        need, plain = C.c_uint64(0), C.c_uint64(0)
-        args = (self.h, slot, C.byref(params), index.h, float(lam), float(K), int(full_ref), int(full_read))
-        self._chk(self.L.smr_pairwise_part_gz(*args, None, 0, C.byref(plain), C.byref(need)), "smr_pairwise_part_gz")
-        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
-        if need.value:
-            self._chk(self.L.smr_pairwise_part_gz(*args, buf.ctypes.data, need.value, C.byref(plain), C.byref(need)), "smr_pairwise_part_gz")
-        return buf[:need.value].tobytes(), int(plain.value)
+        return self._pairwise("smr_pairwise_part_gz", None, slot, params, index, lam, K, full_ref, full_read)
 
     @staticmethod
     def _rows_opts(sam, blast, cols, lam, K, full_ref, full_read):
@@ -704,71 +601,53 @@ class Engine:
         o.lam, o.K, o.full_ref_corr, o.full_read_corr = float(lam), float(K), int(full_ref), int(full_read)
         return o
 
+    def _rows(self, fn, mates, slot, params, index, *opts):
+        """smr_rows_part, its _mates and _gz forms (fn; mates: the batch of the mates, or None) -> (sam, blast), a _gz form: (sam, blast, plain offsets)"""
+        o = self._rows_opts(*opts)
+        (sam, blast), plain_off = self._streams(fn, 2, self._part_head(mates, slot, params, index) + (C.byref(o),))
+        return (sam, blast, plain_off) if fn.endswith("_gz") else (sam, blast)
+
+    def _pairwise(self, fn, mates, slot, params, index, lam, K, full_ref, full_read):
+        """smr_pairwise_part, its _mates and _gz forms (fn; mates as for _rows) -> the text, a _gz form: (the gzip members, the size of the plain text)"""
+        plain = C.c_uint64(0)
+        head = self._part_head(mates, slot, params, index) + (float(lam), float(K), int(full_ref), int(full_read))
+        tail = (C.byref(plain),) if fn.endswith("_gz") else ()
+        text = self._fill(fn, lambda need, b: getattr(self.L, fn)(*head, *b, *tail, need)).tobytes()
+        return (text, int(plain.value)) if tail else text
+
+    def _otu(self, fn, mates, slot, params, index, min_id, min_cov):
+        """smr_otu_part or its _mates form (fn; mates as for _rows) -> (bytes, groups, any)"""
+        any_ = C.c_int(0)
+        head = self._part_head(mates, slot, params, index) + (float(min_id), float(min_cov))
+        text, groups = self._fill(fn, lambda need, b, g: getattr(self.L, fn)(*head, *b, *g, need, C.byref(any_)), kinds=(np.uint8, OTU_GROUP))
+        return text.tobytes(), groups, bool(any_.value)
+
     def rows_part_mates(self, mates, slot, params, index, sam=True, blast=False, cols="", lam=0.0, K=0.0, full_ref=0, full_read=0):
         """smr_rows_part_mates: rows_part for mates in two reads files -- read i of the selected batch and read i of batch `mates` (both uploaded
         with keep=True) -- in the order in which Report.add_pair appends them -> (sam_bytes, blast_bytes).  Other arguments as rows_part."""
-        o = self._rows_opts(sam, blast, cols, lam, K, full_ref, full_read)
-        off = (C.c_uint64 * 3)()
-        need = C.c_uint64(0)
-        args = (self.h, int(mates), slot, C.byref(params), index.h, C.byref(o))
-        self._chk(self.L.smr_rows_part_mates(*args, None, 0, off, C.byref(need)), "smr_rows_part_mates")
-        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
-        if need.value:
-            self._chk(self.L.smr_rows_part_mates(*args, buf.ctypes.data, need.value, off, C.byref(need)), "smr_rows_part_mates")
-        raw = buf.tobytes()
-        return raw[off[0]:off[1]], raw[off[1]:off[2]]
+        return self._rows("smr_rows_part_mates", int(mates), slot, params, index, sam, blast, cols, lam, K, full_ref, full_read)
 
     def pairwise_part_mates(self, mates, slot, params, index, lam=0.0, K=0.0, full_ref=0, full_read=0):
         """smr_pairwise_part_mates: pairwise_part for mates in two reads files (the selected batch and batch `mates`), in the order of
         Report.add_pair -> bytes.  Other arguments as pairwise_part."""
-        need = C.c_uint64(0)
-        args = (self.h, int(mates), slot, C.byref(params), index.h, float(lam), float(K), int(full_ref), int(full_read))
-        self._chk(self.L.smr_pairwise_part_mates(*args, None, 0, C.byref(need)), "smr_pairwise_part_mates")
-        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
-        if need.value:
-            self._chk(self.L.smr_pairwise_part_mates(*args, buf.ctypes.data, need.value, C.byref(need)), "smr_pairwise_part_mates")
-        return buf[:need.value].tobytes()
+        return self._pairwise("smr_pairwise_part_mates", int(mates), slot, params, index, lam, K, full_ref, full_read)
 
     def rows_part_mates_gz(self, mates, slot, params, index, sam=True, blast=False, cols="", lam=0.0, K=0.0, full_ref=0, full_read=0):
         """smr_rows_part_mates_gz: the two streams of rows_part_mates, compressed on the device -> (sam_gz, blast_gz, plain_off) as rows_part_gz"""
-        o = self._rows_opts(sam, blast, cols, lam, K, full_ref, full_read)
-        gz_off, plain_off = (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
-        need = C.c_uint64(0)
-        args = (self.h, int(mates), slot, C.byref(params), index.h, C.byref(o))
-        self._chk(self.L.smr_rows_part_mates_gz(*args, None, 0, gz_off, plain_off, C.byref(need)), "smr_rows_part_mates_gz")
-        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
-        if need.value:
-            self._chk(self.L.smr_rows_part_mates_gz(*args, buf.ctypes.data, need.value, gz_off, plain_off, C.byref(need)), "smr_rows_part_mates_gz")
-        raw = buf.tobytes()
-        return raw[gz_off[0]:gz_off[1]], raw[gz_off[1]:gz_off[2]], [int(x) for x in plain_off]
+        return self._rows("smr_rows_part_mates_gz", int(mates), slot, params, index, sam, blast, cols, lam, K, full_ref, full_read)
 
     def pairwise_part_mates_gz(self, mates, slot, params, index, lam=0.0, K=0.0, full_ref=0, full_read=0):
         """smr_pairwise_part_mates_gz: the text of pairwise_part_mates, compressed on the device -> (gz, plain_bytes) as pairwise_part_gz"""
-        need, plain = C.c_uint64(0), C.c_uint64(0)
-        args = (self.h, int(mates), slot, C.byref(params), index.h, float(lam), float(K), int(full_ref), int(full_read))
-        self._chk(self.L.smr_pairwise_part_mates_gz(*args, None, 0, C.byref(plain), C.byref(need)), "smr_pairwise_part_mates_gz")
-        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
-        if need.value:
-            self._chk(self.L.smr_pairwise_part_mates_gz(*args, buf.ctypes.data, need.value, C.byref(plain), C.byref(need)), "smr_pairwise_part_mates_gz")
-        return buf[:need.value].tobytes(), int(plain.value)
+        return self._pairwise("smr_pairwise_part_mates_gz", int(mates), slot, params, index, lam, K, full_ref, full_read)
 
     def interleave_batch(self, a_pieces, b_pieces):
         """smr_interleave_batch (the seam of the interleave kernel): two equally long lists of bytes objects -> a[0] + b[0] + a[1] + b[1] + ..."""
         n = len(a_pieces)
         if len(b_pieces) != n:
             raise SmrError("interleave_batch: %d pieces against %d" % (n, len(b_pieces)))
-        a_off = np.concatenate([[0], np.cumsum([len(x) for x in a_pieces], dtype=np.uint64)]).astype(np.uint64)
-        b_off = np.concatenate([[0], np.cumsum([len(x) for x in b_pieces], dtype=np.uint64)]).astype(np.uint64)
-        a = np.frombuffer(b"".join(a_pieces) or b"\0", dtype=np.uint8)
-        b = np.frombuffer(b"".join(b_pieces) or b"\0", dtype=np.uint8)
-        u64p = C.POINTER(C.c_uint64)
-        need = C.c_uint64(0)
-        args = (self.h, n, a.ctypes.data, a_off.ctypes.data_as(u64p), b.ctypes.data, b_off.ctypes.data_as(u64p))
-        self._chk(self.L.smr_interleave_batch(*args, None, 0, C.byref(need)), "smr_interleave_batch")
-        buf = np.zeros(max(need.value, 1), dtype=np.uint8)
-        if need.value:
-            self._chk(self.L.smr_interleave_batch(*args, buf.ctypes.data, need.value, C.byref(need)), "smr_interleave_batch")
-        return buf[:need.value].tobytes()
+        (a_off, a), (b_off, b) = _packed(a_pieces), _packed(b_pieces)
+        args = (self.h, n, a.ctypes.data, a_off.ctypes.data_as(U64P), b.ctypes.data, b_off.ctypes.data_as(U64P))
+        return self._fill("smr_interleave_batch", lambda need, out: self.L.smr_interleave_batch(*args, *out, need)).tobytes()
 
     def mates_times(self):
         """HIP-event ms of the last *_mates call: dict(selected, mates, interleave, d2h)"""
@@ -796,10 +675,7 @@ class Engine:
                 blob = np.zeros(1, dtype=np.uint8)
             self._chk(self.L.smr_state_import(self.h, blob.ctypes.data, off.ctypes.data, len(off) - 1), "smr_state_import")
             return
-        off = np.zeros(len(records) + 1, dtype=np.uint64)
-        if records:
-            off[1:] = np.cumsum([len(r) for r in records], dtype=np.uint64)
-        blob = np.frombuffer(b"".join(records) + b"\0", dtype=np.uint8)
+        off, blob = _packed(records)
         self._chk(self.L.smr_state_import(self.h, blob.ctypes.data, off.ctypes.data, len(records)), "smr_state_import")
 
     def export_state(self):
@@ -807,12 +683,7 @@ class Engine:
         is blob[off[i]:off[i + 1]], empty for a read without alignments.  What import_state takes and a state file holds"""
         n = self.n_reads
         off = np.zeros(n + 1, dtype=np.uint64)
-        need = C.c_uint64(0)
-        self._chk(self.L.smr_state_export(self.h, None, 0, off.ctypes.data, n, C.byref(need)), "smr_state_export")
-        blob = np.zeros(need.value, dtype=np.uint8)
-        if need.value:
-            self._chk(self.L.smr_state_export(self.h, blob.ctypes.data, need.value, off.ctypes.data, n, C.byref(need)), "smr_state_export")
-        return blob, off
+        return self._fill("smr_state_export", lambda need, b: self.L.smr_state_export(self.h, *b, off.ctypes.data, n, need)), off
 
     def export_records(self):
         """export_state() cut into one byte string per read: what fetch() + records() give"""
@@ -855,9 +726,9 @@ class Engine:
         """reads: whole FORWARD reads, refs: the reference windows from each alignment's first reference letter on (byte strings in the 0..4
         alphabet), cigars: u32 arrays (len << 4 | op); -> uint32 array (n, 4): n_miss, n_gap, n_match, class 0..3 (smr_idcov_batch)"""
         n = len(reads)
-        ro = np.zeros(n + 1, dtype=np.uint64); fo = np.zeros(n + 1, dtype=np.uint64); co = np.zeros(n + 1, dtype=np.uint64)
-        ro[1:] = np.cumsum([len(x) for x in reads]); fo[1:] = np.cumsum([len(x) for x in refs]); co[1:] = np.cumsum([len(x) for x in cigars])
-        rb = np.frombuffer(b"".join(bytes(x) for x in reads) + b"\0", dtype=np.uint8).copy(); fb = np.frombuffer(b"".join(bytes(x) for x in refs) + b"\0", dtype=np.uint8).copy()
+        (ro, rb), (fo, fb) = _packed(reads), _packed(refs)
+        co = np.zeros(n + 1, dtype=np.uint64)
+        co[1:] = np.cumsum([len(x) for x in cigars])
         cg = np.concatenate([np.asarray(x, dtype=np.uint32) for x in cigars] + [np.zeros(1, dtype=np.uint32)])
         b1 = np.asarray(read_begin, dtype=np.int32); e1 = np.asarray(read_end, dtype=np.int32); rl = np.asarray(readlen, dtype=np.uint32)
         out = np.zeros((max(n, 1), 4), dtype=np.uint32)
@@ -884,25 +755,24 @@ class Engine:
     def fetch(self):
         self._chk(self.L.smr_results_fetch(self.h), "smr_results_fetch")
 
-    def record(self, i):
-        n = self.L.smr_result_record(self.h, i, None, 0)
+    def _record(self, fn, *which):
+        """the record that fn(ctx, *which, buf, cap) serialises: the call returns its size, 0 for a read without one"""
+        n = fn(self.h, *which, None, 0)
         if n == 0:
             return b""
         buf = C.create_string_buffer(n)
-        self.L.smr_result_record(self.h, i, buf, n)
+        fn(self.h, *which, buf, n)
         return buf.raw
+
+    def record(self, i):
+        return self._record(self.L.smr_result_record, i)
 
     def records(self):
         return [self.record(i) for i in range(self.n_reads)]
 
     def record_batch(self, batch, i):
         """record of read i of batch `batch`, whichever batch is selected (smr_result_record_batch: a writer thread's call)"""
-        n = self.L.smr_result_record_batch(self.h, batch, i, None, 0)
-        if n == 0:
-            return b""
-        buf = C.create_string_buffer(n)
-        self.L.smr_result_record_batch(self.h, batch, i, buf, n)
-        return buf.raw
+        return self._record(self.L.smr_result_record_batch, batch, i)
 
     def is_hit(self, i):
         return bool(self.L.smr_result_is_hit(self.h, i))
@@ -913,11 +783,7 @@ class Engine:
         return n.value
 
     def seed_hits(self):
-        n = C.c_uint64()
-        self._chk(self.L.smr_seed_hits_fetch(self.h, None, 0, C.byref(n)), "smr_seed_hits_fetch")
-        arr = np.zeros((max(n.value, 1), 3), dtype=np.uint32)
-        self._chk(self.L.smr_seed_hits_fetch(self.h, arr.ctypes.data, n.value, C.byref(n)), "smr_seed_hits_fetch")
-        return arr[: n.value]
+        return self._fill("smr_seed_hits_fetch", lambda n, b: self.L.smr_seed_hits_fetch(self.h, *b, n), kinds=((np.uint32, 3),), always=True)
 
     def seed_tuples(self):
         """(sorted tuples uint64[n], cbase uint32[nc + 1], meta dict) of the last seed-stage launch (smr_seed_tuples_fetch: a test seam)"""
